@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Conformer-Transducer TS-ASR training step (conformer-t_scratch, T=1000 mel frames, B=32/GPU, bf16).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = TSASR.fit_batch on one synthetic batch resident in HBM: speaker branch + front-end + 12-layer Conformer
@@ -9,7 +9,10 @@ encoder + predictor + fused joint/head + RNN-T loss, backward, gradient all-redu
 Workload = BASELINE.json configs[1]: mel N(0,1) [32,1000,80] (already normalised; fed after A2),
 enrollment mel [32,500,80], tokens randint(1,29) [32,120], all lengths 1.0, injection_mode=cat, dropout 0.1 active,
 grad_accumulation_factor 1, per-rank data seed 1234+rank, weights random-init (seed 0).
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: the headline figure (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and the run's
+settings. A plain run does only that: set up, warm up, time the steps, dump the outputs (--dump-outputs), print. --full adds what takes runs of
+its own: per-kernel HIP-event durations (`hip_kernels`, `roofline`, `rnnt_joint_loss_ms`) from 3 instrumented eager steps after the timed
+region, the Fbank / augmentation timings, the all-reduce probe (`comm`, N > 1) and the CPU baseline (`cpu_baseline`).
 """
 import argparse
 import importlib
@@ -205,6 +208,33 @@ def allreduce_probe(brain, torch, world, reps=5):
     return e0.elapsed_time(e1) / reps, direct, buf.numel() * 4
 
 
+def dump_outputs(brain, loss, out_dir, sample=1 << 22):
+    """--dump-outputs DIR: what the last timed step handed its caller - the loss, the global gradient norm the clip measured, and the updated
+    parameters and AdamW moments - as DIR/<name>.npy (float64 scalars, float32 arrays). The parameter-shaped arrays hold 51 M values at
+    configs[1]: a fixed sample (seed 0, <= `sample` positions, 16 MB per array) over the trainable parameters in name order, located through the
+    arena's offsets - the same positions whatever order the arena laid the parameters out in."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    a, opt = brain.arena, brain.optimizer
+    named = sorted((n, p) for n, p in brain.modules.named_parameters() if id(p) in a.offset)
+    sizes = np.array([p.numel() for _, p in named], np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    total = int(sizes.sum())
+    idx = np.arange(total) if total <= sample else np.unique(np.random.default_rng(0).integers(0, total, sample))
+    j = np.searchsorted(starts, idx, side="right") - 1
+    offsets = np.array([a.offset[id(p)] for _, p in named], np.int64)
+    pos = torch.from_numpy(offsets[j] + (idx - starts[j])).to(a.flat_params.device)
+    out = {"loss": loss.detach().double().reshape(1), "grad_norm": opt.last_grad_norm.detach().double().reshape(1),
+           "params_sample": a.flat_params[pos]}
+    if hasattr(opt, "exp_avg"):
+        out["adam_exp_avg_sample"] = opt.exp_avg[pos]
+        out["adam_exp_avg_sq_sample"] = opt.exp_avg_sq[pos]
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(out))} ({len(idx)} of {total} parameter positions)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -217,6 +247,9 @@ def main():
     ap.add_argument("--eager", action="store_true", help="do not capture the step into a hipGraph")
     ap.add_argument("--config", default="scratch", choices=sorted(WORKLOADS), help="workload (default: the headline, BASELINE.json configs[1])")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch of the workload (pricing runs only: the line is then NOT the headline configuration and says so)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel timings + roofline, Fbank / augmentation timings, all-reduce probe "
+                    "(N > 1) and CPU baseline (runs of their own after the timed region)")
     args = ap.parse_args()
     wl = dict(WORKLOADS[args.config])
     if args.batch:
@@ -271,7 +304,7 @@ def main():
         log(f"warm-up step {i + 1} done" + (" (hipGraph captured)" if brain._graph is not None else ""))
     sync()
     graphed = brain._graph is not None
-    prof.ENABLED = not graphed          # HIP events cannot bracket kernels inside a replayed graph
+    prof.ENABLED = args.full and not graphed    # HIP events cannot bracket kernels inside a replayed graph
     prof.reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -281,7 +314,9 @@ def main():
     prof.ENABLED = False
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
     loss = loss.clone()
-    if graphed:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(brain, loss, args.dump_outputs)
+    if args.full and graphed:
         # per-kernel durations: the same step, same process, run eagerly right after the timed region with HIP events
         # around every hand-written kernel launch (the graph replays the very same kernels with the same arguments)
         brain._graph_mode = False
@@ -292,7 +327,7 @@ def main():
         prof.ENABLED = False
         brain._graph_mode = True
     feat_ms, aug_ms = None, {}
-    if rank == 0:   # Fbank + sentence norm are timed separately, on wav ~ N(0, 0.1^2) [32, 159840] (the step is fed features)
+    if args.full and rank == 0:   # Fbank + sentence norm are timed separately, on wav ~ N(0, 0.1^2) [32, 159840] (the step is fed features)
         wav = torch.randn(B_LOCAL, T_MEL * 160 - 160, device=device) * 0.1
         wlens = torch.ones(B_LOCAL, device=device)
         fx, nm = brain.modules.feature_extractor, brain.modules.normalizer
@@ -325,7 +360,7 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     comm_info = {}
-    if world > 1:
+    if args.full and world > 1:
         ar_ms, direct, nbytes = allreduce_probe(brain, torch, world)
         dpm = importlib.import_module(PKG + ".dp")
         comm_info = {"backend": torch.distributed.get_backend(), "rccl_direct_ranks": int(dpm._DIRECT["ranks"]), "collectives_in_graph": bool(brain._graph_comm()) if brain._graph is not None else False,
@@ -336,50 +371,11 @@ def main():
     # per-launch durations: mean of the HIP-event brackets of every instrumented launch, NET of the empty event-pair time measured in
     # this process (prof.event_overhead_ms x 0.8, ~3 us: the bracket's own two timestamp packets) - without it the brackets read 17 us
     # where rocprofv3 (profiles/r04_kernel_trace.md) reads 11.7 us for the same launches; no fastest-of-N
-    kern = prof.collect(subtract_overhead=True, repeats=3 if graphed else args.steps, fastest=False)
+    kern = prof.collect(subtract_overhead=True, repeats=3 if graphed else args.steps, fastest=False) if args.full else {}
 
     if rank == 0:
         frames = world * B_LOCAL * T_MEL * args.steps
         ms_step = elapsed / args.steps * 1e3
-        ab = algorithmic_bytes(B_LOCAL, T_MEL // 4, U + 1)
-        wk = prof.work()
-        wb = prof.algorithmic_bytes()
-        fam = {}
-        for k, (n, ms) in kern.items():
-            e = {"launches": n, "avg_ms": round(ms, 4)}
-            if k in ab and ms > 0:
-                e["algorithmic_GBps"] = round(ab[k] / (ms * 1e-3) / 1e9, 1)
-            if wk.get(k, 0) > 0 and ms > 0:
-                e["avg_GFLOP_per_launch"] = round(wk[k] / n / 1e9, 3)
-                e["TFLOPps"] = round(wk[k] / n / (ms * 1e-3) / 1e12, 1)
-            if wb.get(k, 0) > 0:
-                e["algorithmic_MB_per_launch"] = round(wb[k] / n / 1e6, 1)
-            fam[k] = e
-        # dominant hand-written kernel = largest share of the step among the instrumented launches
-        dom = max(fam, key=lambda k: fam[k]["avg_ms"] * fam[k]["launches"], default=None)
-        latency_bound = None
-        if dom is not None and "TFLOPps" not in fam[dom] and dom not in ab:
-            # (long-form, B = 1: the largest launch is a chain of dependent steps - persistent LSTM / RNN-T lattice - priced by steps, not by
-            # flops or bytes: the roofline object then describes the largest kernel that has a flop or byte model, and says so)
-            latency_bound = dom
-            cands = [k for k in fam if "TFLOPps" in fam[k] or k in ab]
-            dom = max(cands, key=lambda k: fam[k]["avg_ms"] * fam[k]["launches"], default=None)
-        roof = None
-        if dom is not None and "TFLOPps" in fam[dom]:
-            roof = {"kernel": dom, "bound": "mfma", "achieved": fam[dom]["TFLOPps"], "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(fam[dom]["TFLOPps"] / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None,
-                    "algorithmic_flops_per_launch": fam[dom]["avg_GFLOP_per_launch"] * 1e9, "avg_launch_ms": fam[dom]["avg_ms"],
-                    "note": "dominant kernel = the rocprofv3 kernel name (template instantiation) with the largest share of the step among the hand-written launches; achieved = sum of 2*M*N*K of its launches / sum of their HIP-event durations on the launch stream (mean over 3 instrumented eager steps of this process, net of the measured empty event-pair time: event_pair_overhead_ms)", "event_pair_overhead_ms": round(prof.out_overhead[0], 5)}
-        elif dom is not None and dom in ab:
-            ach = ab[dom] / (fam[dom]["avg_ms"] * 1e-3) / 1e9
-            roof = {"kernel": dom, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                    "algorithmic_bytes_per_launch": ab[dom], "avg_launch_ms": fam[dom]["avg_ms"]}
-        if roof is not None:   # HBM-side bytes per launch from the committed rocprofv3 --pmc passes (tools/pmc_summary.py), newest round
-            roof["traffic"], roof["traffic_source"] = pmc_traffic(roof["kernel"])
-            if latency_bound is not None:
-                roof["largest_launch_without_flop_or_byte_model"] = {"kernel": latency_bound, **fam[latency_bound]}
-        rnnt_ms = sum(fam[k]["avg_ms"] for k in ("joint_fwd", "rnnt_loss_fwd", "rnnt_loss_bwd", "joint_bwd") if k in fam)
         out = {
             "metric": f"utterance-frames/sec ({ {'pretrained': 'conformer-t_wavlm', 'none': 'conformer-t_none'}.get(args.config, 'conformer-t_scratch') } training step, T={T_MEL}, B={B_LOCAL}/GPU)",
             "value": round(frames / elapsed, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -389,17 +385,59 @@ def main():
                        "global_batch": world * B_LOCAL, "grad_accumulation_factor": args.accum, "parallelism": f"dp{world}",
                        "hip_graph": brain._graph is not None},
             "frames_per_sec_per_gpu": round(frames / elapsed / world, 1),
-            "rnnt_joint_loss_ms": round(rnnt_ms, 4),
-            "fbank_sentnorm_ms": None if feat_ms is None else round(feat_ms, 4),
-            **aug_ms,
             "loss": round(float(loss), 4), "nonfinite_steps": nonfinite,
-            "hip_kernels": fam,
-            "roofline": roof,
         }
-        if comm_info:
-            out["comm"] = comm_info
-        if not args.no_cpu_baseline and world == 1 and args.config == "scratch":
-            out["cpu_baseline"] = cpu_baseline(brain, torch)
+        if args.full:
+            ab = algorithmic_bytes(B_LOCAL, T_MEL // 4, U + 1)
+            wk = prof.work()
+            wb = prof.algorithmic_bytes()
+            fam = {}
+            for k, (n, ms) in kern.items():
+                e = {"launches": n, "avg_ms": round(ms, 4)}
+                if k in ab and ms > 0:
+                    e["algorithmic_GBps"] = round(ab[k] / (ms * 1e-3) / 1e9, 1)
+                if wk.get(k, 0) > 0 and ms > 0:
+                    e["avg_GFLOP_per_launch"] = round(wk[k] / n / 1e9, 3)
+                    e["TFLOPps"] = round(wk[k] / n / (ms * 1e-3) / 1e12, 1)
+                if wb.get(k, 0) > 0:
+                    e["algorithmic_MB_per_launch"] = round(wb[k] / n / 1e6, 1)
+                fam[k] = e
+            # dominant hand-written kernel = largest share of the step among the instrumented launches
+            dom = max(fam, key=lambda k: fam[k]["avg_ms"] * fam[k]["launches"], default=None)
+            latency_bound = None
+            if dom is not None and "TFLOPps" not in fam[dom] and dom not in ab:
+                # (long-form, B = 1: the largest launch is a chain of dependent steps - persistent LSTM / RNN-T lattice - priced by steps, not by
+                # flops or bytes: the roofline object then describes the largest kernel that has a flop or byte model, and says so)
+                latency_bound = dom
+                cands = [k for k in fam if "TFLOPps" in fam[k] or k in ab]
+                dom = max(cands, key=lambda k: fam[k]["avg_ms"] * fam[k]["launches"], default=None)
+            roof = None
+            if dom is not None and "TFLOPps" in fam[dom]:
+                roof = {"kernel": dom, "bound": "mfma", "achieved": fam[dom]["TFLOPps"], "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(fam[dom]["TFLOPps"] / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None,
+                        "algorithmic_flops_per_launch": fam[dom]["avg_GFLOP_per_launch"] * 1e9, "avg_launch_ms": fam[dom]["avg_ms"],
+                        "note": "dominant kernel = the rocprofv3 kernel name (template instantiation) with the largest share of the step among the hand-written launches; achieved = sum of 2*M*N*K of its launches / sum of their HIP-event durations on the launch stream (mean over 3 instrumented eager steps of this process, net of the measured empty event-pair time: event_pair_overhead_ms)", "event_pair_overhead_ms": round(prof.out_overhead[0], 5)}
+            elif dom is not None and dom in ab:
+                ach = ab[dom] / (fam[dom]["avg_ms"] * 1e-3) / 1e9
+                roof = {"kernel": dom, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                        "algorithmic_bytes_per_launch": ab[dom], "avg_launch_ms": fam[dom]["avg_ms"]}
+            if roof is not None:   # HBM-side bytes per launch from the committed rocprofv3 --pmc passes (tools/pmc_summary.py), newest round
+                roof["traffic"], roof["traffic_source"] = pmc_traffic(roof["kernel"])
+                if latency_bound is not None:
+                    roof["largest_launch_without_flop_or_byte_model"] = {"kernel": latency_bound, **fam[latency_bound]}
+            rnnt_ms = sum(fam[k]["avg_ms"] for k in ("joint_fwd", "rnnt_loss_fwd", "rnnt_loss_bwd", "joint_bwd") if k in fam)
+            out.update({
+                "rnnt_joint_loss_ms": round(rnnt_ms, 4),
+                "fbank_sentnorm_ms": None if feat_ms is None else round(feat_ms, 4),
+                **aug_ms,
+                "hip_kernels": fam,
+                "roofline": roof,
+            })
+            if comm_info:
+                out["comm"] = comm_info
+            if not args.no_cpu_baseline and world == 1 and args.config == "scratch":
+                out["cpu_baseline"] = cpu_baseline(brain, torch)
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

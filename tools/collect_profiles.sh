@@ -4,7 +4,7 @@ set -e
 TAG=${1:-r02}
 O=gpurun_out/$TAG
 {
-  echo "# $TAG kernel trace: rocprofv3 --kernel-trace --stats of \`python bench.py --steps 10 --warmup 3 --no-cpu-baseline\`"
+  echo "# $TAG kernel trace: rocprofv3 --kernel-trace --stats of \`python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline\`"
   echo
   echo "Per-kernel rows are normalised to ONE training step (the trace holds 17: 3 warm-up + 1 capture pass + 3 instrumented eager + 10 timed"
   echo "replays); n = launches per step, avg = mean rocprofv3 duration of a launch. Summary by tools/trace_summary.py, per-queue timeline"
