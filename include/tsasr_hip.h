@@ -461,6 +461,36 @@ int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, con
                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
                         int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream);
 
+/* The same search over one chunk of a stream (csrc/search.hip): state fp32 [B, 2H + J + 4] (caller-owned, zeroed before the first chunk)
+ * carries h, c, the projected predictor output, the last symbol, the running log-prob sum and a primed flag between calls; n_valid int32 [B]
+ * = frames of this chunk to decode per utterance (preds of the others are -1; a zero count leaves the state untouched); logp_sum [B]
+ * receives the running sum. A tensor decoded in pieces gives the bits of one tsasr_greedy_decode call over it. */
+int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                               const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
+                               const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
+                               float slope, int io_dtype, int wdtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Chunk-by-chunk inference of the causal encoder (csrc/stream.hip); eval only, no backward.
+ * Relative-position attention of a chunk of C query frames at absolute offset t0: qkv [B,C,H,3*Dh] (RelPosMHAXL's per-head Q|K|V);
+ * k_cache / v_cache [B,H,Tmax,Dh] (io_dtype) hold frames 0 .. t0-1 and receive the chunk's K, V at rows t0 .. t0+C-1 (t0 + C <= Tmax);
+ * pk_half [Tmax, H*Dh] = linear_pos(PE(d)), d = 0 .. Tmax-1 (RelPosEncXL's table is symmetric: the offline row j - i + T - 1 is row
+ * |i - j| here); bias_u / bias_v fp32 [H*Dh] as tsasr_relpos_attn_fwd; key_lens int32 [B] (absolute valid frames) or NULL; causal as
+ * tsasr_relpos_attn_fwd on absolute positions (1: look-ahead mask, c > 1: chunks of c frames). out [B,C,H*Dh]. Dh <= 64; bf16 with
+ * Dh = 32 / 64 on the matrix cores (bf16 operands, fp32 softmax and sums), fp32 in exact fp32 arithmetic. workspace (>= tsasr_relpos_attn_stream_workspace_bytes, which is 0 when no split is made; NULL = no
+ * split): small batches with long caches split the keys across workgroups, merged by a second launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_relpos_attn_stream_workspace_bytes(int B, int C, int H, int Dh, int Tmax);
+int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u, const float *bias_v,
+                                 const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax, int t0, int causal, float scale,
+                                 int io_dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* tsasr_convmod_fwd with causal = 1 on a chunk y2 [B,C,2D], no saved tensors: the K-1 GLU rows in front of the chunk come from
+ * hist_in fp32 [B,K-1,D] (zeros = the offline zero pad), the last K-1 GLU rows of [history | chunk] are written to hist_out (a second
+ * buffer: swap the two per chunk). z [B,C,D] (io_dtype). */
+int tsasr_convmod_stream_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
+                             const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
+                             float slope, int io_dtype, void *stream);
+
 int tsasr_count_nonfinite(const float *x, int n, int *counter, void *stream);
 
 /* Direct RCCL gradient all-reduce over xGMI (csrc/comm.hip): replaces the NCCL calls behind the reference's per-module

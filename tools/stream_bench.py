@@ -1,0 +1,129 @@
+"""Per-chunk cost of streaming transcription (ts-asr_amd/streaming.py) at BASELINE.json configs[1] model size (d_model 256, 12 layers,
+4 heads), causal encoder with block-causal attention over chunks of 40 frames, bf16, deterministic weights.
+
+    python tools/stream_bench.py [--B 1 32] [--t0 0 1000 3960] [--reps 20] [--json out.json]
+    python tools/stream_bench.py --profile-chunks 20 --B 32 --t0 3960     # under rocprofv3 --kernel-trace --stats: 20 chunks and nothing else timed
+
+A chunk is one push of 160 mel frames = 40 encoder frames = 1.6 s of audio. The time of a push is host wall-clock from the call to
+the return of its new tokens (the push reads its symbols back, so the device work is included), the median over --reps pushes. For
+each offset t0 the stream is moved there by setting its frame counter (the cost of a chunk does not depend on what the cache holds).
+Kernel launches per chunk are counted with torch.profiler. Real-time factor = time per chunk / 1.6 s.
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "ts-asr_amd"
+CHUNK_MEL, CHUNK_ENC, AUDIO_MS = 160, 40, 1600.0
+
+
+def build(device):
+    from oracle.golden_recipe import load_det_weights
+    hp = importlib.import_module(PKG + ".hparams")
+    tsasr = importlib.import_module(PKG + ".recipes.tsasr")
+    ov = dict(input_is_feats=True, compute_dtype="bf16", causal_encoder=True, frontend_padding="causal", attention_chunk_size=40, dropout=0.0)
+    with open(os.path.join(ROOT, "hparams", "conformer-t_scratch_mi355x.yaml")) as f:
+        h = hp.load_hyperpyyaml(f, ov)
+    for name, mod in h["modules"].items():
+        if isinstance(mod, torch.nn.Module):
+            load_det_weights(mod, name + ".")
+    brain = tsasr.TSASR(h["modules"], h["opt_class"], h, {"device": device, "compute_dtype": "bf16"})
+    brain.modules.eval()
+    return brain, h
+
+
+def make_stream(streaming, brain, B, max_frames, device):
+    D = brain.modules.encoder.d_model
+    g = torch.Generator(device="cpu").manual_seed(7)
+    spk = (torch.randn(B, 1, D, generator=g) * 0.5).to(device)
+    st = streaming.StreamingTranscriber(brain)
+    st.start(B, max_frames, speaker_embs=spk)
+    feats = torch.randn(B, CHUNK_MEL, 80, generator=g).to(device)
+    return st, feats
+
+
+def place(st, t0):
+    """Move the stream to encoder frame t0 (the caches keep whatever they hold)."""
+    st.enc_state["t0"] = t0
+    st.mel.fill_(4 * t0)
+
+
+def count_launches(st, feats, t0):
+    from torch.profiler import ProfilerActivity, profile
+    place(st, t0)
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as p:
+        st.push(feats)
+        torch.cuda.synchronize()
+    kinds = {}
+    n = 0
+    for e in p.events():
+        if getattr(e, "device_type", None) is not None and str(e.device_type).endswith("CUDA") and e.name and "Memcpy" not in e.name \
+                and "Memset" not in e.name:
+            n += 1
+            kinds[e.name] = kinds.get(e.name, 0) + 1
+    return n, kinds
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, nargs="+", default=[1, 32])
+    ap.add_argument("--t0", type=int, nargs="+", default=[0, 1000, 3960])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--max-frames", type=int, default=4000)
+    ap.add_argument("--no-split", action="store_true", help="attention without the key split (prices the split)")
+    ap.add_argument("--profile-chunks", type=int, default=0)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    device = "cuda:0"
+    streaming = importlib.import_module(PKG + ".streaming")
+    ops = importlib.import_module(PKG + ".ops")
+    if a.no_split:
+        ops.relpos_attn_stream_workspace = lambda *args, **kw: None
+    brain, _ = build(device)
+    results = []
+    with torch.no_grad():
+        for B in a.B:
+            st, feats = make_stream(streaming, brain, B, a.max_frames, device)
+            for _ in range(0 if a.profile_chunks else 3):     # warm-up: allocations, workspaces, first launches
+                st.push(feats)
+            if a.profile_chunks:
+                for t0 in a.t0:
+                    for _ in range(a.profile_chunks):
+                        if st.enc_state is not None:
+                            place(st, t0)
+                        st.push(feats)                          # (the first push allocates the stream and runs at t0 = 0)
+                torch.cuda.synchronize()
+                print(json.dumps({"profiled_chunks": a.profile_chunks, "B": B, "t0": a.t0}))
+                continue
+            for t0 in a.t0:
+                times = []
+                for _ in range(a.reps):
+                    place(st, t0)
+                    torch.cuda.synchronize()
+                    s = time.perf_counter()
+                    st.push(feats)
+                    times.append((time.perf_counter() - s) * 1e3)
+                try:
+                    n, _ = count_launches(st, feats, t0)
+                except Exception as e:                          # (profiler not usable: report the timing anyway)
+                    n = f"n/a ({type(e).__name__})"
+                med = statistics.median(times)
+                r = {"B": B, "t0": t0, "ms_per_chunk_median": round(med, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+                     "kernel_launches_per_chunk": n, "rtf": round(med / AUDIO_MS, 5), "split": not a.no_split}
+                print(json.dumps(r), flush=True)
+                results.append(r)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"workload": "streaming configs[1] causal chunk 40, bf16, 160 mel frames per push", "results": results}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -164,6 +164,61 @@ class ConformerEncoder(nn.Module):
         state.update(x=x, pre=pre, next=i)
         return state
 
+    # ---- chunk-by-chunk inference of a causal encoder --------------------------------------------------------------------------
+    def init_stream(self, B, max_frames, dtype=None, device=None):
+        """Caches for a batch of B streams of up to ``max_frames`` encoder frames: per layer a K/V cache and two conv histories, and
+        the half positional table pk_half = linear_pos(PE(d)), d = 0 .. max_frames-1, of every layer (one ops.project_many launch over
+        the non-negative half of RelPosEncXL's symmetric table)."""
+        if not self.causal:
+            raise ValueError("init_stream: only a causal encoder (causal=True) can run as a stream")
+        from .nnet import _pos_cd, compute_dtype
+        dtype = dtype or compute_dtype()
+        device = device or self.norm.norm.weight.device
+        Tm = int(max_frames)
+        pos = self.positional_encoding(torch.empty(1, Tm, 0, device=device))     # [1, 2Tm-1, D]: row Tm-1+d = PE(d)
+        half = _pos_cd(pos)[Tm - 1:]
+        if half.dtype != dtype:
+            half = half.to(dtype)
+        with torch.no_grad():
+            pks = ops.project_many(half.contiguous(), [layer.mha_layer.linear_pos.weight for layer in self.layers])
+            if pks is None:
+                pks = [ops.matmul_nt(half.contiguous(), layer.mha_layer.linear_pos.weight) for layer in self.layers]
+        layers = []
+        for layer, pk in zip(self.layers, pks):
+            st = layer.init_stream(B, Tm, dtype, device)
+            st["pk"] = pk.contiguous()
+            layers.append(st)
+        return {"t0": 0, "max_frames": Tm, "B": int(B), "layers": layers}
+
+    def forward_chunk(self, src_chunk, state, speaker_embs=None, speaker_embs_length=None, enc_lens=None):
+        """Encoder output [B,C,D] of the next C front-end frames ``src_chunk`` [B,C,F',C'] of every stream (same speaker injection and
+        final norm as forward()). ``enc_lens`` int32 [B]: valid encoder frames of each stream so far (keys at or past it are masked;
+        None = all frames valid). Advances state["t0"] by C. Eval only."""
+        if not self.causal:
+            raise ValueError("forward_chunk: only a causal encoder (causal=True) can run as a stream")
+        if torch.is_grad_enabled() or self.training:
+            raise RuntimeError("ConformerEncoder.forward_chunk is inference only (eval mode, under torch.no_grad())")
+        C.require_gpu(src_chunk)
+        if src_chunk.ndim == 4:
+            b, t, c1, c2 = src_chunk.shape
+            src_chunk = src_chunk.reshape(b, t, c1 * c2)
+        t0, Cn = state["t0"], src_chunk.shape[1]
+        blk = max(int(getattr(self.layers[0], "chunk_size", 0) or 0), 1)
+        if t0 % blk:    # block-causal attention: a frame sees its whole block of `chunk_size` frames, so a chunk cannot end inside one
+            raise ValueError(f"forward_chunk: with attention chunks of {blk} frames every chunk but the last must hold a multiple of {blk} frames")
+        if t0 + Cn > state["max_frames"]:
+            raise ValueError(f"stream longer than init_stream's max_frames ({t0} + {Cn} > {state['max_frames']})")
+        key_lens = None if enc_lens is None else enc_lens.to(device=src_chunk.device, dtype=torch.int32)
+        x = self.custom_src_module(_cd(src_chunk))
+        if -1 in self.injection_after and speaker_embs is not None:
+            x = self._inject_speaker_emb(x, speaker_embs, speaker_embs_length)
+        for i, layer in enumerate(self.layers):
+            x = layer.forward_chunk(x, state["layers"][i], t0, key_lens)
+            if i in self.injection_after and speaker_embs is not None:
+                x = self._inject_speaker_emb(x, speaker_embs, speaker_embs_length)
+        state["t0"] = t0 + Cn
+        return self.norm(x)
+
     def _inject_speaker_emb(self, src, spk, spk_len):
         spk = _cd(spk)
         if self.injection_mode in ("prod", "sum"):

@@ -31,6 +31,8 @@ struct GreedyArgs {
     float *logp_sum;            // [B]: sum of the emitted symbols' log-probabilities
     int B, T, J, H, E, V, blank;
     float slope;
+    float *state;               // STREAM: [B, S] fp32, S = 2H + J + 4 (tsasr_greedy_decode_stream)
+    const int *n_valid;         // STREAM: [B] frames of this chunk to decode
 };
 
 template <typename WT> __device__ __forceinline__ void ld4w(const WT *p, float (&o)[4]);
@@ -97,7 +99,10 @@ __device__ __forceinline__ void gemv_rows(const WT *__restrict__ W, int rows, in
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
-template <typename T, typename WT>
+// STREAM: the predictor state of utterance b is loaded from / stored to A.state[b] = [h (H) | c (H) | pn (J) | last symbol | logp sum |
+// primed flag | 0]; a state with primed flag 0 (all zeros) is primed with the blank symbol first, as the one-call decoder does. Only the
+// first n_valid[b] frames are decoded (preds of the rest: -1); with n_valid[b] == 0 the state is neither read for priming nor written.
+template <typename T, typename WT, bool STREAM>
 __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const GreedyArgs A) {
     extern __shared__ __attribute__((aligned(16))) float gs[];
     float *h = gs, *c = h + A.H, *pn = c + A.H, *z = pn + A.J, *gates = z + A.J, *x = gates + 4 * A.H, *logits = x + 64;
@@ -105,12 +110,31 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
     const int b = blockIdx.x, tid = threadIdx.x;
     const T *enc = (const T *)A.enc + (size_t)b * A.T * A.J;
     const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
-    for (int i = tid; i < A.H; i += GREEDY_THREADS) h[i] = c[i] = 0.f;
-    if (tid == 0) s_tok = A.blank;
     float lsum = 0.f;
+    int tbeg = -1, tend = A.T;
+    float *st = nullptr;
+    if (STREAM) {
+        const int S = 2 * A.H + A.J + 4;
+        st = A.state + (size_t)b * S;
+        tend = min(max(A.n_valid[b], 0), A.T);
+        for (int t = tid; t < A.T; t += GREEDY_THREADS)
+            if (t >= tend) A.preds[(size_t)b * A.T + t] = -1;
+        if (tend == 0) {                            // workgroup-uniform: nothing to decode, the state stays as it is
+            if (tid == 0) A.logp_sum[b] = st[2 * A.H + A.J + 1];
+            return;
+        }
+        const bool primed = st[2 * A.H + A.J + 2] != 0.f;
+        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) gs[i] = st[i];   // h | c | pn are contiguous in LDS and in the state
+        if (tid == 0) s_tok = primed ? (int)st[2 * A.H + A.J] : A.blank;
+        lsum = st[2 * A.H + A.J + 1];
+        if (primed) tbeg = 0;
+    } else {
+        for (int i = tid; i < A.H; i += GREEDY_THREADS) h[i] = c[i] = 0.f;
+        if (tid == 0) s_tok = A.blank;
+    }
     __syncthreads();
     // step(-1): the predictor is primed with the blank symbol (transducer.py:160-170); then one pass per frame
-    for (int t = -1; t < A.T; ++t) {
+    for (int t = tbeg; t < tend; ++t) {
         int tok = s_tok;                        // symbol to feed the predictor with (every thread reads the same LDS word)
         bool advance = (t < 0);
         if (t >= 0) {
@@ -156,6 +180,15 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
         }
     }
     if (tid == 0) A.logp_sum[b] = lsum;
+    if (STREAM) {
+        __syncthreads();
+        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) st[i] = gs[i];
+        if (tid == 0) {
+            st[2 * A.H + A.J] = (float)s_tok;
+            st[2 * A.H + A.J + 1] = lsum;
+            st[2 * A.H + A.J + 2] = 1.f;
+        }
+    }
 }
 
 }  // namespace
@@ -176,11 +209,12 @@ int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, con
     TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "tsasr_greedy_decode: bad dtype");
     const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + 64 + 64) * sizeof(float);
     TSASR_CHECK_ARG(lds <= 160 * 1024, "tsasr_greedy_decode: H=%d J=%d need %zu B of LDS", H, J, lds);
-    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope};
+    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope,
+                 nullptr, nullptr};
     hipStream_t st = (hipStream_t)stream;
 #define GREEDY(TT, WW)                                                                                                          \
     {                                                                                                                           \
-        auto kern = greedy_decode_kernel<TT, WW>;                                                                               \
+        auto kern = greedy_decode_kernel<TT, WW, false>;                                                                               \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                                           \
     }
@@ -188,6 +222,37 @@ int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, con
     else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
 #undef GREEDY
     TSASR_CHECK_LAUNCH("tsasr_greedy_decode");
+    return 0;
+}
+
+/* tsasr_greedy_decode over one chunk of a stream: state fp32 [B, 2H + J + 4] (caller-owned, zeroed before the first chunk) carries the
+ * predictor (h, c, projected output), the last symbol, the running log-prob sum and a primed flag between calls; n_valid int32 [B] =
+ * frames of this chunk to decode per utterance (preds of the others are -1, and a zero count leaves the state untouched). logp_sum [B]
+ * receives the running sum. Decoding a tensor in pieces gives the bits of one tsasr_greedy_decode call over it. */
+int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                               const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state, const int32_t *n_valid,
+                               int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype,
+                               int wdtype, void *stream) {
+    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && state && n_valid && preds && logp_sum, "tsasr_greedy_decode_stream: null pointer");
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
+                    "tsasr_greedy_decode_stream: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", B, T, J, H, E, V, blank);
+    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "tsasr_greedy_decode_stream: J=%d H=%d above 1024", J, H);
+    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "tsasr_greedy_decode_stream: bad dtype");
+    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + 64 + 64) * sizeof(float);
+    TSASR_CHECK_ARG(lds <= 160 * 1024, "tsasr_greedy_decode_stream: H=%d J=%d need %zu B of LDS", H, J, lds);
+    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope,
+                 state, n_valid};
+    hipStream_t st = (hipStream_t)stream;
+#define GREEDY(TT, WW)                                                                                                          \
+    {                                                                                                                           \
+        auto kern = greedy_decode_kernel<TT, WW, true>;                                                                         \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                                \
+    }
+    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) GREEDY(float, float) else GREEDY(float, bf16_t) }
+    else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
+#undef GREEDY
+    TSASR_CHECK_LAUNCH("tsasr_greedy_decode_stream");
     return 0;
 }
 

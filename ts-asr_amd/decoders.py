@@ -52,21 +52,10 @@ class TransducerBeamSearcher(torch.nn.Module):
     @torch.no_grad()
     def _greedy_on_device(self, tn_output):
         from . import _capi as C
-        emb, dec, proj = self.decode_network_lst
-        head = self.classifier_network[0]
         B, T, J = tn_output.shape
         enc = tn_output.contiguous()
-        f = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
-        rnn = dec.rnn
-        mats = [rnn.weight_ih_l0, rnn.weight_hh_l0, proj.w.weight, head.w.weight]
-        if enc.dtype == torch.bfloat16:       # the training step's bf16 shadows (or a cast) - half the bytes per predictor step
-            from .ops import _bf16_weight
-            mats, wdt = [_bf16_weight(m).contiguous() for m in mats], C.BF16
-        else:
-            mats, wdt = [f(m) for m in mats], C.F32
-        table = f(emb.Embedding.weight)
-        b_ih, b_hh = (f(rnn.bias_ih_l0), f(rnn.bias_hh_l0)) if rnn.bias else (None, None)
-        b_proj, b_head = f(proj.w.bias), f(head.w.bias)
+        rnn = self.decode_network_lst[1].rnn
+        table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
         preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
         logp = torch.empty(B, dtype=torch.float32, device=enc.device)
         C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
@@ -76,6 +65,70 @@ class TransducerBeamSearcher(torch.nn.Module):
         rows = preds.cpu()
         hyps = [[int(v) for v in row[row >= 0]] for row in rows]
         return hyps, logp.exp().mean(), None, None
+
+    def _device_greedy_args(self, enc):
+        """(embedding table, [W_ih, W_hh, W_proj, W_head], b_ih, b_hh, b_proj, b_head, weight dtype) as csrc/search.hip reads them."""
+        from . import _capi as C
+        emb, dec, proj = self.decode_network_lst
+        head = self.classifier_network[0]
+        f = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+        rnn = dec.rnn
+        mats = [rnn.weight_ih_l0, rnn.weight_hh_l0, proj.w.weight, head.w.weight]
+        if enc.dtype == torch.bfloat16:
+            from .ops import _bf16_weight
+            mats, wdt = [_bf16_weight(m).contiguous() for m in mats], C.BF16
+        else:
+            mats, wdt = [f(m) for m in mats], C.F32
+        b_ih, b_hh = (f(rnn.bias_ih_l0), f(rnn.bias_hh_l0)) if rnn.bias else (None, None)
+        return f(emb.Embedding.weight), mats, b_ih, b_hh, f(proj.w.bias), f(head.w.bias), wdt
+
+    def greedy_stream(self, enc_chunk, state=None, n_valid=None):
+        """Greedy search over the next frames of a batch of streams: enc_chunk [B,C,J] (the encoder_proj output of one chunk), ``state``
+        the value returned by the previous call (None: start of the streams, the predictor is primed with blank as in the one-call
+        search), n_valid int32 [B] = frames of this chunk that belong to each stream (None: all C). Frames past a stream's count are not
+        decoded and leave its state untouched. Returns (new symbols of each stream, state); state["logp_sum"] is the running sum of
+        the emitted symbols' log-probabilities. Decoding a sequence in chunks gives the same symbols as one call over it: the
+        device kernel (csrc/search.hip) carries the predictor state bit for bit, the step-wise loop carries it as tensors."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("greedy_stream is inference only: run it under torch.no_grad()")
+        B, T, _ = enc_chunk.shape
+        dev = enc_chunk.device
+        nv = torch.full((B,), T, dtype=torch.int32, device=dev) if n_valid is None else n_valid.to(device=dev, dtype=torch.int32)
+        if self._device_greedy_ok(enc_chunk):
+            from . import ops
+            enc = enc_chunk.contiguous()
+            table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)
+            if state is None:
+                S = ops.greedy_stream_state_size(mats[1].shape[1], enc.shape[-1])
+                state = {"dev": torch.zeros(B, S, dtype=torch.float32, device=dev)}
+            preds, logp = ops.greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state["dev"], nv, self.blank_id,
+                                                   self.tjoint.nonlinearity.negative_slope, wdt)
+            state["logp_sum"] = logp
+            rows = preds.cpu()
+            return [[int(v) for v in row[row >= 0]] for row in rows], state
+        if state is None:
+            tok = torch.full((B, 1), self.blank_id, dtype=torch.long, device=dev)
+            out_pn, hidden = self._pn(tok, None)
+            state = {"tok": tok, "out_pn": out_pn, "hidden": hidden, "logp_sum": torch.zeros(B, device=dev)}
+        tok, out_pn, hidden, logp_sum = state["tok"], state["out_pn"], state["hidden"], state["logp_sum"]
+        preds = torch.full((B, T), -1, dtype=torch.long, device=dev)
+        for t in range(T):
+            live = t < nv
+            j = self.tjoint(enc_chunk[:, t, :].unsqueeze(1).unsqueeze(1), out_pn.unsqueeze(1))
+            for layer in self.classifier_network:
+                j = layer(j)
+            logp, pos = torch.max(F.log_softmax(j.float(), dim=-1).squeeze(1).squeeze(1), dim=1)
+            upd = (pos != self.blank_id) & live
+            preds[:, t] = torch.where(upd, pos, preds[:, t])
+            logp_sum = logp_sum + torch.where(upd, logp, torch.zeros_like(logp))
+            new_tok = torch.where(upd, pos, tok[:, 0]).unsqueeze(1)
+            new_out, new_hidden = self._pn(new_tok, hidden)
+            out_pn = torch.where(upd.view(B, 1, 1), new_out, out_pn)
+            hidden = tuple(torch.where(upd.view(1, B, 1), nh, h) for nh, h in zip(new_hidden, hidden))
+            tok = new_tok
+        state = {"tok": tok, "out_pn": out_pn, "hidden": hidden, "logp_sum": logp_sum}
+        rows = preds.cpu()
+        return [[int(v) for v in row[row >= 0]] for row in rows], state
 
     @torch.no_grad()
     def transducer_greedy_decode(self, tn_output):

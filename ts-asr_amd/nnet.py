@@ -385,6 +385,29 @@ class ConvolutionFrontEnd(nn.Module):
             x = getattr(self, f"convblock_{i}")(x, self.dropout, self.training)
         return x
 
+    def forward_chunk(self, x, state=None):
+        """Streaming forward of a causally padded front-end (eval only): x [B,F,80] the next F feature frames, ``state`` the list of
+        the last 2 input frames of each block (None = start of the stream: zeros, the offline causal pad). Each block runs the offline
+        kernels on [carry | chunk] and drops its first output row, whose window reaches into the zero pad in front of the carry; row
+        r + 1 of that output is row (t0 + r) of the offline output (3x3 stride-2 window on input rows 2t-2 .. 2t). Returns
+        (y [B, ceil(ceil(F/2)/2), F', C], new state)."""
+        C.require_gpu(x)
+        if torch.is_grad_enabled() or self.training:
+            raise RuntimeError("ConvolutionFrontEnd.forward_chunk is inference only (eval mode, under torch.no_grad())")
+        x = _cd(x)
+        if x.ndim == 3:
+            x = x.unsqueeze(-1)
+        new_state = []
+        for i in range(self.num_blocks):
+            blk = getattr(self, f"convblock_{i}")
+            if blk.padding != "causal":
+                raise ValueError("forward_chunk needs a front-end with padding='causal'")
+            carry = state[i] if state is not None else torch.zeros(x.shape[0], 2, x.shape[2], x.shape[3], dtype=x.dtype, device=x.device)
+            xe = torch.cat([carry, x], dim=1)
+            new_state.append(xe[:, -2:].contiguous())
+            x = blk(xe, 0.0, False)[:, 1:]
+        return x, new_state
+
 
 # ------------------------------------------------------------------------------------------------------
 # A6-A9 Conformer block
@@ -595,3 +618,44 @@ class ConformerEncoderLayer(nn.Module):
             return x, attn, z
         _, x = ops.add_layer_norm(h, pff2[3].bias, x, self.norm2.norm, 0.5, p, tr)                  # norm2(x + .5*drop(ffn2))
         return (x, attn) if next_ln is None else (x, attn, None)
+
+    def init_stream(self, B, max_frames, dtype, device):
+        """Per-layer streaming state: K/V cache [B,H,max_frames,Dh] each, two fp32 conv histories [B,K-1,D] (swapped per chunk)."""
+        mha, conv = self.mha_layer, self.convolution_module
+        H, Dh, D, K = mha.num_heads, mha.head_dim, mha.embed_dim, conv.kernel_size
+        kv = torch.zeros(2, B, H, max_frames, Dh, dtype=dtype, device=device)
+        hist = torch.zeros(2, B, K - 1, D, dtype=torch.float32, device=device)
+        return {"k": kv[0], "v": kv[1], "hist": [hist[0], hist[1]], "pk": None, "ws": {}}
+
+    def forward_chunk(self, x, layer_state, t0, key_lens):
+        """One chunk [B,C,D] of this (causal) layer at absolute frame offset ``t0``; ``key_lens`` int32 [B] = valid frames of each
+        stream so far (None: all). The FFNs, norms and projections are the offline ops; the attention reads and extends the layer's
+        K/V cache (ops.relpos_attention_stream), the convolution core carries its K-1 GLU rows (ops.convmod_stream). Eval only."""
+        if not self.causal:
+            raise ValueError("forward_chunk needs a causal layer")
+        if torch.is_grad_enabled() or self.training:
+            raise RuntimeError("ConformerEncoderLayer.forward_chunk is inference only (eval mode, under torch.no_grad())")
+        conv, mha = self.convolution_module, self.mha_layer
+        ln1, pff1 = self.ffn_module1[0], self.ffn_module1[1].ffn
+        ln2, pff2 = self.ffn_module2[0], self.ffn_module2[1].ffn
+        x = _cd(x)
+        y = ops.layer_norm(x, ln1.weight, ln1.bias, 1e-5)
+        h = ops.ffn_core(y, pff1[0].weight, pff1[0].bias, pff1[3].weight, self.slope, 0.0, False)
+        x, y = ops.add_layer_norm(h, pff1[3].bias, x, self.norm1.norm, 0.5)                          # x + .5*ffn1 ; norm1
+        qkv = ops.matmul_nt(y, mha.in_proj_weight)
+        B, Cn = qkv.shape[0], qkv.shape[1]
+        ws = layer_state["ws"]
+        if Cn not in ws:
+            ws[Cn] = ops.relpos_attn_stream_workspace(B, Cn, mha.num_heads, mha.head_dim, layer_state["k"].shape[2], qkv.device)
+        o = ops.relpos_attention_stream(qkv, layer_state["k"], layer_state["v"], layer_state["pk"], mha.pos_bias_u, mha.pos_bias_v, key_lens,
+                                        mha.num_heads, mha.scale, max(self.chunk_size, 1), t0, ws[Cn])
+        x, y = ops.linear_add_layer_norm(o, mha.out_proj.weight, mha.out_proj.bias, x, conv.layer_norm)               # + attention ; conv LN
+        y2 = ops.matmul_nt(y, conv.bottleneck[0].weight)
+        hin, hout = layer_state["hist"]
+        c = ops.convmod_stream(y2, conv.bottleneck[0].bias, conv.conv.weight, conv.conv.bias, conv.after_conv[0].weight, conv.after_conv[0].bias,
+                               hin, hout, 1e-5, conv.slope)
+        layer_state["hist"] = [hout, hin]
+        x, y = ops.linear_add_layer_norm(c, conv.after_conv[2].weight, conv.after_conv[2].bias, x, ln2)              # + conv ; ffn2 LN
+        h = ops.ffn_core(y, pff2[0].weight, pff2[0].bias, pff2[3].weight, self.slope, 0.0, False)
+        _, x = ops.add_layer_norm(h, pff2[3].bias, x, self.norm2.norm, 0.5)                          # norm2(x + .5*ffn2)
+        return x

@@ -32,6 +32,8 @@ STATUS = {
     "lstm(num_layers > 1, bidirectional, H not a multiple of 16 / > 1024)": "LIB (nn.LSTM -> MIOpen), logged",
     "cross_attention injection with head dim > 64": "LIB (ATen matmul / softmax), logged",
     "relpos_attention(need_weights=True: attention maps for plots)": "LIB (ATen matmul / softmax), logged",
+    "streaming (causal encoder, chunk by chunk)": "HIP (stream.hip: relpos_attention_stream on a K/V cache, convmod_stream with carried history; "
+                                                  "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
 }
 
 STRICT_HIP = os.environ.get("TSASR_STRICT_HIP", "0") == "1"
@@ -2190,3 +2192,90 @@ def convmod_core(y2, b2, conv_w, conv_b, ln_w, ln_b, causal, eps, slope):
 
 def glu_dwconv_ln_act(y2, conv_w, conv_b, ln_w, ln_b, causal, eps, slope):
     return convmod_core(y2, None, conv_w, conv_b, ln_w, ln_b, causal, eps, slope)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Streaming inference of the causal encoder (csrc/stream.hip, csrc/search.hip). Forward only: there is no backward to these kernels.
+def _no_grad_only(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what} is inference only: run it under torch.no_grad() / torch.inference_mode()")
+
+
+def relpos_attn_stream_workspace(B, Cn, H, Dh, Tmax, device):
+    """Workspace of the key split of relpos_attention_stream for chunks of Cn frames (None when the shape is not split)."""
+    n = C.lib().tsasr_relpos_attn_stream_workspace_bytes(int(B), int(Cn), int(H), int(Dh), int(Tmax))
+    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+
+
+def relpos_attention_stream(qkv, k_cache, v_cache, pk_half, pos_bias_u, pos_bias_v, key_lens, H, scale, causal, t0, workspace=None):
+    """Context [B,C,D] of a chunk of C query frames at absolute offset ``t0`` (RelPosMHAXL's core): qkv [B,C,H*3*Dh] per-head Q|K|V,
+    k_cache / v_cache [B,H,Tmax,Dh] (the chunk's K, V are appended at t0 by the same launch), pk_half [Tmax,D] = linear_pos(PE(|i-j|)),
+    key_lens int32 [B] absolute valid frames or None, causal 1 (look-ahead) or c > 1 (block-causal chunks of c frames)."""
+    _no_grad_only("relpos_attention_stream")
+    C.require_gpu(qkv, k_cache, v_cache, pk_half)
+    qkvc = qkv.contiguous()
+    B, Cn, D3 = qkvc.shape
+    D = D3 // 3
+    Dh = D // H
+    Tmax = k_cache.shape[2]
+    if k_cache.dtype != qkvc.dtype or v_cache.dtype != qkvc.dtype or pk_half.dtype != qkvc.dtype:
+        raise ValueError("qkv, the K/V cache and pk_half must share one dtype")
+    if tuple(k_cache.shape) != (B, H, Tmax, Dh) or tuple(v_cache.shape) != (B, H, Tmax, Dh) or pk_half.shape[0] < Tmax or pk_half.shape[1] != D:
+        raise ValueError(f"cache / table shapes {tuple(k_cache.shape)} {tuple(pk_half.shape)} do not fit qkv {tuple(qkvc.shape)}")
+    if t0 + Cn > Tmax:
+        raise ValueError(f"stream longer than its cache: t0 {t0} + chunk {Cn} > {Tmax} frames")
+    u = _f32(pos_bias_u).reshape(-1).contiguous()      # (Dh,H) storage read as [H,Dh]
+    v = _f32(pos_bias_v).reshape(-1).contiguous()
+    kl = None if key_lens is None else key_lens.to(torch.int32).contiguous()
+    out = torch.empty(B, Cn, D, dtype=qkvc.dtype, device=qkvc.device)
+    with prof.region("relpos_attn_stream_fwd"):
+        C.check(C.lib().tsasr_relpos_attn_stream_fwd(C.ptr(qkvc), C.ptr(k_cache), C.ptr(v_cache), C.ptr(pk_half.contiguous()), C.ptr(u), C.ptr(v),
+                                                     C.ptr(kl), C.ptr(out), B, Cn, H, Dh, Tmax, int(t0), int(causal), float(scale),
+                                                     C.io_dtype(qkvc), C.ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                                     C.stream_ptr()), "tsasr_relpos_attn_stream_fwd")
+    return out
+
+
+def convmod_stream(y2, b2, conv_w, conv_b, ln_w, ln_b, hist_in, hist_out, eps, slope):
+    """convmod_core(causal=True) on a chunk y2 [B,C,2D] whose K-1 preceding GLU rows are hist_in fp32 [B,K-1,D]; writes the next
+    chunk's history to hist_out (another buffer). Returns z [B,C,D]."""
+    _no_grad_only("convmod_stream")
+    C.require_gpu(y2, hist_in, hist_out)
+    y2c = y2.contiguous()
+    B, Cn, D2 = y2c.shape
+    D, K = D2 // 2, conv_w.shape[-1]
+    if tuple(hist_in.shape) != (B, K - 1, D) or tuple(hist_out.shape) != (B, K - 1, D) or hist_in.dtype != torch.float32 \
+            or hist_out.dtype != torch.float32 or hist_in.data_ptr() == hist_out.data_ptr():
+        raise ValueError("convmod_stream: histories must be two distinct fp32 [B, K-1, D] buffers")
+    f = lambda t: None if t is None else _f32(t).contiguous()  # noqa: E731
+    b2f, cw, cb, g, be = f(b2), f(conv_w).reshape(D, K), f(conv_b), f(ln_w), f(ln_b)
+    z = torch.empty(B, Cn, D, dtype=y2c.dtype, device=y2c.device)
+    with prof.region("convmod_stream_fwd"):
+        C.check(C.lib().tsasr_convmod_stream_fwd(C.ptr(y2c), C.ptr(b2f), C.ptr(cw), C.ptr(cb), C.ptr(g), C.ptr(be), C.ptr(hist_in),
+                                                 C.ptr(hist_out), C.ptr(z), B, Cn, D, K, float(eps), float(slope), C.io_dtype(y2c),
+                                                 C.stream_ptr()), "tsasr_convmod_stream_fwd")
+    return z
+
+
+def greedy_stream_state_size(H, J):
+    """fp32 words of one utterance's tsasr_greedy_decode_stream state: h | c | projected output | symbol | log-prob sum | flag | pad."""
+    return 2 * H + J + 4
+
+
+def greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_valid, blank, slope, wdtype):
+    """One chunk of greedy transducer search on the device: enc [B,T,J], state fp32 [B, greedy_stream_state_size] (updated in place),
+    n_valid int32 [B]. Returns (preds int32 [B,T] with -1 for no symbol, running logp_sum fp32 [B])."""
+    _no_grad_only("greedy_decode_stream")
+    C.require_gpu(enc, state, n_valid)
+    B, T, J = enc.shape
+    H = mats[1].shape[1]
+    if tuple(state.shape) != (B, greedy_stream_state_size(H, J)) or state.dtype != torch.float32 or not state.is_contiguous():
+        raise ValueError("greedy_decode_stream: state must be a contiguous fp32 [B, 2H + J + 4] tensor")
+    preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
+    logp = torch.empty(B, dtype=torch.float32, device=enc.device)
+    nv = n_valid.to(torch.int32).contiguous()
+    C.check(C.lib().tsasr_greedy_decode_stream(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                               C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(state), C.ptr(nv), C.ptr(preds), C.ptr(logp),
+                                               B, T, J, H, table.shape[1], mats[3].shape[0], int(blank), float(slope), C.io_dtype(enc), wdtype,
+                                               C.stream_ptr()), "tsasr_greedy_decode_stream")
+    return preds, logp

@@ -1,0 +1,174 @@
+"""Chunk-by-chunk transcription with a causal TS-ASR model (``causal_encoder: True``, ``frontend_padding: causal``).
+
+    st = StreamingTranscriber(brain)
+    st.start(batch_size=B, max_frames=4000, enroll=(enroll_sig, enroll_lens))     # or speaker_embs=..., or nothing (variant none)
+    with torch.no_grad():
+        for feats in chunks:                        # [B, F, 80] normalised fbank frames, F a multiple of 4
+            new_tokens = st.push(feats)             # list (per stream) of the symbols emitted for these frames
+        hyps = st.finish()
+
+Every block of such a model is causal: the front-end pads time on the left only, the depthwise convolution is left-padded, the
+attention mask (look-ahead or block-causal on absolute frame indices) never looks past the current chunk, and RelPosEncXL's table is
+symmetric, so one half table serves every offset. A push therefore costs the new frames only: the front-end carries the last 2 input
+frames of each block, every encoder layer a K/V cache and the K-1 GLU rows of its convolution, the greedy search its predictor state
+(ConvolutionFrontEnd.forward_chunk, ConformerEncoder.forward_chunk, TransducerBeamSearcher.greedy_stream). The valid encoder rows
+equal those of the offline causal encoder over the whole utterance.
+
+Features are an INPUT of the stream, not part of it. The recipe's Fbank clamps each utterance at ``top_db`` below its own maximum and
+InputNormalization (``norm_type: sentence``) subtracts the utterance's mean and divides by its deviation: both use statistics of the
+whole utterance, so a waveform-in stream would change what the model sees. The caller provides normalised feature frames (for example
+the offline front-end's output for an utterance, or features normalised with statistics it chooses); this class does not approximate
+the sentence-level steps.
+
+With block-causal attention (``attention_chunk_size`` c > 1) a push holds a multiple of 4c feature frames (a frame attends its
+whole block, so a push cannot end inside one).
+
+Streams of different lengths share a batch: each one stops at its own valid count, ``ceil(ceil(L/2)/2)`` encoder frames for L valid
+mel frames pushed so far (``mel_lens`` per push, default the whole push); ``enc_lens`` overrides that count (absolute encoder frames).
+Inference only: eval mode, under torch.no_grad().
+"""
+import types
+
+import torch
+
+from . import _capi as C
+
+__all__ = ["StreamingTranscriber"]
+
+
+def _enc_frames(mel):
+    return (mel + 3) // 4 if isinstance(mel, int) else torch.div(torch.div(mel + 1, 2, rounding_mode="floor") + 1, 2, rounding_mode="floor")
+
+
+class StreamingTranscriber:
+    """Streams of one causal model; see the module docstring. Side effect while a stream is open (bf16 compute): from start() to
+    finish() every fp32 weight matrix of the front-end, the encoder and encoder_proj that has no bf16 copy carries one (``p._bf16``,
+    valid while ``p._version`` is unchanged; the copy the training step's gradient arena keeps, so that a push does not cast its
+    weights again). That is one bf16 copy of those matrices in memory; do not change the weights in place (``p.data``) while a stream
+    is open. finish() removes the copies."""
+
+    def __init__(self, brain):
+        m = brain.modules
+        enc, fe = m["encoder"] if isinstance(m, dict) else m.encoder, m["frontend"] if isinstance(m, dict) else m.frontend
+        if not getattr(enc, "causal", False):
+            raise ValueError("StreamingTranscriber needs a causal encoder (causal_encoder: True); this model looks at future frames")
+        pads = {getattr(fe, f"convblock_{i}").padding for i in range(fe.num_blocks)}
+        if pads != {"causal"}:
+            raise ValueError(f"StreamingTranscriber needs frontend_padding: causal (the front-end pads with {sorted(pads)})")
+        self.brain, self.encoder, self.frontend = brain, enc, fe
+        self.encoder_proj = m["encoder_proj"] if isinstance(m, dict) else m.encoder_proj
+        hp = brain.hparams
+        self.searcher = hp["greedy_searcher"] if isinstance(hp, dict) else hp.greedy_searcher
+        self._started = False
+        self._copies = []
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False):
+        """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
+        ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
+        ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
+        every chunk's encoder output (before encoder_proj) for encoder_out()."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        if hasattr(self.brain, "_setup_dtype"):      # the brain's compute dtype (as fit / evaluate set it)
+            self.brain._setup_dtype()
+        for mod in (self.frontend, self.encoder, self.encoder_proj, self.searcher):
+            mod.eval()
+        from .nnet import compute_dtype
+        if compute_dtype() == torch.bfloat16:
+            # bf16 copies of the matrices, kept beside the weights as the training step's gradient arena keeps them (ops._bf16_weight
+            # takes them while the weight's version is unchanged): without them every GEMM of every push casts its weight again.
+            # A weight that already has a copy (the arena's view into its flat shadow) is left alone; finish() removes the copies.
+            self._drop_copies()
+            for mod in (self.frontend, self.encoder, self.encoder_proj):
+                for p in mod.parameters():
+                    if p.dim() >= 2 and p.is_cuda and p.dtype == torch.float32 and getattr(p, "_bf16", None) is None:
+                        p._bf16 = p.detach().to(torch.bfloat16).contiguous()
+                        p._bf16_ver = p._version
+                        self._copies.append((p, p._bf16))
+        if enroll is not None:
+            sig, lens = enroll
+            batch = types.SimpleNamespace(enroll_sig=(sig, lens))
+            for name in ("speaker_frontend", "speaker_encoder", "speaker_proj"):
+                mods = self.brain.modules
+                if (name in mods) if isinstance(mods, dict) else hasattr(mods, name):
+                    (mods[name] if isinstance(mods, dict) else getattr(mods, name)).eval()
+            speaker_embs, speaker_embs_length = self.brain._speaker_embedding(batch, 0)
+        self.B, self.max_frames = int(batch_size), int(max_frames)
+        self.spk, self.spk_len = speaker_embs, speaker_embs_length
+        self.enc_state = None                    # allocated by the first push (after its arguments are checked)
+        self.fe_state, self.search_state = None, None
+        self.mel = None
+        self.hyps = [[] for _ in range(self.B)]
+        self.closed = False
+        self.keep = bool(keep_encoder_out)
+        self.enc_chunks = []
+        self._started = True
+        return self
+
+    def push(self, feats, mel_lens=None, enc_lens=None, last=False):
+        """Feed the next F feature frames of every stream, feats [B, F, 80]; F must be a multiple of 4 unless ``last`` (no push may
+        follow a last one). mel_lens [B]: valid frames of this push per stream (default F); enc_lens [B]: absolute valid encoder frames
+        after this push (default ceil(ceil(L/2)/2) of the mel frames pushed so far). Returns the new symbols of each stream."""
+        if not self._started:
+            raise RuntimeError("push() before start()")
+        if self.closed:
+            raise RuntimeError("push() after the last push of the stream")
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        if feats.ndim != 3 or feats.shape[0] != self.B:
+            raise ValueError(f"feats must be [B={self.B}, F, n_mels], got {tuple(feats.shape)}")
+        F = feats.shape[1]
+        if F % 4 and not last:
+            raise ValueError(f"a push carries a multiple of 4 feature frames (one encoder frame per 4) except the last one: got {F}")
+        blk = max(int(getattr(self.encoder.layers[0], "chunk_size", 0) or 0), 1)
+        if (F // 4) % blk and not last:
+            raise ValueError(f"with block-causal attention over {blk} frames a push carries a multiple of {4 * blk} feature frames "
+                             f"except the last one: got {F}")
+        if F == 0:
+            return [[] for _ in range(self.B)]
+        t_done = 0 if self.enc_state is None else self.enc_state["t0"]
+        if t_done + _enc_frames(F) > self.max_frames:      # checked before any state of the stream moves
+            raise ValueError(f"the push would take the stream past start()'s max_frames: {t_done} + {_enc_frames(F)} > {self.max_frames} encoder frames")
+        C.require_gpu(feats)
+        dev = feats.device
+        if self.enc_state is None:
+            self.enc_state = self.encoder.init_stream(self.B, self.max_frames, device=dev)
+            self.mel = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        ml = torch.full((self.B,), F, dtype=torch.int64, device=dev) if mel_lens is None else torch.as_tensor(mel_lens, device=dev).long()
+        self.mel = self.mel + ml.clamp(0, F)
+        valid = _enc_frames(self.mel) if enc_lens is None else torch.as_tensor(enc_lens, device=dev).long()
+        t0 = self.enc_state["t0"]
+        x, self.fe_state = self.frontend.forward_chunk(feats, self.fe_state)
+        e = self.encoder.forward_chunk(x, self.enc_state, self.spk, self.spk_len, enc_lens=valid.to(torch.int32))
+        if self.keep:
+            self.enc_chunks.append(e)
+        e = self.encoder_proj(e)
+        n_valid = (valid - t0).clamp(0, e.shape[1]).to(torch.int32)
+        new, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid)
+        for b, toks in enumerate(new):
+            self.hyps[b].extend(toks)
+        self.closed = bool(last)
+        return new
+
+    def finish(self):
+        """The hypotheses (symbol lists) of every stream; the stream is closed and the weights' bf16 copies made by start() are dropped."""
+        self.closed = True
+        self._drop_copies()
+        return [list(h) for h in self.hyps]
+
+    def _drop_copies(self):
+        for p, copy in self._copies:
+            if getattr(p, "_bf16", None) is copy:          # (not replaced since: e.g. by a gradient arena)
+                del p._bf16
+                if hasattr(p, "_bf16_ver"):
+                    del p._bf16_ver
+        self._copies = []
+
+    def encoder_out(self):
+        """[B, frames so far, d_model]: the encoder output of every push (start(keep_encoder_out=True))."""
+        return torch.cat(self.enc_chunks, dim=1)
+
+    @property
+    def encoder_frames(self):
+        return 0 if self.enc_state is None else self.enc_state["t0"]
