@@ -471,6 +471,32 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
                                float slope, int io_dtype, int wdtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beam transducer search on the device (SB/decoders/transducer.py:220-373, transducer_beam_search_decode, no LM fusion) for the networks
+ * tsasr_greedy_decode takes: one persistent workgroup per utterance, one launch decodes the batch. Scores in fp64 as the host loop;
+ * list order as the reference (first maximum of logp / len, appends in top-k order, stable n-best sort, top-k ties: lower index). Each
+ * node of the hypothesis tree runs its predictor step once. 2 <= beam <= V, 1 <= nbest <= 64, cap >= beam = hypotheses a frame may
+ * hold (its A list). workspace >= tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap) = B * (align16(64 + 24 beam) +
+ * align16(8 (1 + (max_frames + 1) beam + cap)) + 4 (cap + beam)(J + 2H)). hyps int32 [B,nbest,Lmax] (first min(len, Lmax) tokens),
+ * lens int32 [B,nbest] (-1: the beam holds fewer), scores fp64 [B,nbest] = logp / len(prediction incl. the blank prefix), status int32
+ * [B]: 0 ok, 1 a frame needed more than cap hypotheses, 2 token tree full, 3 no hypothesis left to expand; such an utterance stops
+ * there, the others are unaffected. The offline call starts the workspace afresh and leaves the final beam in it.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, int cap);
+int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                      const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
+                      int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
+                      int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
+
+/* The same search over one chunk of a stream: resumes the beam, token tree and predictor slots from the workspace (laid out for
+ * max_frames; zeroed = start of the stream); n_valid int32 [B] = frames of this chunk to decode per utterance (0: the state is left as
+ * it is, the outputs describe it). A nonzero status is sticky. A tensor decoded in pieces gives the bits of one call over it. */
+int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                             size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                             int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                             double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chunk-by-chunk inference of the causal encoder (csrc/stream.hip); eval only, no backward.
  * Relative-position attention of a chunk of C query frames at absolute offset t0: qkv [B,C,H,3*Dh] (RelPosMHAXL's per-head Q|K|V);
  * k_cache / v_cache [B,H,Tmax,Dh] (io_dtype) hold frames 0 .. t0-1 and receive the chunk's K, V at rows t0 .. t0+C-1 (t0 + C <= Tmax);

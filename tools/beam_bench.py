@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Device beam search (csrc/search.hip, tsasr_beam_search) against the host loop on a configs[1]-shaped TEST batch.
+
+enc_proj [32, 250, 640] (seeded, the golden encoder output's scale), predictor 512 / joint 640 / 29 symbols with the deterministic golden
+weights and the golden fixture's blank-bias shift (+3.0, so that the reference's loop ends); fp32 and bf16, beam 4 and 15. The device
+search is timed over the whole batch (HIP events, median of --reps); the host loop (TSASR_BEAM_KERNEL=0) over --host-utts utterances and
+reported per utterance. Expansions per frame and predictor steps computed come from a host restatement of the kernel's bookkeeping over
+the device's own inputs (count only; the counts do not depend on which route ran).
+
+    python tools/beam_bench.py [--reps 5] [--host-utts 2] [--frames 250]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry  # noqa: E402
+from oracle.golden_recipe import det_tensor  # noqa: E402
+
+
+def counts(s, enc):
+    """(expansions, predictor steps with memoisation, frames) of the host loop's bookkeeping on enc [1,T,J], counted as the kernel
+    computes: one predictor step per hypothesis node (a blank copy keeps its node, an extension is a new node)."""
+    import torch.nn.functional as F
+    key = lambda h: h[1] / h[0]  # noqa: E731
+    nodes = [(-1, s.blank_id)]                      # node -> (parent, token)
+    beam, exp, memo = [(1, 0.0, 0)], 0, {}          # (len, logp, node)
+    for t in range(enc.shape[1]):
+        A, beam = beam, []
+        while len(beam) < s.beam_size:
+            a = max(A, key=key)
+            if beam and max(beam, key=key)[1] >= s.state_beam + a[1]:
+                break
+            A.remove(a)
+            exp += 1
+            n = a[2]
+            if n not in memo:
+                par, tok = nodes[n]
+                memo[n] = s._pn(torch.full((1, 1), tok, dtype=torch.long, device=enc.device), memo[par][1] if par >= 0 else None)
+            j = s.tjoint(enc[0, t].view(1, 1, 1, -1), memo[n][0].unsqueeze(0))
+            for layer in s.classifier_network:
+                j = layer(j)
+            logp, pos = torch.topk(F.log_softmax(j.float(), dim=-1).view(-1), k=s.beam_size)
+            logp, pos = logp.tolist(), pos.tolist()
+            bnb = logp[0] if pos[0] != s.blank_id else logp[1]
+            for lp, sym in zip(logp, pos):
+                if sym == s.blank_id:
+                    beam.append((a[0], a[1] + lp, n))
+                elif lp >= bnb - s.expand_beam:
+                    nodes.append((n, sym))
+                    A.append((a[0] + 1, a[1] + lp, len(nodes) - 1))
+    return exp, len(memo), enc.shape[1]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host-utts", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=250)
+    ap.add_argument("--beams", default="4,15")
+    ap.add_argument("--dtypes", default="fp32,bf16")
+    args = ap.parse_args()
+    dec = importlib.import_module("ts-asr_amd.decoders")
+    ops = importlib.import_module("ts-asr_amd.ops")
+    results = []
+    for dtype in args.dtypes.split(","):
+        brain, h = entry._config1_brain("cuda:0", dtype, joint_dim=640, decoder_neurons=512)
+        brain._setup_dtype()
+        m = brain.modules
+        dt = torch.float32 if dtype == "fp32" else torch.bfloat16
+        g = np.load(os.path.join(ROOT, "tests", "golden", "c1_chain_cat.npz"))["enc_proj"]
+        enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (32, args.frames, 640), float(np.std(g)))).to("cuda:0", dt)
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] += 3.0
+        for beam in (int(b) for b in args.beams.split(",")):
+            s = dec.TransducerBeamSearcher([m.embedding, m.decoder, m.decoder_proj], m.joiner, [m.transducer_head], blank_id=0,
+                                           beam_size=beam, nbest=5, state_beam=2.3, expand_beam=2.3)
+            with torch.no_grad():
+                assert s._device_beam_ok(enc)
+                _, _, status = s._device_beam_call(enc, ops.beam_search)          # warm-up (no host re-decode: timed alone)
+                ms = []
+                for _ in range(args.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    s._device_beam_call(enc, ops.beam_search)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms.append(e0.elapsed_time(e1))
+                stopped = int((status != 0).sum())
+                host_ms, exp, steps, frames = float("nan"), 0, 0, 1
+                ok = [b for b in range(32) if int(status[b]) == 0][: args.host_utts]
+                if ok:                                               # (an utterance past cap would keep the host loop busy for long)
+                    os.environ["TSASR_BEAM_KERNEL"] = "0"
+                    try:
+                        t0 = time.perf_counter()
+                        s(enc[ok])
+                        torch.cuda.synchronize()
+                        host_ms = (time.perf_counter() - t0) * 1e3 / len(ok)
+                        exp, steps, frames = counts(s, enc[ok[:1]])
+                    finally:
+                        del os.environ["TSASR_BEAM_KERNEL"]
+            dev_ms = float(np.median(ms))
+            r = dict(dtype=dtype, beam=beam, B=32, T=args.frames, device_ms_per_batch=round(dev_ms, 2), host_ms_per_utt=round(host_ms, 1),
+                     speedup_batch=round(host_ms * 32 / dev_ms, 1), expansions_per_frame=round(exp / frames, 2),
+                     predictor_steps_per_frame=round(steps / frames, 2), device_stopped_utts=stopped)
+            print(json.dumps(r), flush=True)
+            results.append(r)
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] -= 3.0
+    return results
+
+
+if __name__ == "__main__":
+    main()

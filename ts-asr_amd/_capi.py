@@ -24,6 +24,7 @@ class TsasrHipError(RuntimeError):
 _lib = None
 
 c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+c_double = ctypes.c_double
 c_ll, c_ull = ctypes.c_longlong, ctypes.c_ulonglong
 
 # name -> (restype, argtypes); mirrors include/tsasr_hip.h one to one
@@ -138,6 +139,9 @@ _PROTOS = {
     "tsasr_inject_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "tsasr_greedy_decode": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
     "tsasr_greedy_decode_stream": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
+    "tsasr_beam_search_workspace_bytes": (c_size_t, [c_int] * 6),
+    "tsasr_beam_search": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
+    "tsasr_beam_search_stream": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),
     "tsasr_relpos_attn_stream_fwd": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_float, c_int, c_void_p, c_size_t, c_void_p]),
     "tsasr_convmod_stream_fwd": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_float, c_float, c_int, c_void_p]),

@@ -191,6 +191,351 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Beam transducer search (speechbrain/decoders/transducer.py:220-373, restated in decoders.py's host loop and oracle beam_decode): one
+// persistent workgroup per utterance. Per frame, A = hypotheses to extend (the last frame's beam), beam = those that emitted blank here.
+// Until |beam| >= beam_size: a = first entry of A with the largest logp / len (len counts the blank prefix); stop once the first best
+// beam entry has logp >= state_beam + logp(a); remove a; run the predictor on a's last token from a's state; top-k (k = beam_size) of
+// log_softmax(head(LeakyReLU(enc[t] + pn))); blank appends a copy of a (same node, same state) to the beam, a non-blank within
+// expand_beam of the best non-blank appends a's extension (new state) to A. Scores are fp64 (the host loop adds Python floats).
+//
+// Bookkeeping: A lives in LDS as an append-only array (removal = a flag, so "first in insertion order" is "lowest index"); a hypothesis
+// is a node of a token tree ((token, parent) int pairs in the workspace) and the predictor step of a node (pn | h | c) is computed once,
+// on its first expansion, into a slot of the workspace: a hypothesis that survives a frame is re-expanded with the joint alone. At the
+// end of a frame the new nodes on the beam's paths are promoted into the tree (in creation order), all other new nodes and every slot
+// not held by the beam are recycled. Workspace of one utterance: header (16 ints: primed, status, nbeam, tree size, frames) + beam
+// entries | tree | slots; a zeroed header is the start of a stream.
+constexpr int BEAM_THREADS = 1024;
+constexpr int BEAM_MAXK = 64;            // beam_size <= V <= 63
+
+struct BeamEnt {
+    double logp;
+    int node, len, slot, tok;
+};
+
+struct BeamLayout {
+    size_t hdr, tree, per_utt;
+    int nn, ns;
+};
+
+__host__ __device__ inline size_t beam_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+__host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam, int cap) {
+    BeamLayout L;
+    L.nn = 1 + (T + 1) * beam + cap;                          // tree nodes: root + (typically <= beam promoted per frame) + slack
+    L.ns = cap + beam;                                         // slots: the beam's + one per node expanded in a frame (<= cap)
+    L.hdr = beam_align16(64 + sizeof(BeamEnt) * (size_t)beam);
+    L.tree = beam_align16(8 * (size_t)L.nn);
+    L.per_utt = L.hdr + L.tree + (size_t)L.ns * (size_t)(J + 2 * H) * sizeof(float);
+    return L;
+}
+
+struct BeamArgs {
+    const void *enc;            // [B, T, J] io dtype (T = frames of this call)
+    const float *emb;
+    const void *w_ih, *w_hh;
+    const float *b_ih, *b_hh;
+    const void *w_proj;
+    const float *b_proj;
+    const void *w_head;
+    const float *b_head;
+    unsigned char *ws;          // [B, layout.per_utt]
+    const int *n_valid;         // [B] or NULL (= T, and the workspace is started afresh)
+    int *hyps;                  // [B, nbest, Lmax]
+    int *lens;                  // [B, nbest]: tokens of the hypothesis (-1: no such entry)
+    double *scores;             // [B, nbest]: logp / len
+    int *status;                // [B]
+    int B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames;
+    double state_beam, expand_beam;
+    float slope;
+};
+
+// (key, index) of the larger key; equal keys: the lower index (Python max: the first maximal entry)
+__device__ __forceinline__ void beam_argmax_step(double &k, int &i, int mask) {
+    const double k2 = __shfl_xor(k, mask);
+    const int i2 = __shfl_xor(i, mask);
+    if (k2 > k || (k2 == k && i2 < i)) { k = k2; i = i2; }
+}
+
+template <typename T, typename WT>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float bsm[];
+    const int H = A.H, J = A.J, cap = A.cap;
+    float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + 64;
+    double *Alp = reinterpret_cast<double *>(lg + 64), *Akey = Alp + cap;
+    int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
+        *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
+    __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
+    __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
+    __shared__ float s_lp[64];
+    // s_ctl: 0 nA, 1 nbeam (this frame), 2 chosen a, 3 stop (1 frame done, 2 status set), 4 status, 5 n_init, 6 next slot, 7 tree size,
+    //        8 compute the predictor step, 9 parent slot, 10 token, 11 A full (appends), 12 tree full (promotion). Each flag is written in
+    //        one phase and read right after that phase's barrier, so that no wave reads a word another wave is writing.
+    __shared__ int s_ctl[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap);
+    unsigned char *wsu = A.ws + (size_t)b * L.per_utt;
+    int *hdr = reinterpret_cast<int *>(wsu);
+    BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
+    int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
+    float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
+    const int SW = J + 2 * H;                                // floats per slot: pn | h | c
+    const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
+    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
+    const bool fresh = A.n_valid == nullptr;
+    const int tend = fresh ? A.T : min(max(A.n_valid[b], 0), A.T);
+
+    if (tid == 0) {
+        const bool primed = !fresh && hdr[0] != 0;
+        s_ctl[4] = fresh ? 0 : hdr[1];
+        s_ctl[11] = s_ctl[12] = 0;
+        if (primed) {
+            const int nb = min(max(hdr[2], 1), A.beam);
+            s_ctl[5] = nb;
+            s_ctl[7] = hdr[3];
+        } else {
+            s_ctl[5] = 1;
+            s_ctl[7] = 1;
+        }
+    }
+    __syncthreads();
+    const bool primed = !fresh && hdr[0] != 0;
+    if (tid < s_ctl[5]) {                                    // the beam entering this call = the first frame's A
+        BeamEnt e = primed ? bent[tid] : BeamEnt{0.0, 0, 1, -1, A.blank};
+        Alp[tid] = e.logp;
+        Akey[tid] = e.logp / (double)e.len;
+        Apar[tid] = -1;
+        Atok[tid] = e.tok;
+        Alen[tid] = e.len;
+        Aslot[tid] = e.slot;
+        Anode[tid] = e.node;
+        Aflag[tid] = 1;
+    }
+    __syncthreads();
+    const bool run = s_ctl[4] == 0 && tend > 0;              // workgroup-uniform
+    if (run && !primed && tid == 0) tree[0] = make_int2(A.blank, -1);
+
+    for (int t = 0; run && t < tend; ++t) {
+        if (tid == 0) { s_ctl[0] = s_ctl[5]; s_ctl[1] = 0; s_ctl[6] = 0; s_ctl[3] = 0; }
+        __syncthreads();
+        while (true) {
+            if (wave == 0) {
+                const int nA = s_ctl[0], nb = s_ctl[1];
+                double bk = -INFINITY;
+                int bi = INT_MAX;
+                if (nb < A.beam) {
+                    for (int i = lane; i < nA; i += 64)
+                        if ((Aflag[i] & 1) && (Akey[i] > bk || bi == INT_MAX)) { bk = Akey[i]; bi = i; }
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) beam_argmax_step(bk, bi, m);
+                }
+                if (lane == 0) {
+                    int stop = 0;
+                    if (nb >= A.beam) stop = 1;
+                    else if (bi == INT_MAX) { s_ctl[4] = 3; stop = 2; }          // A ran empty (the reference's max() raises)
+                    else if (nb > 0) {
+                        int bm = 0;
+                        for (int j = 1; j < nb; ++j)
+                            if (s_bkey[j] > s_bkey[bm]) bm = j;
+                        if (s_blp[bm] >= A.state_beam + Alp[bi]) stop = 1;
+                    }
+                    if (!stop) {
+                        Aflag[bi] &= ~1;
+                        s_ctl[2] = bi;
+                        s_ctl[8] = Aslot[bi] < 0;
+                        if (Aslot[bi] < 0) {                         // first expansion of this node: a slot for its predictor step
+                            int p = s_ctl[6];
+                            const int ni = s_ctl[5];
+                            for (bool used = true; used && p < L.ns;) {
+                                used = false;
+                                for (int j = 0; j < ni; ++j) used |= Aslot[j] == p;
+                                if (used) ++p;
+                            }
+                            if (p >= L.ns) { s_ctl[4] = 1; stop = 2; }
+                            else {
+                                Aslot[bi] = p;
+                                s_ctl[6] = p + 1;
+                                s_ctl[9] = Apar[bi] >= 0 ? Aslot[Apar[bi]] : -1;
+                                s_ctl[10] = Atok[bi];
+                            }
+                        }
+                    }
+                    s_ctl[3] = stop;
+                }
+            }
+            __syncthreads();
+            if (s_ctl[3] != 0) break;
+            const int a = s_ctl[2];
+            float *sl = slots + (size_t)Aslot[a] * SW;
+            if (s_ctl[8]) {                                  // predictor step of node a: pn(token, parent's state), once per node
+                const int ps = s_ctl[9], tok = s_ctl[10];
+                const float *pst = ps >= 0 ? slots + (size_t)ps * SW : nullptr;
+                for (int i = tid; i < 2 * H; i += BEAM_THREADS) h[i] = pst ? pst[J + i] : 0.f;   // h | c contiguous in LDS and in a slot
+                for (int e = tid; e < A.E; e += BEAM_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
+                __syncthreads();
+                gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
+                __syncthreads();
+                for (int u = tid; u < H; u += BEAM_THREADS) {
+                    const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[H + u]), gg = tanhf(gates[2 * H + u]), og = sigmoid_f(gates[3 * H + u]);
+                    const float cn = fg * c[u] + ig * gg;
+                    c[u] = cn;
+                    h[u] = og * tanhf(cn);
+                }
+                __syncthreads();
+                gemv_rows<WT>(w_proj, J, H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
+                __syncthreads();
+                for (int i = tid; i < SW; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];     // slot = pn | h | c (h, c adjacent in LDS)
+            } else {
+                for (int k = tid; k < J; k += BEAM_THREADS) pn[k] = sl[k];
+                __syncthreads();
+            }
+            for (int k = tid; k < J; k += BEAM_THREADS) {
+                const float v = ld1(enc + (size_t)t * J + k) + pn[k];
+                z[k] = v > 0.f ? v : v * A.slope;
+            }
+            __syncthreads();
+            gemv_rows<WT>(w_head, A.V, J, z, A.b_head, nullptr, nullptr, 0, nullptr, lg);
+            __syncthreads();
+            if (wave == 0) {                                 // log_softmax, top-k (equal values: lower index first), the appends
+                const float v = lane < A.V ? lg[lane] : -INFINITY;
+                const float m = wave_max(v);
+                const float s = wave_sum(lane < A.V ? expf(v - m) : 0.f);
+                const float lp = (v - m) - logf(s);
+                s_lp[lane] = lp;
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (lane < A.V) {
+                    int rank = 0;
+                    for (int u = 0; u < A.V; ++u) {
+                        const float o = s_lp[u];
+                        rank += (o > lp) || (o == lp && u < lane);
+                    }
+                    if (rank < A.beam) { s_tlp[rank] = (double)lp; s_tpos[rank] = lane; }
+                }
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (lane == 0) {
+                    const double alp = Alp[a];
+                    const int alen = Alen[a];
+                    const double bnb = s_tpos[0] != A.blank ? s_tlp[0] : s_tlp[1];
+                    int nA = s_ctl[0], nb = s_ctl[1];
+                    for (int j = 0; j < A.beam; ++j) {
+                        const double sc = alp + s_tlp[j];
+                        const int sym = s_tpos[j];
+                        if (sym == A.blank) {
+                            s_blp[nb] = sc;
+                            s_bkey[nb] = sc / (double)alen;
+                            s_bidx[nb] = a;
+                            ++nb;
+                        } else if (s_tlp[j] >= bnb - A.expand_beam) {
+                            if (nA >= cap) { s_ctl[4] = 1; s_ctl[11] = 1; break; }
+                            Alp[nA] = sc;
+                            Akey[nA] = sc / (double)(alen + 1);
+                            Apar[nA] = a;
+                            Atok[nA] = sym;
+                            Alen[nA] = alen + 1;
+                            Aslot[nA] = -1;
+                            Anode[nA] = -1;
+                            Aflag[nA] = 1;
+                            ++nA;
+                        }
+                    }
+                    s_ctl[0] = nA;
+                    s_ctl[1] = nb;
+                }
+            }
+            __syncthreads();
+            if (s_ctl[11] != 0) break;
+        }
+        __syncthreads();
+        if (s_ctl[4] != 0) break;
+        // End of the frame: promote the new nodes on the beam's paths into the tree, in creation (index) order.
+        if (tid == 0) {
+            int cnt = 0;
+            for (int j = 0; j < s_ctl[1]; ++j)
+                for (int e = s_bidx[j]; e >= 0 && Anode[e] < 0 && !(Aflag[e] & 2); e = Apar[e]) { Aflag[e] |= 2; ++cnt; }
+            if (s_ctl[7] + cnt > L.nn) s_ctl[12] = 1;
+        }
+        __syncthreads();
+        if (s_ctl[12] != 0) break;
+        if (wave == 0) {
+            int base = s_ctl[7];
+            const int nA = s_ctl[0];
+            for (int i0 = 0; i0 < nA; i0 += 64) {
+                const int i = i0 + lane;
+                const bool mk = i < nA && (Aflag[i] & 2);
+                const unsigned long long bal = __ballot(mk);
+                if (mk) Anode[i] = base + __popcll(bal & ((1ull << lane) - 1));
+                base += __popcll(bal);
+            }
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            for (int i = lane; i < nA; i += 64)
+                if (Aflag[i] & 2) tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
+            if (lane == 0) s_ctl[7] = base;
+        }
+        __syncthreads();
+        BeamEnt ne{};
+        const int nb = s_ctl[1];
+        if (tid < nb) {
+            const int e = s_bidx[tid];
+            ne = BeamEnt{s_blp[tid], Anode[e], Alen[e], Aslot[e], Atok[e]};
+        }
+        __syncthreads();
+        if (tid < nb) {
+            Alp[tid] = ne.logp;
+            Akey[tid] = s_bkey[tid];
+            Apar[tid] = -1;
+            Atok[tid] = ne.tok;
+            Alen[tid] = ne.len;
+            Aslot[tid] = ne.slot;
+            Anode[tid] = ne.node;
+            Aflag[tid] = 1;
+        }
+        if (tid == 0) s_ctl[5] = nb;
+        __syncthreads();
+    }
+    __syncthreads();
+    const int st = s_ctl[4] != 0 ? s_ctl[4] : (s_ctl[12] != 0 ? 2 : 0), nbeam = s_ctl[5];
+    if (tid == 0) {
+        if (run) {                                           // the state this call leaves (a zero count leaves it untouched)
+            hdr[1] = st;
+            if (st == 0) {
+                hdr[0] = 1;
+                hdr[2] = nbeam;
+                hdr[3] = s_ctl[7];
+                hdr[4] = (fresh ? 0 : hdr[4]) + tend;
+            }
+        }
+        A.status[b] = st;
+        // n-best: sorted(beam, key=logp/len, reverse=True)[:nbest], stable -> repeated first-maximum selection
+        for (int r = 0; r < A.nbest; ++r) {
+            int best = -1;
+            if (st == 0)
+                for (int j = 0; j < nbeam; ++j)
+                    if (Aflag[j] & 1 && (best < 0 || Akey[j] > Akey[best])) best = j;
+            if (best >= 0) Aflag[best] &= ~1;
+            s_order[r] = best;
+            A.lens[(size_t)b * A.nbest + r] = best >= 0 ? Alen[best] - 1 : -1;
+            A.scores[(size_t)b * A.nbest + r] = best >= 0 ? Akey[best] : -INFINITY;
+        }
+    }
+    if (tid < nbeam && st == 0 && run) bent[tid] = BeamEnt{Alp[tid], Anode[tid], Alen[tid], Aslot[tid], Atok[tid]};
+    __syncthreads();
+    for (int r = wave; r < A.nbest; r += BEAM_THREADS / 64) {  // one wave's lane 0 walks a hypothesis up the tree
+        const int e = s_order[r];
+        if (lane == 0 && e >= 0) {
+            int node = Anode[e];
+            int *out = A.hyps + ((size_t)b * A.nbest + r) * A.Lmax;
+            for (int d = Alen[e] - 2; d >= 0 && node > 0; --d) {
+                const int2 nd = tree[node];
+                if (d < A.Lmax) out[d] = nd.x;
+                node = nd.y;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -254,6 +599,73 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
 #undef GREEDY
     TSASR_CHECK_LAUNCH("tsasr_greedy_decode_stream");
     return 0;
+}
+
+/* Beam transducer search (speechbrain/decoders/transducer.py:220-373, no LM) for the networks tsasr_greedy_decode takes; see the kernel's
+ * comment. Workspace: tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap) bytes; T = max_frames for the offline call. */
+size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, int cap) {
+    if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
+    return (size_t)B * beam_layout(T, H, J, beam, cap).per_utt;
+}
+
+static int beam_launch(const char *name, const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih,
+                       const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                       size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                       int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                       double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
+    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status, "%s: null pointer", name);
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
+                    "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
+    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
+    TSASR_CHECK_ARG(beam >= 2 && beam <= V && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
+                    "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
+    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
+    const size_t need = tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap);
+    TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
+    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + 6 * sizeof(int));
+    TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
+    BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
+               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope};
+    hipStream_t st = (hipStream_t)stream;
+#define BEAM(TT, WW)                                                                                                            \
+    {                                                                                                                           \
+        auto kern = beam_search_kernel<TT, WW>;                                                                                 \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        kern<<<B, BEAM_THREADS, lds, st>>>(a);                                                                                  \
+    }
+    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) BEAM(float, float) else BEAM(float, bf16_t) }
+    else { if (wdtype == TSASR_F32) BEAM(bf16_t, float) else BEAM(bf16_t, bf16_t) }
+#undef BEAM
+    TSASR_CHECK_LAUNCH(name);
+    return 0;
+}
+
+/* Beam search over enc [B,T,J] from the start (every frame, padding included, as the reference). The workspace is (re)initialised and
+ * left holding the final beam: a tsasr_beam_search_stream call with zero counts (max_frames = T) reads the n-best out again, e.g. with a
+ * larger Lmax. hyps int32 [B,nbest,Lmax] (the first min(len, Lmax) tokens), lens int32 [B,nbest] (-1: fewer beam entries), scores fp64
+ * [B,nbest] = logp / len(prediction incl. the blank prefix), status int32 [B]: 0 ok, 1 more than cap hypotheses in a frame, 2 token
+ * tree full, 3 no hypothesis left to expand; an utterance with a nonzero status stops there, the others are unaffected. */
+int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                      const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
+                      int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
+                      int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
+    return beam_launch("tsasr_beam_search", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+                       nullptr, hyps, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam, expand_beam, slope,
+                       io_dtype, wdtype, stream);
+}
+
+/* The same search over one chunk of a stream: the beam, token tree and predictor slots are resumed from the workspace (laid out for
+ * max_frames; zeroed = start of the stream), n_valid int32 [B] = frames of this chunk to decode per utterance (0: the state is left as it
+ * is). The outputs describe the beam after the chunk; a nonzero status is sticky. Pieces give the bits of one call over the whole. */
+int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                             size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                             int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                             double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
+    TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream: null n_valid");
+    return beam_launch("tsasr_beam_search_stream", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
+                       workspace_bytes, n_valid, hyps, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap, Lmax,
+                       state_beam, expand_beam, slope, io_dtype, wdtype, stream);
 }
 
 }  // extern "C"

@@ -4,22 +4,30 @@ beam_size = 1 -> greedy (transducer.py:138-218): at most one symbol per encoder 
 advances only when it emitted a non-blank. The per-frame decision stays on the device (argmax + masked state update, no
 per-item Python loop as in transducer.py:187-194); only the final token table is read back.
 beam_size > 1 -> the reference's per-utterance beam search with state_beam / expand_beam pruning (transducer.py:220-373,
-no LM fusion): host-side hypothesis bookkeeping exactly as specified there, device-side predictor /
-joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
+no LM fusion). For the recipes' networks one launch of csrc/search.hip decodes the batch (tsasr_beam_search: fp64 scores, the
+reference's list order, one predictor step per hypothesis node); utterances that need more than ``cap`` hypotheses in a frame, and
+every other network shape, run the host loop: host-side hypothesis bookkeeping exactly as specified there (SURVEY.md section 8f
+row f1), device-side predictor / joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
 """
 import os
+import warnings
 
 import torch
 import torch.nn.functional as F
 
+BEAM_CAP = 512                  # hypotheses one frame of the device beam search may hold (its A list); past it: the host loop
+BEAM_STREAM_FRAMES = 4096       # frames a beam_stream workspace is laid out for when the caller does not say
+BEAM_HOST_REDECODES = {"utterances": 0}     # utterances the device beam search handed back to the host loop (status != 0)
+
 
 class TransducerBeamSearcher(torch.nn.Module):
     def __init__(self, decode_network_lst, tjoint, classifier_network, blank_id, beam_size=4, nbest=5, lm_module=None,
-                 lm_weight=0.0, state_beam=2.3, expand_beam=2.3):
+                 lm_weight=0.0, state_beam=2.3, expand_beam=2.3, cap=BEAM_CAP):
         super().__init__()
         self.decode_network_lst, self.tjoint, self.classifier_network = decode_network_lst, tjoint, classifier_network
         self.blank_id, self.beam_size, self.nbest = blank_id, beam_size, nbest
         self.state_beam, self.expand_beam = state_beam, expand_beam
+        self.cap = int(cap)
         if lm_module is not None or lm_weight != 0.0:
             raise NotImplementedError("LM fusion is not part of the TS-ASR recipes")
 
@@ -36,8 +44,22 @@ class TransducerBeamSearcher(torch.nn.Module):
     def _device_greedy_ok(self, tn_output):
         """The one-launch device decoder (csrc/search.hip) covers the recipes' networks: one-hot or learned embedding (<= 64 columns),
         one-layer unidirectional LSTM, Linear projection, joint = LeakyReLU(sum), one Linear classifier."""
+        if os.environ.get("TSASR_GREEDY_KERNEL", "1") == "0":
+            return False
+        return self._device_net_ok(tn_output)
+
+    def _device_beam_ok(self, tn_output):
+        """The one-launch device beam search (csrc/search.hip) takes the networks the greedy decoder takes, with 2 <= beam_size <= V,
+        nbest <= 64 and cap >= beam_size; TSASR_BEAM_KERNEL=0 sends every call to the host loop."""
+        if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output):
+            return False
+        rnn, V = self.decode_network_lst[1].rnn, self.classifier_network[0].w.out_features
+        return bool(2 <= self.beam_size <= V and 1 <= self.nbest <= 64 and self.cap >= self.beam_size and rnn.hidden_size <= 1024
+                    and tn_output.shape[-1] <= 1024 and tn_output.shape[0] > 0 and tn_output.shape[1] > 0)
+
+    def _device_net_ok(self, tn_output):
         from . import nnet, rnnt
-        if os.environ.get("TSASR_GREEDY_KERNEL", "1") == "0" or not tn_output.is_cuda or tn_output.dtype not in (torch.float32, torch.bfloat16):
+        if not tn_output.is_cuda or tn_output.dtype not in (torch.float32, torch.bfloat16):
             return False
         if len(self.decode_network_lst) != 3 or len(self.classifier_network) != 1:
             return False
@@ -164,35 +186,117 @@ class TransducerBeamSearcher(torch.nn.Module):
         A = hypotheses still to be extended at this frame, B = those that emitted blank here (the next frame's A). Until
         |B| >= beam: take the best a in A by logp / len(prediction); stop once the best b in B has logp >= state_beam + logp(a);
         run the predictor on a's last token, score the beam best symbols of the joint at this frame; blank closes a copy of
-        a into B, a non-blank symbol within expand_beam of the best non-blank extends a (new predictor state) back into A."""
-        dev = tn_output.device
-        key = lambda hyp: hyp[1] / len(hyp[0])  # noqa: E731
+        a into B, a non-blank symbol within expand_beam of the best non-blank extends a (new predictor state) back into A.
+        The recipes' networks run on the device (_device_beam_ok); an utterance the device search could not finish within ``cap``
+        hypotheses per frame is decoded again by the host loop (counted in BEAM_HOST_REDECODES)."""
+        if self._device_beam_ok(tn_output):
+            return self._beam_on_device(tn_output)
+        return self._beam_host_loop(tn_output)
+
+    def _beam_host_loop(self, tn_output):
         nbest_batch, nbest_scores = [], []
         for b in range(tn_output.shape[0]):
             beam = [([self.blank_id], 0.0, None)]           # (prediction incl. the blank prefix, logp, predictor state)
             for t in range(tn_output.shape[1]):
-                A, beam = beam, []
-                frame = tn_output[b, t, :].view(1, 1, 1, -1)
-                while len(beam) < self.beam_size:
-                    a = max(A, key=key)
-                    if beam and max(beam, key=key)[1] >= self.state_beam + a[1]:
-                        break
-                    A.remove(a)
-                    tok = torch.full((1, 1), a[0][-1], dtype=torch.long, device=dev)
-                    out_pn, new_state = self._pn(tok, a[2])
-                    j = self.tjoint(frame, out_pn.unsqueeze(0))
-                    for layer in self.classifier_network:
-                        j = layer(j)
-                    logp, pos = torch.topk(F.log_softmax(j.float(), dim=-1).view(-1), k=self.beam_size)
-                    logp, pos = logp.tolist(), pos.tolist()      # one host read per expansion (the reference: one per symbol)
-                    best_nonblank = logp[0] if pos[0] != self.blank_id else logp[1]
-                    for lp, sym in zip(logp, pos):
-                        if sym == self.blank_id:
-                            beam.append((a[0][:], a[1] + lp, a[2]))
-                        elif lp >= best_nonblank - self.expand_beam:
-                            A.append((a[0] + [sym], a[1] + lp, new_state))
-            ranked = sorted(beam, key=key, reverse=True)[: self.nbest]
-            nbest_batch.append([h[0][1:] for h in ranked])
-            nbest_scores.append([h[1] / len(h[0]) for h in ranked])
+                beam = self._beam_frame(beam, tn_output[b, t, :])
+            hyps, scores = self._beam_rank(beam)
+            nbest_batch.append(hyps)
+            nbest_scores.append(scores)
         best = [n[0] for n in nbest_batch]
         return best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+
+    def _beam_frame(self, A, enc_t):
+        """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it."""
+        key = lambda hyp: hyp[1] / len(hyp[0])  # noqa: E731
+        dev = enc_t.device
+        frame = enc_t.view(1, 1, 1, -1)
+        beam = []
+        while len(beam) < self.beam_size:
+            a = max(A, key=key)
+            if beam and max(beam, key=key)[1] >= self.state_beam + a[1]:
+                break
+            A.remove(a)
+            tok = torch.full((1, 1), a[0][-1], dtype=torch.long, device=dev)
+            out_pn, new_state = self._pn(tok, a[2])
+            j = self.tjoint(frame, out_pn.unsqueeze(0))
+            for layer in self.classifier_network:
+                j = layer(j)
+            logp, pos = torch.topk(F.log_softmax(j.float(), dim=-1).view(-1), k=self.beam_size)
+            logp, pos = logp.tolist(), pos.tolist()      # one host read per expansion (the reference: one per symbol)
+            best_nonblank = logp[0] if pos[0] != self.blank_id else logp[1]
+            for lp, sym in zip(logp, pos):
+                if sym == self.blank_id:
+                    beam.append((a[0][:], a[1] + lp, a[2]))
+                elif lp >= best_nonblank - self.expand_beam:
+                    A.append((a[0] + [sym], a[1] + lp, new_state))
+        return beam
+
+    def _beam_rank(self, beam):
+        """(n-best symbol lists, their logp / len) of a beam: sorted(beam, key, reverse=True)[:nbest] (stable, as the reference)."""
+        ranked = sorted(beam, key=lambda hyp: hyp[1] / len(hyp[0]), reverse=True)[: self.nbest]
+        return [h[0][1:] for h in ranked], [h[1] / len(h[0]) for h in ranked]
+
+    def _device_beam_call(self, enc, fn, *extra):
+        table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
+        return fn(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id, self.tjoint.nonlinearity.negative_slope, wdt, self.beam_size,
+                  self.nbest, self.state_beam, self.expand_beam, self.cap, *extra)
+
+    @torch.no_grad()
+    def _beam_on_device(self, tn_output):
+        from . import ops
+        enc = tn_output.contiguous()
+        nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search)
+        bad = [b for b in range(enc.shape[0]) if int(status[b]) != 0]
+        if bad:
+            if BEAM_HOST_REDECODES["utterances"] == 0:
+                warnings.warn(f"ts-asr_amd: the device beam search stopped {len(bad)} utterance(s) "
+                              f"({sorted({ops.BEAM_STATUS[int(status[b])] for b in bad})}, cap={self.cap}); they are decoded by the host "
+                              f"loop (counted in decoders.BEAM_HOST_REDECODES)", RuntimeWarning, stacklevel=3)
+            BEAM_HOST_REDECODES["utterances"] += len(bad)
+            for b in bad:
+                _, _, hyps, scores = self._beam_host_loop(enc[b:b + 1])
+                nbest_batch[b], nbest_scores[b] = hyps[0], scores[0]
+        best = [n[0] for n in nbest_batch]
+        return best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+
+    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None):
+        """Beam search over the next frames of a batch of streams, the counterpart of greedy_stream: enc_chunk [B,C,J], ``state`` the
+        value returned by the previous call (None: start of the streams), n_valid int32 [B] = frames of this chunk that belong to each
+        stream (None: all C); max_frames = frames a stream may reach (device route; default BEAM_STREAM_FRAMES), read at the first call.
+        Returns (current best hypothesis of each stream, state); state["nbest"] / state["scores"] hold the n-best lists and their
+        logp / len. Under beam search the best prefix can change, so the whole hypothesis is returned, not new symbols. Decoding a
+        sequence in chunks gives the bits of one call over it: the device route resumes its workspace (csrc/search.hip), the host
+        route carries the beam lists. A stream past ``cap`` hypotheses in a frame cannot be re-decoded chunk by chunk: RuntimeError."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("beam_stream is inference only: run it under torch.no_grad()")
+        B, T, _ = enc_chunk.shape
+        dev = enc_chunk.device
+        nv = torch.full((B,), T, dtype=torch.int32, device=dev) if n_valid is None else n_valid.to(device=dev, dtype=torch.int32)
+        if self._device_beam_ok(enc_chunk):
+            from . import ops
+            enc = enc_chunk.contiguous()
+            if state is None:
+                mf = int(max_frames or BEAM_STREAM_FRAMES)
+                nbytes = ops.beam_stream_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
+                state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf}
+            elif "dev" not in state:
+                raise ValueError("beam_stream: this state was made by the host route")
+            nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"])
+            bad = [b for b in range(B) if int(status[b]) != 0]
+            if bad:
+                raise RuntimeError(f"beam_stream: stream(s) {bad} stopped ({sorted({ops.BEAM_STATUS[int(status[b])] for b in bad})}) with "
+                                   f"cap={self.cap} hypotheses per frame and max_frames={state['max_frames']}; restart the stream with a "
+                                   f"larger cap (TransducerBeamSearcher(cap=...)) or max_frames")
+            state["nbest"], state["scores"] = nbest_batch, nbest_scores
+            return [n[0] for n in nbest_batch], state
+        if state is None:
+            state = {"beams": [[([self.blank_id], 0.0, None)] for _ in range(B)]}
+        elif "beams" not in state:
+            raise ValueError("beam_stream: this state was made by the device route")
+        counts = nv.cpu().tolist()
+        for b in range(B):
+            for t in range(min(max(int(counts[b]), 0), T)):
+                state["beams"][b] = self._beam_frame(state["beams"][b], enc_chunk[b, t, :])
+        ranked = [self._beam_rank(beam) for beam in state["beams"]]
+        state["nbest"], state["scores"] = [r[0] for r in ranked], [r[1] for r in ranked]
+        return [n[0] for n in state["nbest"]], state

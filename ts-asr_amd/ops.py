@@ -34,6 +34,8 @@ STATUS = {
     "relpos_attention(need_weights=True: attention maps for plots)": "LIB (ATen matmul / softmax), logged",
     "streaming (causal encoder, chunk by chunk)": "HIP (stream.hip: relpos_attention_stream on a K/V cache, convmod_stream with carried history; "
                                                   "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
+    "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search / beam_search_stream, one launch per batch or chunk; "
+                                                         "the host loop only for other predictor shapes and utterances past cap)",
 }
 
 STRICT_HIP = os.environ.get("TSASR_STRICT_HIP", "0") == "1"
@@ -2279,3 +2281,136 @@ def greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_
                                                B, T, J, H, table.shape[1], mats[3].shape[0], int(blank), float(slope), C.io_dtype(enc), wdtype,
                                                C.stream_ptr()), "tsasr_greedy_decode_stream")
     return preds, logp
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Beam transducer search on the device (csrc/search.hip: tsasr_beam_search / tsasr_beam_search_stream). Inference only.
+BEAM_STATUS = {0: "ok", 1: "a frame needed more than cap hypotheses", 2: "token tree full", 3: "no hypothesis left to expand"}
+
+
+def beam_stream_workspace_bytes(B, T, H, J, beam, cap):
+    """Bytes of the beam-search workspace for B utterances of at most T frames (include/tsasr_hip.h): per utterance a header with the
+    beam, a token tree of 1 + (T + 1) * beam + cap nodes and cap + beam predictor slots of J + 2H floats."""
+    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
+    B, T, H, J, beam, cap = (int(v) for v in (B, T, H, J, beam, cap))
+    if min(B, T, H, J, beam, cap) <= 0:
+        return 0
+    return B * (a16(64 + 24 * beam) + a16(8 * (1 + (T + 1) * beam + cap)) + 4 * (cap + beam) * (J + 2 * H))
+
+
+def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype):
+    """Shapes and settings tsasr_beam_search takes (ValueError before any device call)."""
+    if not isinstance(enc, torch.Tensor) or enc.dim() != 3 or enc.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("beam_search: enc must be a float32 / bfloat16 [B, T, J] tensor")
+    B, T, J = enc.shape
+    if B == 0 or T == 0:
+        raise ValueError(f"beam_search: empty enc {tuple(enc.shape)}")
+    if len(mats) != 4:
+        raise ValueError("beam_search: mats = [W_ih, W_hh, W_proj, W_head]")
+    w_ih, w_hh, w_proj, w_head = mats
+    H, V, E = w_hh.shape[1], w_head.shape[0], table.shape[1]
+    want_w = torch.float32 if wdtype == C.F32 else torch.bfloat16
+    if wdtype not in (C.F32, C.BF16) or any(m.dtype != want_w or not m.is_contiguous() for m in mats):
+        raise ValueError(f"beam_search: weight matrices must be contiguous {want_w}")
+    if table.dtype != torch.float32 or table.dim() != 2 or E > 64:
+        raise ValueError("beam_search: the embedding table must be fp32 [n_emb, E <= 64]")
+    if tuple(w_ih.shape) != (4 * H, E) or tuple(w_hh.shape) != (4 * H, H) or tuple(w_proj.shape) != (J, H) or tuple(w_head.shape) != (V, J):
+        raise ValueError(f"beam_search: weight shapes {[tuple(m.shape) for m in mats]} do not fit E={E} H={H} J={J}")
+    if H % 4 or J % 4 or H > 1024 or J > 1024 or V < 2 or V > 63:
+        raise ValueError(f"beam_search: H={H} and J={J} must be multiples of 4 <= 1024 and 2 <= V={V} <= 63")
+    for name, bvec, n in (("b_ih", b_ih, 4 * H), ("b_hh", b_hh, 4 * H), ("b_proj", b_proj, J), ("b_head", b_head, V)):
+        if bvec is not None and (bvec.dtype != torch.float32 or bvec.numel() != n):
+            raise ValueError(f"beam_search: {name} must be fp32 [{n}] or None")
+    if not 0 <= int(blank) < V:
+        raise ValueError(f"beam_search: blank {blank} outside the vocabulary of {V}")
+    if not 2 <= int(beam_size) <= V:
+        raise ValueError(f"beam_search: beam_size {beam_size} must be in [2, V={V}]")
+    if not 1 <= int(nbest) <= 64:
+        raise ValueError(f"beam_search: nbest {nbest} must be in [1, 64]")
+    if int(cap) < int(beam_size):
+        raise ValueError(f"beam_search: cap {cap} below beam_size {beam_size}")
+    return B, T, J, H, E, V
+
+
+def _beam_read(run, B, nbest, Lmax, device):
+    """Launch ``run(hyps, lens, scores, status, Lmax, readout)``; when a hypothesis is longer than Lmax, read the n-best out again (a
+    zero-count stream call on the workspace the first launch left). Returns (n-best token lists, n-best fp64 scores, status) on the host."""
+    hyps = torch.empty(B, nbest, Lmax, dtype=torch.int32, device=device)
+    lens = torch.empty(B, nbest, dtype=torch.int32, device=device)
+    scores = torch.empty(B, nbest, dtype=torch.float64, device=device)
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    run(hyps, lens, scores, status, Lmax, False)
+    lens_h, st_h = lens.cpu(), status.cpu()
+    longest = int(lens_h.max())
+    if longest > Lmax:
+        hyps = torch.empty(B, nbest, longest, dtype=torch.int32, device=device)
+        run(hyps, lens, scores, status, longest, True)
+    hy, sc = hyps.cpu(), scores.cpu()
+    out, out_sc = [], []
+    for b in range(B):
+        rows = [r for r in range(nbest) if int(lens_h[b, r]) >= 0] if int(st_h[b]) == 0 else []
+        out.append([hy[b, r, : int(lens_h[b, r])].tolist() for r in rows])
+        out_sc.append([float(sc[b, r]) for r in rows])
+    return out, out_sc, st_h
+
+
+def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
+    return (C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]), C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head),
+            C.ptr(ws), ws.numel())
+
+
+def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
+                workspace=None):
+    """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
+    lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
+    n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap)."""
+    _no_grad_only("beam_search")
+    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
+    need = beam_stream_workspace_bytes(B, T, H, J, beam_size, cap)
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
+        raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
+    C.require_gpu(enc, table, *mats)
+    encc = enc.contiguous()
+    ws = torch.empty(need, dtype=torch.uint8, device=enc.device) if workspace is None else workspace
+    zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
+    ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws)
+
+    def run(hyps, lens, scores, status, Lmax, readout):
+        tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
+                C.io_dtype(encc), wdtype, C.stream_ptr())
+        outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
+        if readout:
+            C.check(C.lib().tsasr_beam_search_stream(C.ptr(encc), *ptrs, C.ptr(zero), *outs, B, T, T, J, H, E, V, *tail), "tsasr_beam_search_stream")
+        else:
+            C.check(C.lib().tsasr_beam_search(C.ptr(encc), *ptrs, *outs, B, T, J, H, E, V, *tail), "tsasr_beam_search")
+
+    with prof.region("beam_search"):
+        return _beam_read(run, B, int(nbest), 2 * T + 16, enc.device)
+
+
+def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
+                       workspace, n_valid, max_frames):
+    """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
+    (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
+    beam_search returns, for the beam after the chunk."""
+    _no_grad_only("beam_search_stream")
+    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
+    need = beam_stream_workspace_bytes(B, max_frames, H, J, beam_size, cap)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
+    if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
+        raise ValueError(f"beam_search_stream: n_valid must be a [B={B}] tensor")
+    C.require_gpu(enc, table, workspace, n_valid, *mats)
+    encc = enc.contiguous()
+    nv = n_valid.to(torch.int32).contiguous()
+    zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
+    ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
+
+    def run(hyps, lens, scores, status, Lmax, readout):
+        C.check(C.lib().tsasr_beam_search_stream(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores),
+                                                 C.ptr(status), B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size), int(nbest),
+                                                 int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
+                                                 wdtype, C.stream_ptr()), "tsasr_beam_search_stream")
+
+    with prof.region("beam_search_stream"):
+        return _beam_read(run, B, int(nbest), 256, enc.device)

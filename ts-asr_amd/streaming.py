@@ -7,6 +7,10 @@
             new_tokens = st.push(feats)             # list (per stream) of the symbols emitted for these frames
         hyps = st.finish()
 
+StreamingTranscriber(brain, search="beam") decodes with the recipe's beam searcher instead (TransducerBeamSearcher.beam_stream): push()
+then returns each stream's best hypothesis so far as a whole token list (its prefix may change), finish() the best hypotheses and
+nbest() the n-best lists with their logp / len.
+
 Every block of such a model is causal: the front-end pads time on the left only, the depthwise convolution is left-padded, the
 attention mask (look-ahead or block-causal on absolute frame indices) never looks past the current chunk, and RelPosEncXL's table is
 symmetric, so one half table serves every offset. A push therefore costs the new frames only: the front-end carries the last 2 input
@@ -47,7 +51,9 @@ class StreamingTranscriber:
     weights again). That is one bf16 copy of those matrices in memory; do not change the weights in place (``p.data``) while a stream
     is open. finish() removes the copies."""
 
-    def __init__(self, brain):
+    def __init__(self, brain, search="greedy"):
+        if search not in ("greedy", "beam"):
+            raise ValueError(f"StreamingTranscriber: search must be 'greedy' or 'beam', got {search!r}")
         m = brain.modules
         enc, fe = m["encoder"] if isinstance(m, dict) else m.encoder, m["frontend"] if isinstance(m, dict) else m.frontend
         if not getattr(enc, "causal", False):
@@ -58,7 +64,9 @@ class StreamingTranscriber:
         self.brain, self.encoder, self.frontend = brain, enc, fe
         self.encoder_proj = m["encoder_proj"] if isinstance(m, dict) else m.encoder_proj
         hp = brain.hparams
-        self.searcher = hp["greedy_searcher"] if isinstance(hp, dict) else hp.greedy_searcher
+        name = "greedy_searcher" if search == "greedy" else "beam_searcher"
+        self.search = search
+        self.searcher = hp[name] if isinstance(hp, dict) else getattr(hp, name)
         self._started = False
         self._copies = []
 
@@ -126,7 +134,7 @@ class StreamingTranscriber:
             raise ValueError(f"with block-causal attention over {blk} frames a push carries a multiple of {4 * blk} feature frames "
                              f"except the last one: got {F}")
         if F == 0:
-            return [[] for _ in range(self.B)]
+            return [list(h) for h in self.hyps] if self.search == "beam" else [[] for _ in range(self.B)]
         t_done = 0 if self.enc_state is None else self.enc_state["t0"]
         if t_done + _enc_frames(F) > self.max_frames:      # checked before any state of the stream moves
             raise ValueError(f"the push would take the stream past start()'s max_frames: {t_done} + {_enc_frames(F)} > {self.max_frames} encoder frames")
@@ -145,6 +153,11 @@ class StreamingTranscriber:
             self.enc_chunks.append(e)
         e = self.encoder_proj(e)
         n_valid = (valid - t0).clamp(0, e.shape[1]).to(torch.int32)
+        if self.search == "beam":                 # the best hypothesis so far (its prefix may change with later frames)
+            best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames)
+            self.hyps = [list(h) for h in best]
+            self.closed = bool(last)
+            return best
         new, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid)
         for b, toks in enumerate(new):
             self.hyps[b].extend(toks)
@@ -156,6 +169,14 @@ class StreamingTranscriber:
         self.closed = True
         self._drop_copies()
         return [list(h) for h in self.hyps]
+
+    def nbest(self):
+        """search="beam": (n-best symbol lists of every stream, their logp / len), best first, as TransducerBeamSearcher returns them."""
+        if self.search != "beam":
+            raise RuntimeError("nbest() needs StreamingTranscriber(brain, search='beam')")
+        if self.search_state is None:
+            return [[[]] for _ in range(self.B)], [[0.0] for _ in range(self.B)]
+        return [[list(h) for h in n] for n in self.search_state["nbest"]], [list(s) for s in self.search_state["scores"]]
 
     def _drop_copies(self):
         for p, copy in self._copies:
