@@ -195,12 +195,13 @@ __global__ __launch_bounds__(GBG_THREADS, 2) void gemm_big_kernel(BigArgs a) {
                         const float t = fmaxf(x, x * slope_eff);
                         v[e] = __uint_as_float(__float_as_uint(t) & (unsigned)((int)(km << (31 - e)) >> 31));
                     }
-                    if constexpr (MASK) {     // sign bits of the values AS STORED (bf16, pair-converted; -0 counts as not negative)
+                    if constexpr (MASK) {     // sign bits of the values AS STORED (bf16, pair-converted; -0 counts as not negative: each half is
+                                              // tested on its own - `w > 0x80000000` would count a -0 above a non-zero neighbour)
                         unsigned neg = 0;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const unsigned w = pk_bf16(v[2 * q], v[2 * q + 1]);
-                            neg |= ((w & 0xffffu) > 0x8000u ? 1u : 0u) << (2 * q) | (w > 0x80000000u ? 1u : 0u) << (2 * q + 1);
+                            neg |= ((w & 0xffffu) > 0x8000u ? 1u : 0u) << (2 * q) | ((w >> 16) > 0x8000u ? 1u : 0u) << (2 * q + 1);
                         }
                         if (FULL || m < a.M) a.mask[((long long)m * a.N + n) >> 3] = (unsigned short)((km & 0xffu) | (neg << 8));
                     }
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(GBG_THREADS, 2) void gemm_big_kernel(BigArgs a) {
                         const unsigned yw[4] = {yraw[it].x, yraw[it].y, yraw[it].z, yraw[it].w};
 #pragma unroll
                         for (int q = 0; q < 4; ++q)       // sign bit of a bf16 activation that is not a zero
-                            kw |= (((yw[q] & 0xffffu) > 0x8000u ? 1u : 0u) << (8 + 2 * q)) | ((yw[q] > 0x80000000u ? 1u : 0u) << (9 + 2 * q));
+                            kw |= (((yw[q] & 0xffffu) > 0x8000u ? 1u : 0u) << (8 + 2 * q)) | (((yw[q] >> 16) > 0x8000u ? 1u : 0u) << (9 + 2 * q));
                     }
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
