@@ -212,6 +212,9 @@ def lab():
         L.tsasr_lab_fill_lds.argtypes, L.tsasr_lab_fill_lds.restype = [ctypes.c_uint, c_void_p], c_int
         L.tsasr_lab_fill.argtypes, L.tsasr_lab_fill.restype = [c_void_p, ctypes.c_uint, c_size_t, c_void_p], c_int
         L.tsasr_lab_stamp.argtypes, L.tsasr_lab_stamp.restype = [c_void_p, c_void_p], c_int
+        L.tsasr_lab_dpk_part_bytes.argtypes, L.tsasr_lab_dpk_part_bytes.restype = [c_int, c_int, c_int], c_size_t
+        L.tsasr_lab_dpk.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+        L.tsasr_lab_dpk.restype = c_int
         _lab = L
     return _lab
 

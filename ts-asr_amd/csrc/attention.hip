@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "attn_common.h"
+#include "dpk_pass.h"
 
 #ifndef AT_NW
 #define AT_NW 4           // waves per workgroup (forward and query-major backward kernels)
@@ -74,17 +75,6 @@ __device__ __forceinline__ void load8_clamped(const T *__restrict__ row, int d0,
     }
 }
 
-// The same 8 elements WITHOUT the zeroing of the dims at and beyond Dh (the address is clamped into the row; the caller masks when it
-// consumes the values): load8_clamped's mask overwrites the load's destination, i.e. waits for the load on the spot - a sequence of
-// calls was a sequence of round trips (20 of them at the head of relpos_attn_bwd_q). FAST as a compile-time flag: no branch per call.
-template <typename T, bool FAST>
-__device__ __forceinline__ void load8_raw(const T *__restrict__ row, int d0, int Dh, float (&v)[8]) {
-    if constexpr (FAST) ld8(row + min(d0, Dh - 8), v);
-    else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ld1(row + min(d0 + j, Dh - 1));
-    }
-}
 
 // stage ROWS rows of Dh elements (row r -> src + r*src_stride, or zeros when r is outside [lo,hi)) into lds[ROWS][AT_LD]:
 // all of a thread's pieces are requested before the first one is stored
@@ -1238,110 +1228,7 @@ __global__ __launch_bounds__(256) void relpos_attn_kv_merge_kernel(const float *
             if (d + e < Dh) st1(dst + e, a[e]);
 }
 
-// d(pk)[r][h*Dh + d] = sum_b sum_i dS[b][h][i][j = r + i - (T-1)] * (q + v)[b][i][h][d]  - the gradient of the projected positional
-// table, straight from the materialised dS (the first version shifted dS back onto an (r, i) grid in HBM - 32 MB - and ran a library
-// batched GEMM over it whose K dimension was half zeros: 20 + 31 + 5 us per layer). workgroup = (64 band rows, head, group of
-// utterances); per utterance and block of 64 queries that can reach those rows: the 64 x 136 rectangle of dS goes to LDS as
-// 16-byte pieces, the skew happens on the way into the A tile (A[rl][i] = dS[i][r0 + rl + i - (T-1)], 2-byte LDS reads, 16-byte
-// writes), (q+v) rows are the B tile (k-major: transposing fragment reads), 4 MFMAs per wave; blocks of queries that cannot reach
-// the rows are skipped (half of them). Partial sums per utterance group, summed by dpk_reduce_kernel in a fixed order.
-#define SH_LD 136
-#define DPK_LD 72
-template <typename T>
-__device__ __forceinline__ void dpk_body(const T *__restrict__ ds, const T *__restrict__ qv /*[H][B*T][Dh]*/,
-                                         const int32_t *__restrict__ key_lens, float *__restrict__ part /*[G][R][H*64]*/,
-                                         int Bn, int Tn, int Tp, int H, int Dh, int causal, int bgroup, int isplit, int i_span,
-                                         int bx, int by, int bz) {
-    // (bx, by, bz) = the block index of the one-job launch; isplit > 1 (long sequences, few utterances): bz = utterance group * isplit +
-    // query range; a workgroup walks the query blocks of [ipart * i_span, (ipart + 1) * i_span) only - the band rows around r = T-1 are
-    // reached by every query block
-    __shared__ __attribute__((aligned(16))) T raw[64 * SH_LD];
-    __shared__ __attribute__((aligned(16))) bf16_t a_tile[64 * DPK_LD], b_tile[64 * DPK_LD];
-    const int r0 = bx * 64, h = by, grp = bz / isplit, ipart = bz % isplit;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-    const int rblk = wave & 1, dblk = wave >> 1;
-    const int R = 2 * Tn - 1;
-    const int grp4 = lane >> 4, mhalf = grp4 & 1, q4 = (lane & 15) >> 2, p4 = lane & 3;
-    constexpr int VE = 16 / (int)sizeof(T), NG = SH_LD / VE;
-    f32x16 acc = {0};
-    const int b_end = min(Bn, (grp + 1) * bgroup);
-    const int i_lo = ipart * i_span, i_hi = min(Tn, i_lo + i_span);
-    // band rows whose every (query, key) pair lies beyond the causal limit (j - i = r - (T-1) > chunk - 1) only ever see zeros
-    const bool dead = causal && r0 - (Tn - 1) > max(causal, 1) - 1;
-    // (a version that requested the next pair's global loads before building this pair's tiles - LDS-only barriers in between -
-    // measured 5 % slower than this plain loop: two to four workgroups share a CU and cover each other's round trips)
-    for (int b = grp * bgroup; b < b_end && !dead; ++b) {
-        const int len = key_lens ? min(max(key_lens[b], 1), Tn) : Tn;
-        const T *src = ds + (((long long)b * H + h) * Tn) * Tp;
-        const T *qrow = qv + ((long long)h * Bn + b) * Tn * Dh;
-        for (int i0 = i_lo; i0 < i_hi; i0 += 64) {
-            const int jlo = r0 + i0 - (Tn - 1);                  // key of (rl = 0, il = 0); keys jlo .. jlo + 126 are touched
-            if (jlo + 126 < 0 || jlo >= len) continue;           // no query of this block reaches these band rows (workgroup-uniform)
-            const int jal = (jlo >= 0 ? jlo : jlo - 7) / 8 * 8, off = jlo - jal;
-            __syncthreads();                                     // previous tiles consumed
-            for (int e = tid; e < 64 * NG; e += 256) {           // always-issued clamped loads; validity decided below
-                const int il = e / NG, gq = e % NG, j = jal + gq * VE;
-                *reinterpret_cast<uint4 *>(raw + il * SH_LD + gq * VE) =
-                    *reinterpret_cast<const uint4 *>(src + (long long)min(i0 + il, Tn - 1) * Tp + min(max(j, 0), Tp - VE));
-            }
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {                     // (q + v) rows i0 .. i0+63: 64 x 8 pieces of 8 dims
-                const int e = tid + 256 * it, il = e >> 3, c = (e & 7) * 8;
-                float v8[8];
-                if ((Dh % 8) == 0) load8_raw<T, true>(qrow + (long long)min(i0 + il, Tn - 1) * Dh, c, Dh, v8);     // (both pieces of the
-                else load8_raw<T, false>(qrow + (long long)min(i0 + il, Tn - 1) * Dh, c, Dh, v8);                  //  thread in flight together)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v8[q] = (c + q < Dh) ? v8[q] : 0.f;
-                if (i0 + il >= Tn) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) v8[q] = 0.f;
-                }
-                st8(b_tile + il * DPK_LD + c, v8);
-            }
-            __syncthreads();
-            {   // A tile: thread = (band row rl, 16 consecutive queries)
-                // All 16 reads are issued together and masked afterwards by a bit mask: written as `valid ? raw[..] : 0` with the four-term
-                // validity test, each read sat in its own exec-masked block behind ~50 instructions of branches and was waited for on the
-                // spot - 16 serialized LDS round trips per tile for 4 MFMAs. Without a look-ahead mask the valid elements of a thread are a
-                // contiguous range of q (j = jlo + rl + il0 + q in [0, len), i0 + il0 + q < Tn).
-                const int rl = tid >> 2, il0 = (tid & 3) * 16;
-                float v16[16];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) v16[q] = (float)raw[(il0 + q) * SH_LD + off + rl + il0 + q];     // always inside the 64 x 136 rectangle
-                pin_all(v16);
-                const int jq0 = jlo + rl + il0;                                                   // key of q = 0
-                const int q_lo = min(max(-jq0, 0), 16), q_hi = min(max(min(len - jq0, Tn - i0 - il0), 0), 16);
-                unsigned vm = q_hi > q_lo ? (0xffffu >> (16 - q_hi)) & (0xffffu << q_lo) : 0u;
-                if (causal) {       // workgroup-uniform
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) vm &= ~((jq0 + q > causal_limit(i0 + il0 + q, causal) ? 1u : 0u) << q);
-                }
-#pragma unroll
-                for (int q = 0; q < 16; ++q) v16[q] = __uint_as_float(__float_as_uint(v16[q]) & (unsigned)((int)(vm << (31 - q)) >> 31));
-                st8(a_tile + rl * DPK_LD + il0, *reinterpret_cast<float(*)[8]>(&v16[0]));
-                st8(a_tile + rl * DPK_LD + il0 + 8, *reinterpret_cast<float(*)[8]>(&v16[8]));
-            }
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 af = *reinterpret_cast<const bf16x8 *>(a_tile + (32 * rblk + r) * DPK_LD + 16 * s + 8 * hh);
-                const bf16_t *bp = b_tile + (16 * s + 8 * hh + q4) * DPK_LD + 32 * dblk + 16 * mhalf + 4 * p4;
-                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4 *)(bp));
-                const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4 *)(bp + 4 * DPK_LD));
-                bf16x8 bfr;
-                bfr[0] = lo[0]; bfr[1] = lo[1]; bfr[2] = lo[2]; bfr[3] = lo[3]; bfr[4] = hi[0]; bfr[5] = hi[1]; bfr[6] = hi[2]; bfr[7] = hi[3];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
-            }
-        }
-    }
-    // accumulator: rows = band rows 32*rblk + (g&3) + 8(g>>2) + 4hh, column = head dim 32*dblk + r
-    float *pw = part + ((long long)bz * R) * (H * 64) + h * 64 + 32 * dblk + r;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int rg = r0 + 32 * rblk + (g & 3) + 8 * (g >> 2) + 4 * hh;
-        if (rg < R) pw[(long long)rg * (H * 64)] = acc[g];
-    }
-}
+// d(pk) pass bodies (dpk_body, dpk_once_body, dpk_reduce_body): csrc/dpk_pass.h
 
 template <typename T>
 __global__ __launch_bounds__(256) void relpos_dpk_kernel(const T *__restrict__ ds, const T *__restrict__ qv, const int32_t *__restrict__ key_lens,
@@ -1349,19 +1236,11 @@ __global__ __launch_bounds__(256) void relpos_dpk_kernel(const T *__restrict__ d
                                                          int isplit, int i_span) {
     dpk_body<T>(ds, qv, key_lens, part, Bn, Tn, Tp, H, Dh, causal, bgroup, isplit, i_span, blockIdx.x, blockIdx.y, blockIdx.z);
 }
-
-// dpk[r][h*Dh + d] = sum over the utterance groups of part[g][r][h*64 + d], written in the io dtype (blocks `blk` of `nblk` of one job)
-template <typename T>
-__device__ __forceinline__ void dpk_reduce_body(const float *__restrict__ part, T *__restrict__ dpk, int R, int H, int Dh, int G, int blk, int nblk) {
-    const long long n = (long long)R * H * 64;
-    for (long long e = blk * 256LL + threadIdx.x; e < n; e += (long long)nblk * 256) {
-        const int c = (int)(e % (H * 64)), d = c & 63, hq = c >> 6;
-        const long long rr = e / (H * 64);
-        if (d >= Dh) continue;
-        float sum = 0.f;
-        for (int g = 0; g < G; ++g) sum += part[(long long)g * n + e];
-        st1(dpk + rr * (H * Dh) + hq * Dh + d, sum);
-    }
+// the one-pass form (short path): workgroup = (head, utterance group)
+__global__ __launch_bounds__(DPO_TH, 4) void relpos_dpk_once_kernel(const bf16_t *__restrict__ ds, const bf16_t *__restrict__ qv,
+                                                                    const int32_t *__restrict__ key_lens, float *__restrict__ part, int Bn, int Tn,
+                                                                    int Tp, int H, int causal, int bgroup) {
+    dpk_once_body(ds, qv, key_lens, part, Bn, Tn, Tp, H, causal, bgroup, blockIdx.x, blockIdx.y);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void dpk_reduce_kernel(const float *__restrict__ part, T *__restrict__ dpk, int R, int H, int Dh, int G) {
@@ -1379,6 +1258,7 @@ struct DpkJob {
     float *part;
     void *dpk;
     int Bn, Tn, Tp, H, Dh, causal, bgroup, isplit, i_span, G, nbx, io_dtype;
+    int once;                               // 1: dpk_once_body (ntiles = H * G workgroups of DPO_TH threads), 0: dpk_body
     int tile0, ntiles, rtile0, rtiles;      // first block / block count of this job in the grouped pass and in the grouped reduction
 };
 
@@ -1394,6 +1274,12 @@ __global__ __launch_bounds__(256) void relpos_dpk_group_kernel(const DpkJob *__r
     const int lid = blockIdx.x - j.tile0;
     dpk_body<T>((const T *)j.ds, (const T *)j.qv, j.key_lens, j.part, j.Bn, j.Tn, j.Tp, j.H, j.Dh, j.causal, j.bgroup, j.isplit, j.i_span,
                 lid % j.nbx, (lid / j.nbx) % j.H, lid / (j.nbx * j.H));
+}
+
+__global__ __launch_bounds__(DPO_TH, 4) void relpos_dpk_once_group_kernel(const DpkJob *__restrict__ jobs, int njobs) {
+    const DpkJob j = jobs[dpk_find_job(jobs, njobs, blockIdx.x, false)];
+    const int lid = blockIdx.x - j.tile0;
+    dpk_once_body((const bf16_t *)j.ds, (const bf16_t *)j.qv, j.key_lens, j.part, j.Bn, j.Tn, j.Tp, j.H, j.causal, j.bgroup, lid % j.H, lid / j.H);
 }
 
 template <typename T>
@@ -1427,6 +1313,10 @@ static bool attn_kv_split_enabled() {      // TSASR_ATTN_KV_SPLIT=0: one workgro
 }
 static bool attn_zero_band_enabled() {      // TSASR_ATTN_ZERO_BAND=0: clear the whole P_d / dS matrices under a look-ahead mask (A/B, round 4's form)
     static const bool on = [] { const char *e = getenv("TSASR_ATTN_ZERO_BAND"); return !e || e[0] != '0'; }();
+    return on;
+}
+static bool dpk_once_enabled() {      // TSASR_DPK_ONCE=0: dpk_body on the short path too (A/B runs; bit-identical d(pk) either way)
+    static const bool on = [] { const char *e = getenv("TSASR_DPK_ONCE"); return !e || e[0] != '0'; }();
     return on;
 }
 static int attn_short_version() {   // TSASR_ATTN_SHORT = 1: round 3's short-sequence forward (A/B); default 2
@@ -1492,11 +1382,8 @@ static int attn_dpk_max_isplit(int T) { return std::max(1, std::min(cdiv(T, 64) 
 // fills the chip anyway; fewer, longer workgroups write a quarter of the partial planes and leave the reduction a quarter to add
 // (configs[1], ms per step at 1024 / 512 / 256 / 128 workgroups per layer: 11.88 / 11.83 / 11.80 / 11.87). A stand-alone launch (one
 // layer, no gradient arena) under-fills the chip with it - the price of keeping both forms bit-identical.
-static int attn_bgroup(int B, int T) {
-    static const int dpk_wgs = 256;
-    const int want = std::max(1, dpk_wgs / (4 * cdiv(2 * T - 1, 64)));
-    return std::max(1, cdiv(B, std::min(B, want)));
-}
+// The one-pass body keeps the same groups (one workgroup per head and group): same partial planes, same order of sums.
+static int attn_bgroup(int B, int T) { return dpk_bgroup(B, T); }
 static size_t attn_qv_bytes(int B, int T, int H) { return align_up((size_t)B * T * H * AT_DP * sizeof(float), 256); }
 static size_t attn_part_bytes(int B, int T, int H) {
     return align_up((size_t)cdiv(B, attn_bgroup(B, T)) * attn_dpk_max_isplit(T) * (2 * T - 1) * H * 64 * sizeof(float), 256);
@@ -1544,6 +1431,7 @@ static void launch_attn_bwd(const void *qkv, const void *pk, const float *bias_u
     const int nparts = attn_key_parts(B, Tn, H, causal, &part_keys);
     const int isplit = std::min(attn_dpk_isplit(B, Tn, H, causal, G), attn_dpk_max_isplit(Tn)), i_span = cdiv(cdiv(Tn, 64), isplit) * 64;
     const bool short_path = sizeof(T) == 2 && Dh == 64 && Tn <= 256 && Tn >= 2 && nparts == 1 && attn_short_version() >= 2;
+    const bool once = short_path && dpk_once_enabled();      // the d(pk) pass that reads dS once (csrc/dpk_pass.h)
     if (causal && (short_path || Tp % (16 / (int)sizeof(T)) != 0 || !attn_zero_band_enabled())) {
         // key blocks in the future of a whole query wave are skipped by bwd_q: their entries must read as zero (the short key-major pass streams
         // every query chunk past its keys: the whole matrices)
@@ -1591,8 +1479,14 @@ static void launch_attn_bwd(const void *qkv, const void *pk, const float *bias_u
     }
     if (g_dpk_defer) {   // queued: both passes run in tsasr_relpos_dpk_flush (workspace, key_lens and dpk stay alive until then)
         DpkJob j{ds, qv, key_lens, part, dpk, B, Tn, Tp, H, Dh, causal, bg, isplit, i_span, G * isplit, cdiv(R, 64),
-                 sizeof(T) == 2 ? TSASR_BF16 : TSASR_F32, 0, cdiv(R, 64) * H * G * isplit, 0, std::min(1024, cdiv(R * H * 64, 256))};
+                 sizeof(T) == 2 ? TSASR_BF16 : TSASR_F32, once ? 1 : 0, 0, once ? H * G : cdiv(R, 64) * H * G * isplit, 0,
+                 std::min(1024, cdiv(R * H * 64, 256))};
         g_dpk_jobs.push_back(j);
+        return;
+    }
+    if (once) {       // (isplit == 1 here: fewer than 16 query blocks)
+        relpos_dpk_once_kernel<<<dim3(H, G), DPO_TH, 0, st>>>((const bf16_t *)ds, (const bf16_t *)qv, key_lens, part, B, Tn, Tp, H, causal, bg);
+        dpk_reduce_kernel<T><<<std::min(1024, cdiv(R * H * 64, 256)), 256, 0, st>>>(part, (T *)dpk, R, H, Dh, G);
         return;
     }
     relpos_dpk_kernel<T><<<dim3(cdiv(R, 64), H, G * isplit), 256, 0, st>>>(ds, qv, key_lens, part, B, Tn, Tp, H, Dh, causal, bg, isplit, i_span);
@@ -1747,20 +1641,20 @@ void tsasr_relpos_dpk_discard(void) { g_dpk_jobs.clear(); g_dpk_defer = 0; }
 void tsasr_relpos_attn_keepbits(void *bits) { g_attn_keepbits = bits; }
 size_t tsasr_relpos_attn_keepbits_bytes(int B, int T, int H) { return (T >= 2 && T <= 256) ? (size_t)B * H * T * 16 * sizeof(unsigned short) : 0; }
 
-/* Runs every queued d(pk) pass: ONE launch for the passes, one for the sums of their partials (per io dtype present). table_host: PINNED
+/* Runs every queued d(pk) pass: ONE launch for the passes, one for the sums of their partials (per io dtype and body present). table_host: PINNED
  * host memory, table_dev: device memory, both >= tsasr_relpos_dpk_table_bytes(tsasr_relpos_dpk_pending()); copied host -> device on `stream`
  * except while it is being captured (then the caller uploads table_host after the capture: the protocol of tsasr_wgrad_flush). */
 int tsasr_relpos_dpk_flush(void *table_host, void *table_dev, size_t table_bytes, void *stream) {
     if (g_dpk_jobs.empty()) return 0;
     hipStream_t st = (hipStream_t)stream;
-    std::stable_sort(g_dpk_jobs.begin(), g_dpk_jobs.end(), [](const DpkJob &a, const DpkJob &b) { return a.io_dtype < b.io_dtype; });
+    std::stable_sort(g_dpk_jobs.begin(), g_dpk_jobs.end(), [](const DpkJob &a, const DpkJob &b) { return a.io_dtype != b.io_dtype ? a.io_dtype < b.io_dtype : a.once > b.once; });
     const size_t need = g_dpk_jobs.size() * sizeof(DpkJob);
     TSASR_CHECK_ARG(table_host && table_dev && table_bytes >= need, "tsasr_relpos_dpk_flush: job table too small (%zu < %zu bytes)", table_bytes, need);
-    struct Group { int first, count, tiles, rtiles, dtype; };
+    struct Group { int first, count, tiles, rtiles, dtype, once; };
     std::vector<Group> groups;
     for (size_t i = 0; i < g_dpk_jobs.size(); ++i) {
         DpkJob &j = g_dpk_jobs[i];
-        if (groups.empty() || groups.back().dtype != j.io_dtype) groups.push_back(Group{(int)i, 0, 0, 0, j.io_dtype});
+        if (groups.empty() || groups.back().dtype != j.io_dtype || groups.back().once != j.once) groups.push_back(Group{(int)i, 0, 0, 0, j.io_dtype, j.once});
         Group &g = groups.back();
         j.tile0 = g.tiles; j.rtile0 = g.rtiles;
         g.tiles += j.ntiles; g.rtiles += j.rtiles; g.count += 1;
@@ -1778,7 +1672,8 @@ int tsasr_relpos_dpk_flush(void *table_host, void *table_dev, size_t table_bytes
     for (const Group &g : groups) {
         const DpkJob *tab = (const DpkJob *)table_dev + g.first;
         if (g.dtype == TSASR_BF16) {
-            relpos_dpk_group_kernel<bf16_t><<<g.tiles, 256, 0, st>>>(tab, g.count);
+            if (g.once) relpos_dpk_once_group_kernel<<<g.tiles, DPO_TH, 0, st>>>(tab, g.count);
+            else relpos_dpk_group_kernel<bf16_t><<<g.tiles, 256, 0, st>>>(tab, g.count);
             dpk_reduce_group_kernel<bf16_t><<<g.rtiles, 256, 0, st>>>(tab, g.count);
         } else {
             relpos_dpk_group_kernel<float><<<g.tiles, 256, 0, st>>>(tab, g.count);

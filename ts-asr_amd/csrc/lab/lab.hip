@@ -1,9 +1,11 @@
-// libtsasr_lab.so: lab equipment (include/tsasr_lab.h) - LDS / memory fills and a wall-clock stamp. Not linked into the product library.
+// libtsasr_lab.so: lab equipment (include/tsasr_lab.h) - LDS / memory fills, a wall-clock stamp and the d(pk) pass of the attention
+// backward on caller-supplied tensors. Not linked into the product library.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 
 #include "../../../include/tsasr_lab.h"
+#include "../dpk_pass.h"
 
 __global__ __launch_bounds__(256) void lab_fill_lds_kernel(unsigned pattern, int words, unsigned *sink) {
     extern __shared__ unsigned fill_lds[];
@@ -17,6 +19,20 @@ __global__ void lab_fill_words_kernel(unsigned *p, unsigned pattern, size_t n) {
 }
 
 __global__ void lab_stamp_kernel(unsigned long long *out) { *out = __builtin_amdgcn_s_memrealtime(); }
+
+// the two bodies of csrc/dpk_pass.h, launched as csrc/attention.hip launches them stand-alone
+__global__ __launch_bounds__(256) void lab_dpk_kernel(const bf16_t *__restrict__ ds, const bf16_t *__restrict__ qv, const int32_t *__restrict__ key_lens,
+                                                      float *__restrict__ part, int Bn, int Tn, int Tp, int H, int causal, int bgroup) {
+    dpk_body<bf16_t>(ds, qv, key_lens, part, Bn, Tn, Tp, H, 64, causal, bgroup, 1, Tp, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+__global__ __launch_bounds__(DPO_TH, 4) void lab_dpk_once_kernel(const bf16_t *__restrict__ ds, const bf16_t *__restrict__ qv,
+                                                                 const int32_t *__restrict__ key_lens, float *__restrict__ part, int Bn, int Tn, int Tp,
+                                                                 int H, int causal, int bgroup) {
+    dpk_once_body(ds, qv, key_lens, part, Bn, Tn, Tp, H, causal, bgroup, blockIdx.x, blockIdx.y);
+}
+__global__ __launch_bounds__(256) void lab_dpk_reduce_kernel(const float *__restrict__ part, bf16_t *__restrict__ dpk, int R, int H, int G) {
+    dpk_reduce_body<bf16_t>(part, dpk, R, H, 64, G, blockIdx.x, gridDim.x);
+}
 
 static int launched(void) { return hipGetLastError() == hipSuccess ? 0 : -2; }
 
@@ -42,6 +58,23 @@ int tsasr_lab_fill(void *p, unsigned pattern, size_t nwords, void *stream) {
 int tsasr_lab_stamp(void *out, void *stream) {
     if (!out || ((uintptr_t)out & 7)) return -1;
     lab_stamp_kernel<<<1, 1, 0, (hipStream_t)stream>>>((unsigned long long *)out);
+    return launched();
+}
+
+size_t tsasr_lab_dpk_part_bytes(int B, int T, int H) {
+    if (B < 1 || H < 1 || !dpk_once_shape(T)) return 0;
+    return (size_t)cdiv(B, dpk_bgroup(B, T)) * (2 * T - 1) * H * 64 * sizeof(float);
+}
+
+int tsasr_lab_dpk(int body, const void *ds, const void *qv, const int *key_lens, void *part, void *dpk, int B, int T, int H, int causal, void *stream) {
+    if (!ds || !qv || !part || !dpk || B < 1 || H < 1 || !dpk_once_shape(T) || causal < 0 || (body != 0 && body != 1)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int Tp = cdiv(T, 64) * 64, R = 2 * T - 1, bg = dpk_bgroup(B, T), G = cdiv(B, bg);
+    if (body == 1)
+        lab_dpk_once_kernel<<<dim3(H, G), DPO_TH, 0, st>>>((const bf16_t *)ds, (const bf16_t *)qv, key_lens, (float *)part, B, T, Tp, H, causal, bg);
+    else
+        lab_dpk_kernel<<<dim3(cdiv(R, 64), H, G), 256, 0, st>>>((const bf16_t *)ds, (const bf16_t *)qv, key_lens, (float *)part, B, T, Tp, H, causal, bg);
+    lab_dpk_reduce_kernel<<<std::min(1024, cdiv(R * H * 64, 256)), 256, 0, st>>>((const float *)part, (bf16_t *)dpk, R, H, G);
     return launched();
 }
 
