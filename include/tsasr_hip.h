@@ -497,6 +497,26 @@ int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih
                              double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:
+ * 124-334, Kaldi's compute-wer order: the substitution / match only if strictly cheaper than both others, else the deletion if strictly
+ * cheaper than the insertion, else the insertion; row 0 insertions, column 0 deletions; the walk back from (n, m) follows the cell's
+ * operation). One launch, one workgroup per pair (csrc/editdist.hip). Ragged int32 input: pair k is ref_sym[ref_off[k] .. ref_off[k+1])
+ * against hyp_sym[hyp_off[k] .. hyp_off[k+1]), lengths n, m >= 0; max_ref / max_hyp = the longest of each side (both <= 16384; max_ref ints of dynamic LDS), cells = sum
+ * over pairs of (n + 1) * (m + 1). counts int32 [N,4] = edits, insertions, deletions, substitutions; the alignment of pair k in forward
+ * order at offset ref_off[k] + hyp_off[k] of align_op uint8 ('=', 'S', 'D', 'I'), align_i, align_j int32 (index into the pair's reference
+ * / hypothesis, -1 = aligned to nothing), align_len int32 [N] entries of it (<= n + m; the buffers hold sum(n + m) entries). totals
+ * int64 [8] is ADDED to with device-scope atomics: edits, insertions, deletions, substitutions, sum of ref_count[k] (int32 [N]: the
+ * reference tokens pair k counts for), pairs, pairs with >= 1 edit, spare. workspace >= tsasr_edit_distance_workspace_bytes(N, cells)
+ * = 16 N + cells / 2 + 16 bytes (an upper bound: 2 bits per cell are used, and nothing for a pair whose table fits in 60 KiB), 16-byte
+ * aligned; results do not depend on its contents. All pointers are device memory.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_edit_distance_workspace_bytes(int N, long long cells);
+int tsasr_edit_distance(const int32_t *ref_sym, const int32_t *ref_off, const int32_t *hyp_sym, const int32_t *hyp_off,
+                        const int32_t *ref_count, int N, int max_ref, int max_hyp, long long cells, int32_t *counts, uint8_t *align_op,
+                        int32_t *align_i, int32_t *align_j, int32_t *align_len, long long *totals, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chunk-by-chunk inference of the causal encoder (csrc/stream.hip); eval only, no backward.
  * Relative-position attention of a chunk of C query frames at absolute offset t0: qkv [B,C,H,3*Dh] (RelPosMHAXL's per-head Q|K|V);
  * k_cache / v_cache [B,H,Tmax,Dh] (io_dtype) hold frames 0 .. t0-1 and receive the chunk's K, V at rows t0 .. t0+C-1 (t0 + C <= Tmax);

@@ -12,6 +12,7 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
   --synthetic N    : N synthetic LibriSpeechMix-shaped batches per epoch instead of manifests (no dataset on the GPU box); shapes from
         --syn_batch / --syn_seconds / --syn_enroll_seconds / --syn_tokens; lengths are length-bucketed like `sorting: ascending`.
   --hip_graph True : capture the step into hipGraphs (one per batch shape).
+  --wer_file PATH  : the TEST stage writes the reference's WER report there (summary lines + one alignment per utterance).
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
 import importlib
 import os
@@ -29,7 +30,7 @@ batch_mod = importlib.import_module(PKG + ".batch")
 tsasr = importlib.import_module(PKG + ".recipes.tsasr")
 
 EXTRA = {"synthetic": 0, "syn_batch": 8, "syn_seconds": 4.0, "syn_enroll_seconds": 2.0, "syn_tokens": 24, "hip_graph": False,
-         "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None}
+         "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None}
 
 
 def synthetic_loader(n_batches, hparams, opts, seed, device):
@@ -55,6 +56,8 @@ def main(argv=None):
     opts = {k: overrides.pop(k, v) for k, v in EXTRA.items()}
     with open(hparams_file) as f:
         hparams = hp_mod.load_hyperpyyaml(f, overrides)
+    if opts["wer_file"]:
+        hparams["wer_file"] = str(opts["wer_file"])
     dp.ddp_init_group(run_opts)                                           # one process per GPU (SB/utils/distributed.py:123-201)
     brain = tsasr.TSASR(hparams["modules"], hparams["opt_class"], hparams, run_opts)
     if opts["hip_graph"]:
@@ -76,6 +79,9 @@ def main(argv=None):
     if test is not None:
         result["test_loss"] = brain.evaluate(test)
         result["test_hyps"] = getattr(brain, "last_hyps", None)
+        result["test_stats"] = getattr(brain, "test_stats", None)
+    if valid is not None:
+        result["valid_stats"] = getattr(brain, "valid_stats", None)
     if rank == 0:
         print({k: (v if k != "test_hyps" else (v[:2] if v else v)) for k, v in result.items()})
     if dp.is_initialized():

@@ -5,7 +5,7 @@ tags: ``!new:``, ``!name:``, ``!apply:``, ``!ref`` (with ``<key>`` interpolation
 ``<vocab_size> - 1``) and ``!PLACEHOLDER``, plus tuple-like strings ``(128, 128)``. This reader supports
 exactly those. Class paths that point into the reference's Python packages are re-pointed to their MI355X
 mirrors through ``ALIASES`` - so ``!new:speechbrain.lobes.features.Fbank`` builds ``ts-asr_amd.nnet.Fbank``.
-Paths with no mirror on the hot path (checkpointing, WER statistics, ...) become ``Unavailable``
+Paths with no mirror on the hot path (checkpointing, loggers, ...) become ``Unavailable``
 placeholders that raise only when used (out of scope).
 """
 import ast
@@ -33,6 +33,7 @@ ALIASES = {
     "speechbrain.nnet.schedulers.NoamScheduler": _PKG + ".core.NoamScheduler",
     "speechbrain.utils.epoch_loop.EpochCounter": _PKG + ".core.EpochCounter",
     "speechbrain.decoders.transducer.TransducerBeamSearcher": _PKG + ".decoders.TransducerBeamSearcher",
+    "speechbrain.utils.metric_stats.ErrorRateStats": _PKG + ".metrics.ErrorRateStats",
 }
 
 

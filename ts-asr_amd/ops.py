@@ -36,6 +36,7 @@ STATUS = {
                                                   "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
     "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search / beam_search_stream, one launch per batch or chunk; "
                                                          "the host loop only for other predictor shapes and utterances past cap)",
+    "WER / CER statistics (VALID / TEST stages)": "HIP (editdist.hip: edit_distance, one launch per searched batch; metrics.ErrorRateStats)",
 }
 
 STRICT_HIP = os.environ.get("TSASR_STRICT_HIP", "0") == "1"
@@ -2414,3 +2415,49 @@ def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slop
 
     with prof.region("beam_search_stream"):
         return _beam_read(run, B, int(nbest), 256, enc.device)
+
+
+EditResult = __import__("collections").namedtuple("EditResult", ["counts", "align_op", "align_i", "align_j", "align_len", "totals"])
+
+
+def edit_distance_workspace_bytes(N, cells):
+    """Bytes of the workspace of edit_distance for N pairs, cells = sum of (n + 1) * (m + 1) (include/tsasr_hip.h: an upper bound)."""
+    N, cells = int(N), int(cells)
+    return 16 * N + cells // 2 + 16 if N > 0 and cells > 0 else 0
+
+
+def edit_distance(ref_sym, ref_off, hyp_sym, hyp_off, ref_count, max_ref, max_hyp, cells, totals=None, workspace=None):
+    """Edit distance of N ragged pairs of int32 symbol sequences with the reference's path choice (csrc/editdist.hip), one launch on the
+    current stream, no synchronisation. ref_sym / hyp_sym int32 device vectors, ref_off / hyp_off int32 [N+1], ref_count int32 [N];
+    max_ref / max_hyp / cells = what the host knows of the lengths (longest reference, longest hypothesis, sum of (n + 1) * (m + 1)).
+    ``totals`` int64 [8] is added to (a new zeroed one when None). Returns EditResult(counts [N,4], align_op uint8, align_i, align_j
+    [len(ref_sym) + len(hyp_sym)], align_len [N], totals), all on the device."""
+    C.require_gpu(ref_sym, ref_off, hyp_sym, hyp_off, ref_count, totals, workspace)
+    for name, t in (("ref_sym", ref_sym), ("ref_off", ref_off), ("hyp_sym", hyp_sym), ("hyp_off", hyp_off), ("ref_count", ref_count)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"edit_distance: {name} must be a contiguous int32 vector")
+    N = ref_count.numel()
+    if N < 1 or ref_off.numel() != N + 1 or hyp_off.numel() != N + 1:
+        raise ValueError(f"edit_distance: {N} pairs need offsets of {N + 1} entries")
+    dev = ref_off.device
+    if totals is None:
+        totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    elif totals.dtype != torch.int64 or totals.numel() != 8 or not totals.is_contiguous():
+        raise ValueError("edit_distance: totals must be a contiguous int64 [8]")
+    need = edit_distance_workspace_bytes(N, cells)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise ValueError(f"edit_distance: workspace must be uint8 with at least {need} bytes")
+    slots = ref_sym.numel() + hyp_sym.numel()
+    counts = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    align_len = torch.empty(N, dtype=torch.int32, device=dev)
+    align_op = torch.empty(max(slots, 1), dtype=torch.uint8, device=dev)
+    align_i = torch.empty(max(slots, 1), dtype=torch.int32, device=dev)
+    align_j = torch.empty(max(slots, 1), dtype=torch.int32, device=dev)
+    with prof.region("edit_distance"):
+        C.check(C.lib().tsasr_edit_distance(C.ptr(ref_sym), C.ptr(ref_off), C.ptr(hyp_sym), C.ptr(hyp_off), C.ptr(ref_count), N, int(max_ref),
+                                            int(max_hyp), int(cells), C.ptr(counts), C.ptr(align_op), C.ptr(align_i), C.ptr(align_j),
+                                            C.ptr(align_len), C.ptr(totals), C.ptr(workspace), workspace.numel(), C.stream_ptr()),
+                "tsasr_edit_distance")
+    return EditResult(counts, align_op[:slots], align_i[:slots], align_j[:slots], align_len, totals)

@@ -4,14 +4,16 @@ Mirrors train_librispeechmix_scratch.py:33-195 (and the ``pretrained`` / ``none`
 the speaker branch: train_librispeechmix_pretrained.py:45-63, train_librispeechmix_none.py): same module names in
 ``self.modules``, same call order, same return values (``compute_forward -> (logits [B,T',U+1,V], hyps or None)``,
 ``compute_objectives -> 0-dim loss with autograd``). Differences: joiner + head run as ONE fused HIP kernel
-(the [B,T',U+1,J] joint tensor is never built), lengths stay on the device, plotting/WER bookkeeping is left to the
-caller (out of scope).
+(the [B,T',U+1,J] joint tensor is never built), lengths stay on the device, WER / CER are scored on the device
+(metrics.py); plotting, logging and checkpoint selection are left to the caller (out of scope).
 """
 import os
 
 import torch
 
 from .. import core, prof, rnnt
+from ..hparams import Unavailable
+from ..metrics import merge_across_ranks, undo_padding
 from ..nnet import abs_lengths_round
 
 Stage = core.Stage
@@ -227,8 +229,70 @@ class TSASR(core.Brain):
         loss = self.hparams.transducer_loss(logits, tokens, mixed_lens, tokens_lens)
         prof.stamp("loss forward done [main]")
         if hyps is not None:
-            self.last_hyps = hyps  # the reference feeds them to its WER/CER statistics (out of scope here)
+            self.last_hyps = hyps
+            self._score(hyps, batch)
         return loss
+
+    # ---- WER / CER statistics (train_librispeechmix_scratch.py:162-188, 197-262), scored on the device by metrics.ErrorRateStats ----
+    def _metric(self, key):
+        make = getattr(self.hparams, key, None)
+        return make() if callable(make) and not isinstance(make, Unavailable) else None
+
+    def _score(self, hyps, batch):
+        """Appends a searched batch to the stage's statistics: launches only, nothing is read back before the stage ends. With a
+        tokenizer (the caller's, called as the reference calls its SentencePiece wrapper) words against batch.target_words into the
+        CER and WER objects; without one the hypothesis token ids against batch.tokens cut to their lengths, into one token-level object."""
+        wer, cer = getattr(self, "wer_metric", None), getattr(self, "cer_metric", None)
+        tokenizer = getattr(self, "tokenizer", None)
+        if wer is None and (cer is None or tokenizer is None):
+            return
+        ids = getattr(batch, "id", None)
+        if ids is None:      # a hand-made batch without utterance ids: number them through the stage
+            ids = [f"utt{len((wer or cer).ids) + k}" for k in range(len(hyps))]
+        if tokenizer is not None:
+            words = tokenizer(hyps, task="decode_from_list")
+            for m in (cer, wer):
+                if m is not None:
+                    m.append(ids, words, batch.target_words)
+        else:
+            tokens, rel = batch.tokens
+            wer.append_ids(ids, hyps, undo_padding(tokens.cpu(), rel.cpu()))
+
+    def on_stage_start(self, stage, epoch=None):
+        super().on_stage_start(stage, epoch)
+        if stage != Stage.TRAIN:
+            self.cer_metric, self.wer_metric = self._metric("cer_computer"), self._metric("wer_computer")
+
+    def on_stage_end(self, stage, stage_loss, epoch=None):
+        super().on_stage_end(stage, stage_loss, epoch)
+        hp = self.hparams
+        stats = {"loss": stage_loss}
+        if stage == Stage.TRAIN:
+            self.train_stats = stats
+            return
+        wer, cer = getattr(self, "wer_metric", None), getattr(self, "cer_metric", None)
+        current = hp.epoch_counter.current if hasattr(hp, "epoch_counter") else 0
+        searched = wer is not None and (stage == Stage.TEST or current % getattr(hp, "valid_search_freq", 1) == 0)
+        if searched and self.distributed:      # every rank takes part, also one that saw no batch
+            for m in (cer, wer):
+                if m is not None:
+                    merge_across_ranks(m)
+        searched = searched and (len(wer.ids) > 0 or len(wer.scores) > 0)      # (no searcher in the YAML: nothing was appended)
+        if searched:
+            if getattr(self, "tokenizer", None) is not None:
+                if cer is not None:
+                    stats["CER"] = cer.summarize("error_rate")
+                stats["WER"] = wer.summarize("error_rate")
+            else:
+                stats["TER"] = wer.summarize("error_rate")
+        # (the reference logs through hparams.train_logger and keeps checkpoints by WER here: both are Unavailable, the caller's)
+        if stage == Stage.VALID:
+            self.valid_stats = stats
+        else:
+            self.test_stats = stats
+            if searched and self.rank == 0 and getattr(hp, "wer_file", None):
+                with open(hp.wer_file, "w") as w:
+                    wer.write_stats(w)
 
     def on_fit_batch_end(self, batch, outputs, loss, should_step):
         if getattr(self.hparams, "enable_scheduler", False) and should_step:
