@@ -395,9 +395,12 @@ int tsasr_add_layernorm2_bwd(const void *dz, const void *dy, const void *dout, c
                              float alpha, float p, unsigned long long seed, const unsigned long long *seed_dev, const int32_t *valid_lens,
                              int Trows, int io_dtype, void *workspace, size_t workspace_bytes, void *stream);
 
-/* Whole-sequence LSTM recurrences (all U steps of tsasr_lstm_step_fwd / _bwd). bf16, H in {256, 512}, B <= 256: one persistent
- * launch per direction (workgroups exchange h_t / dG_t through write-through stores and an arrival counter); otherwise a loop of
- * the per-step kernels. Replaces the time loop inside torch.nn.LSTM (speechbrain/nnet/RNN.py:244-278). */
+/* Whole-sequence LSTM recurrences (all U steps of tsasr_lstm_step_fwd / _bwd). One persistent launch per direction (workgroups
+ * exchange h_t / dG_t through write-through stores and an arrival counter) when io_dtype is bf16, H is 256 or 512, and the grid fits
+ * the device: G = ceil(B / BR) exchange groups of BR = 8 (B <= 8) or 16 rows, G <= 16 (so B <= 256) and G * H / 32 workgroups <= the
+ * compute units THIS device exposes (tsasr_lstm_seq_persistent tells); B = 1 with H = 512 runs the single-utterance kernels unless
+ * TSASR_LSTM_SEQ1=0. Otherwise (any other H % 16 == 0, fp32 io, B > 256, too few CUs) a loop of the per-step kernels.
+ * Replaces the time loop inside torch.nn.LSTM (speechbrain/nnet/RNN.py:244-278). */
 /* Input projection of the predictor when its Embedding is one-hot and frozen (speechbrain/nnet/embedding.py:76-95 consider_as_one_hot,
  * train_librispeechmix_scratch.py:117-119 `embedding` -> `decoder`): gates [B,U,H,4] fp32 = b_ih + b_hh + the token's column of w_ih
  * [4H, I] (fp32), i.e. F.embedding + x . W_ih^T + biases of torch.nn.LSTM without the gather, the casts and the GEMM. tokens int64 [B,U];
