@@ -91,6 +91,22 @@ int tsasr_rnnt_loss_bwd(const float *logits, const int32_t *targets, int ldt, co
  * one loss must run under the same plan. Every plan returns the same bits (tests/test_rnnt_gpu.py). */
 void tsasr_rnnt_lattice_plan(int skew, int waves, int mc);
 
+/* ------------------------------------------------------------------------------------------
+ * Forced alignment on the same lattice (no reference counterpart): the best path instead of the sum over all paths.
+ *   delta(0,0) = 0,  delta(t,u) = max(delta(t-1,u) + lp_blank(t-1,u), delta(t,u-1) + lp_label(t,u-1)),  fp32, lp_* as in the loss;
+ *   scores[b] = delta(T_b-1, U_b) + lp_blank(T_b-1, U_b)  = log-probability of the best path  (<= -costs[b]);
+ *   frames[b, u] = frame at which label u of that path is emitted (non-decreasing in u) for u < U_b, -1 for U_b <= u < U1-1.
+ * Equal candidates (in the kernel's own fp32 arithmetic): the blank predecessor (t-1) wins, i.e. among equal paths the one whose
+ * (f_{U-1}, ..., f_0) is lexicographically smallest; identical logits in every cell give frames == 0.
+ * logits / targets / ldt / tlen / ulen / ldl / blank as tsasr_rnnt_loss_fwd (T_b = clamp(tlen[b], 1, T), U_b = clamp(ulen[b], 0, U1-1);
+ * V <= 32 fast path and general V). frames: [B, ldf] int32, ldf >= max(U1-1, 1). One backpointer bit per cell in `workspace`
+ * (plus three fp32 planes); no allocation, no host sync, nothing shared between calls: re-entrant per stream, capturable.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_rnnt_align_workspace_bytes(int B, int T, int U1);
+int tsasr_rnnt_align(const float *logits, const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen,
+                     int32_t *frames /* [B, ldf] */, int ldf, float *scores /* [B] */,
+                     int B, int T, int U1, int V, int ldl, int blank, void *workspace, size_t workspace_bytes, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Row kernels of the Conformer block (HBM-bound, one pass each, fp32 math, deterministic column reductions).

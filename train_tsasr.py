@@ -13,6 +13,9 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
         --syn_batch / --syn_seconds / --syn_enroll_seconds / --syn_tokens; lengths are length-bucketed like `sorting: ascending`.
   --hip_graph True : capture the step into hipGraphs (one per batch shape).
   --wer_file PATH  : the TEST stage writes the reference's WER report there (summary lines + one alignment per utterance).
+  --align_file PATH : after the TEST stage the test batches are force-aligned to their reference transcripts (TSASR.align_batch: the best
+        path through the RNN-T lattice) and a CTM is written there, "<utt> 1 <start> <dur> <word>" per word; without a tokenizer one
+        line per token with the token id as the word. Works with --synthetic N.
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
 import importlib
 import os
@@ -30,7 +33,8 @@ batch_mod = importlib.import_module(PKG + ".batch")
 tsasr = importlib.import_module(PKG + ".recipes.tsasr")
 
 EXTRA = {"synthetic": 0, "syn_batch": 8, "syn_seconds": 4.0, "syn_enroll_seconds": 2.0, "syn_tokens": 24, "hip_graph": False,
-         "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None}
+         "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None,
+         "align_file": None}
 
 
 def synthetic_loader(n_batches, hparams, opts, seed, device):
@@ -49,6 +53,24 @@ def synthetic_loader(n_batches, hparams, opts, seed, device):
                                       seed=seed + i, ragged=True, feats=feats, enroll_emb_dim=emb)
         out.append(b.to(device))
     return out
+
+
+def write_alignments(brain, batches, hparams, path):
+    """Force-aligns every batch to its reference transcript and writes one CTM; returns the number of lines. One device-to-host copy per batch."""
+    align = importlib.import_module(PKG + ".align")
+    fs = align.frame_seconds(hparams)
+    pieces = getattr(getattr(brain, "tokenizer", None), "pieces", None)      # the tokenizer's piece texts by id (metrics.CharTokenizer has them)
+    ids, spans = [], []
+    for n, batch in enumerate(batches):
+        frames, _ = align.fetch(*brain.align_batch(batch))
+        refs = batch.tokens.data.tolist()      # whole rows: frames are -1 beyond an utterance's tokens, the spans stop there
+        utts = getattr(batch, "id", None) or [f"utt{len(ids) + k}" for k in range(len(refs))]
+        if len(set(utts) & set(ids)):      # synthetic batches reuse their ids: keep the CTM's utterance names apart
+            utts = [f"{u}-{n}" for u in utts]
+        for utt, fr, ref in zip(utts, frames, refs):
+            ids.append(utt)
+            spans.append(align.word_spans(fr, ref, pieces, fs) if pieces is not None else align.token_spans(fr, ref, fs))
+    return align.write_ctm(path, ids, spans)
 
 
 def main(argv=None):
@@ -80,6 +102,8 @@ def main(argv=None):
         result["test_loss"] = brain.evaluate(test)
         result["test_hyps"] = getattr(brain, "last_hyps", None)
         result["test_stats"] = getattr(brain, "test_stats", None)
+        if opts["align_file"] and rank == 0:
+            result["align_lines"] = write_alignments(brain, test, hparams, str(opts["align_file"]))
     if valid is not None:
         result["valid_stats"] = getattr(brain, "valid_stats", None)
     if rank == 0:

@@ -46,6 +46,8 @@ _PROTOS = {
                                                c_ull, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "tsasr_rnnt_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
     "tsasr_rnnt_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "tsasr_rnnt_align_workspace_bytes": (c_size_t, [c_int] * 3),
+    "tsasr_rnnt_align": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
     "tsasr_layernorm_fwd": (c_int, [c_void_p] * 6 + [c_ll, c_int, c_float, c_float, c_int, c_void_p]),
     "tsasr_layernorm_bwd_workspace_bytes": (c_size_t, [c_ll, c_int]),
     "tsasr_layernorm_bwd": (c_int, [c_void_p] * 9 + [c_ll, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),

@@ -1310,6 +1310,175 @@ static int launch_alphabeta(RnntWs w, const int32_t *tlen, const int32_t *ulen, 
 }
 
 // ============================================================================================
+// forced alignment: the best path through the same lattice (Viterbi instead of log-sum-exp)
+// ============================================================================================
+// rnnt_lp fills the blank / label planes of an alignment workspace of its own (rnnt_lp's lse and lpe_out go to one plane nobody reads),
+// then ONE workgroup per utterance walks the lattice as rnnt_alphabeta_kernel's alpha direction does - thread g owns KT columns and is
+// skewed by g frames, the neighbour's boundary value moves by a DPP wave shift (LDS word + barrier across waves), operands are requested
+// PF steps ahead, the guarded form is straight-line code - with   delta = max(delta(t-1,u) + lp_blank, delta(t,u-1) + lp_label)   in
+// place of logaddexp: three dependent operations per column. delta lives in registers only. What a cell leaves behind is ONE bit (1: the
+// label predecessor won; equal candidates: blank): a thread gathers the bits of 32 consecutive frames of a column in a register and stores
+// the growing word every step, unconditionally (words [b][t / 32][u]: the lanes of a step, one frame apart, touch 2 - 3 rows of it).
+// The backtrace is scalar work of wave 0: it fetches the words of 64 columns x 128 frames around its cell in one go and walks inside that
+// window with readlane: one iteration per label and per 32-frame word crossed; a path crosses at most T / 128 + U / 64 + 1 windows.
+// Plan: U1 <= 256: one wave, frame-major planes; longer targets: 4 / 8 waves on skewed planes (rnnt_plan's reasons). A lattice is never
+// split over workgroups here: nothing waits on another workgroup.
+static void align_plan(int U1, int *KT, int *NW) {
+    const int K = rnnt_K(U1);
+    int nw = 1;
+    if (K >= 8) {
+        nw = std::min(8, K / 2);
+        while (nw & (nw - 1)) nw &= nw - 1;
+    }
+    *KT = K / nw;
+    *NW = nw;
+}
+static size_t align_plane_floats(int B, int T, int U1) {
+    int kt, nw;
+    align_plan(U1, &kt, &nw);
+    return (size_t)B * (T + (nw > 1 ? 64 * nw - 1 : 0)) * 64 * rnnt_K(U1);
+}
+static size_t align_bits_words(int B, int T, int U1) { return (size_t)B * cdiv(T, 32) * 64 * rnnt_K(U1); }
+
+static RnntWs align_carve(void *ws, int B, int T, int U1, unsigned **bits) {
+    RnntWs w = {};
+    w.K = rnnt_K(U1);
+    w.U1P = 64 * w.K;
+    align_plan(U1, &w.KT, &w.NW);
+    w.NC = 1;
+    w.R = T + (w.NW > 1 ? 64 * w.NW - 1 : 0);
+    w.sh = 31;
+    if (w.NW > 1) { w.sh = 0; while ((1 << w.sh) < w.KT) ++w.sh; }
+    const size_t n = align_plane_floats(B, T, U1);
+    float *p = reinterpret_cast<float *>(ws);
+    w.lpb = p; w.lpe_in = p + n; w.lpe_out = w.lse = p + 2 * n;      // (lpe_out / lse: written by rnnt_lp, same cell by the same lane; not read)
+    *bits = reinterpret_cast<unsigned *>(p + 3 * n);
+    return w;
+}
+
+template <int K, int NW, bool SKEW>
+__global__ __launch_bounds__(64 * NW) void rnnt_viterbi_kernel(RnntWs w, unsigned *bits, const int32_t *__restrict__ tlen,
+                                                               const int32_t *__restrict__ ulen, int32_t *__restrict__ frames, int ldf,
+                                                               float *__restrict__ scores, int Tn, int U1) {
+    constexpr int G = 64 * NW;
+    __shared__ float edge_lds[2][NW > 1 ? NW : 1];
+    const int b = blockIdx.x, g = threadIdx.x, l = g & 63, wave = g >> 6;
+    const int U1P = w.U1P, T32 = (Tn + 31) >> 5;
+    const int Tb = min(max(tlen[b], 1), Tn), Ub = min(max(ulen[b], 0), U1 - 1);
+    for (int u = Ub + g; u < U1 - 1; u += G) frames[(size_t)b * ldf + u] = -1;
+    const size_t base = (size_t)b * w.R * U1P + (size_t)K * g;
+    unsigned *bcol = bits + (size_t)b * T32 * U1P + (size_t)K * g;
+    const int nsteps = Tb + G - 1;
+    const int rmax = w.R - 1;     // SKEW: frame t of this thread's columns is row t + g: a step touches ONE row for the whole workgroup
+    float prev[K], cur[K];
+    unsigned acc[K];              // backpointer bits of the 32-frame word this thread is in, per column
+#pragma unroll
+    for (int i = 0; i < K; ++i) { prev[i] = cur[i] = NEG_INF; acc[i] = 0u; }
+    float edge = NEG_INF;
+    constexpr int PF = 16;   // steps the operand requests run ahead (8: 59 us, 16: 57 us at B = 32, T' = 250, U1 = 121; 3 memory operations per step, vmcnt counts to 63)
+    float qb[PF][K], qe[PF][K];
+#pragma unroll
+    for (int d = 0; d < PF; ++d)
+#pragma unroll
+        for (int i = 0; i < K; ++i) qb[d][i] = qe[d][i] = 0.f;
+    auto fetch = [&](int ss, float (&vb)[K], float (&ve)[K]) {       // ss >= 0
+        const int t = min(max(ss - g, 0), Tb - 1);
+        const float *pb = w.lpb + base + (size_t)(SKEW ? min(max(ss - 1, 0), rmax) : (t > 0 ? t - 1 : 0)) * U1P;
+        const float *pe = w.lpe_in + base + (size_t)(SKEW ? min(ss, rmax) : t) * U1P;
+#pragma unroll
+        for (int i = 0; i < K; ++i) { vb[i] = pb[i]; ve[i] = pe[i]; }
+    };
+    // a chunk of PF steps, straight-line in both forms (rnnt_alphabeta_kernel): outside its frames a thread computes on a clamped frame, keeps
+    // its values by select and stores its unchanged word again (before its first frame: zero into word 0, which it overwrites in order)
+    auto chunk = [&](int s0, auto guard_tag) {
+        constexpr bool GUARD = decltype(guard_tag)::value;
+#pragma unroll
+        for (int d = 0; d < PF; ++d) {
+            const int s = s0 + d;
+            const int t = s - g;
+            const bool valid = !GUARD || (t >= 0 && t < Tb);
+            const int tc = GUARD ? min(max(t, 0), Tb - 1) : t;
+            float left = __builtin_amdgcn_update_dpp(NEG_INF, edge, 0x138, 0xf, 0xf, false);  // wave_shr:1
+            if (NW > 1 && l == 0 && wave > 0) left = edge_lds[(s + 1) & 1][wave - 1];          // written in step s-1
+            // the lattice's edges enter as -inf operands chosen by select (cells outside the lattice hold whatever the workspace held)
+            float ne[K], qm[K], nv[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const int u = K * g + i;
+                ne[i] = (t > 0) ? prev[i] + qb[d][i] : (u == 0 ? 0.f : NEG_INF);
+                qm[i] = (u > 0) ? qe[d][i] : NEG_INF;
+                if (u > Ub) ne[i] = qm[i] = NEG_INF;
+            }
+            const int sh = tc & 31;
+            unsigned *pw = bcol + (size_t)(tc >> 5) * U1P;
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const float em = ((i == 0) ? left : nv[i > 0 ? i - 1 : 0]) + qm[i];
+                const bool lab = em > ne[i];                       // equal: the blank predecessor wins
+                nv[i] = lab ? em : ne[i];
+                const unsigned a = (sh ? acc[i] : 0u) | ((lab ? 1u : 0u) << sh);
+                acc[i] = valid ? a : acc[i];
+                cur[i] = valid ? nv[i] : cur[i];
+                prev[i] = cur[i];
+                pw[i] = acc[i];
+            }
+            edge = cur[K - 1];
+            if (NW > 1 && l == 63) edge_lds[s & 1][wave] = edge;
+            fetch(s + PF, qb[d], qe[d]);
+            if (NW > 1) ab_step_barrier();
+        }
+    };
+    int s0 = -PF;
+    for (; s0 < nsteps && !(s0 >= G - 1 && s0 + PF < Tb); s0 += PF) chunk(s0, std::true_type{});
+    for (; s0 < nsteps && s0 + PF < Tb; s0 += PF) chunk(s0, std::false_type{});
+    for (; s0 < nsteps; s0 += PF) chunk(s0, std::true_type{});
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        if (K * g + i == Ub) scores[b] = cur[i] + w.lpb[base + (size_t)(Tb - 1 + (SKEW ? g : 0)) * U1P + i];
+    // backtrace: by wave 0 behind the workgroup barrier. The words were written by this workgroup's own waves, which share the CU's L1:
+    // workgroup scope is enough (a device-scope fence here wrote the L2's dirty lines back - the planes rnnt_lp has just left there)
+    __syncthreads();
+    if (wave != 0) return;
+    const unsigned *bb = bits + (size_t)b * T32 * U1P;
+    int t = Tb - 1, u = Ub;                   // wave-uniform; at u == 0 only blanks are left: nothing to record
+    int32_t *fr = frames + (size_t)b * ldf;
+    constexpr int NR = 4;                     // words (32 frames each) per lane and window: the NR requests of a window travel together
+    while (u > 0) {
+        const int tw = t >> 5, ub = u & ~63;
+        unsigned win[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            win[r] = __hip_atomic_load(bb + (size_t)max(tw - r, 0) * U1P + ub + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for (;;) {
+            // column u's word of frames 32 * (t >> 5) ..; the blanks below frame t are skipped in one step: the highest set bit at or below t
+            // is the frame at which label u-1 is emitted (frame 0 counts as set: nothing else leads to (0, 0))
+            const int tq = t >> 5, rr = tw - tq;
+            unsigned wd = __builtin_amdgcn_readlane(win[0], u - ub);
+#pragma unroll
+            for (int r = 1; r < NR; ++r) {
+                const unsigned x = __builtin_amdgcn_readlane(win[r], u - ub);
+                wd = rr == r ? x : wd;
+            }
+            const unsigned m = (wd & (0xffffffffu >> (31 - (t & 31)))) | (tq == 0 ? 1u : 0u);
+            if (m == 0u) {
+                t = 32 * tq - 1;              // tq > 0
+            } else {
+                t = 32 * tq + 31 - __builtin_clz(m);
+                if (l == 0) fr[u - 1] = t;
+                --u;
+            }
+            if (u == 0 || (u & ~63) != ub || (t >> 5) <= tw - NR) break;
+        }
+    }
+}
+
+template <int K, int NW>
+static void launch_viterbi(RnntWs w, unsigned *bits, const int32_t *tlen, const int32_t *ulen, int32_t *frames, int ldf, float *scores,
+                           int B, int T, int U1, hipStream_t st) {
+    rnnt_viterbi_kernel<K, NW, (NW > 1)><<<B, 64 * NW, 0, st>>>(w, bits, tlen, ulen, frames, ldf, scores, T, U1);
+}
+
+// ============================================================================================
 // C-ABI
 // ============================================================================================
 extern "C" {
@@ -1494,6 +1663,37 @@ int tsasr_rnnt_loss_bwd(const float *logits, const int32_t *targets, int ldt, co
     const long long rows = (long long)B * T * U1;
     rnnt_grad_kernel<<<(unsigned)((rows + 31) / 32), 256, 0, (hipStream_t)stream>>>(logits, targets, ldt, tlen, ulen, gscale, dlogits, w, B, T, U1, V, ldl, blank);
     TSASR_CHECK_LAUNCH("tsasr_rnnt_loss_bwd");
+    return 0;
+}
+
+size_t tsasr_rnnt_align_workspace_bytes(int B, int T, int U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return 0;
+    return align_up((3 * align_plane_floats(B, T, U1) + align_bits_words(B, T, U1)) * sizeof(float), 256);
+}
+
+int tsasr_rnnt_align(const float *logits, const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen, int32_t *frames,
+                     int ldf, float *scores, int B, int T, int U1, int V, int ldl, int blank, void *workspace, size_t workspace_bytes,
+                     void *stream) {
+    TSASR_CHECK_ARG(logits && targets && tlen && ulen && frames && scores && workspace, "tsasr_rnnt_align: null pointer");
+    TSASR_CHECK_ARG(B > 0 && T > 0 && U1 > 0, "tsasr_rnnt_align: empty batch (B=%d T=%d U1=%d)", B, T, U1);
+    TSASR_CHECK_ARG(V > 0 && ldl >= V && ldl % 4 == 0, "tsasr_rnnt_align: rows must be padded to a multiple of 4 floats (V=%d ldl=%d)", V, ldl);
+    TSASR_CHECK_ARG(blank >= 0 && blank < V, "tsasr_rnnt_align: blank=%d outside [0,%d)", blank, V);
+    TSASR_CHECK_ARG(U1 <= 64 * 32, "tsasr_rnnt_align: U1=%d > 2048 lattice columns not supported", U1);
+    TSASR_CHECK_ARG(ldf >= std::max(U1 - 1, 1), "tsasr_rnnt_align: ldf=%d < max(U1-1, 1)=%d", ldf, std::max(U1 - 1, 1));
+    TSASR_CHECK_ARG(workspace_bytes >= tsasr_rnnt_align_workspace_bytes(B, T, U1), "tsasr_rnnt_align: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned *bits = nullptr;
+    RnntWs w = align_carve(workspace, B, T, U1, &bits);
+    const long long rows = (long long)B * T * U1;
+    rnnt_lp_kernel<<<(unsigned)(V <= 32 ? (rows + 127) / 128 : (rows + 31) / 32), 256, 0, st>>>(logits, targets, ldt, tlen, ulen, w, B, T, U1, V, ldl, blank);
+#define VT_CASE(K_, NW_) if (w.KT == K_ && w.NW == NW_) launch_viterbi<K_, NW_>(w, bits, tlen, ulen, frames, ldf, scores, B, T, U1, st); else
+    VT_CASE(1, 1) VT_CASE(2, 1) VT_CASE(4, 1) VT_CASE(2, 4) VT_CASE(2, 8) VT_CASE(4, 8)
+#undef VT_CASE
+    {
+        tsasr_set_error("tsasr_rnnt_align: no lattice kernel for %d columns per thread x %d waves", w.KT, w.NW);
+        return TSASR_E_INVALID;
+    }
+    TSASR_CHECK_LAUNCH("tsasr_rnnt_align");
     return 0;
 }
 

@@ -118,7 +118,8 @@ class TSASR(core.Brain):
                 prof.stamp("early weight gradients done [main]")
         return None
 
-    def compute_forward(self, batch, stage):
+    def _forward_logits(self, batch, stage):
+        """The forward up to the fused joint logits, shared by compute_forward and align_batch: (logits, enc_out, tlen, ulen, epoch)."""
         hp = self.hparams
         epoch = hp.epoch_counter.current if hasattr(hp, "epoch_counter") else 0
         batch = batch.to(self.device)
@@ -211,6 +212,11 @@ class TSASR(core.Brain):
         logits = rnnt.fused_joint_logits(enc_out, dec_out, head.weight, head.bias, self.modules.joiner.nonlinearity.negative_slope,
                                          tlen, ulen)
         prof.stamp("joint forward done [main]")
+        return logits, enc_out, tlen, ulen, epoch
+
+    def compute_forward(self, batch, stage):
+        hp = self.hparams
+        logits, enc_out, _, _, epoch = self._forward_logits(batch, stage)
         hyps = None
         if stage == Stage.VALID:
             if epoch % getattr(hp, "valid_search_freq", 1) == 0 and hasattr(hp, "greedy_searcher"):
@@ -218,6 +224,20 @@ class TSASR(core.Brain):
         elif stage == Stage.TEST and hasattr(hp, "beam_searcher"):
             hyps, _, _, _ = hp.beam_searcher(enc_out)
         return logits, hyps
+
+    def align_batch(self, batch):
+        """Forced alignment of a batch's reference transcripts: ``(frames int32 [B, U], scores fp32 [B])`` on the device (rnnt.rnnt_align:
+        frames[b, u] = encoder frame at which token u is emitted, -1 beyond the utterance's tokens). Eval mode, no gradients; the forward
+        of compute_forward up to the joint logits with the same lengths - no searcher, no loss. The modules' training flag is restored."""
+        was_training = self.modules.training
+        self.modules.eval()
+        try:
+            with torch.no_grad():
+                logits, _, tlen, ulen, _ = self._forward_logits(batch, Stage.TEST)
+                return rnnt.rnnt_align(logits, self._tokens32[1], tlen, ulen, getattr(self.hparams, "blank_index", 0))
+        finally:
+            if was_training:
+                self.modules.train()
 
     def compute_objectives(self, predictions, batch, stage):
         logits, hyps = predictions

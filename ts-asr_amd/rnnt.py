@@ -167,6 +167,38 @@ def transducer_loss(logits, targets, input_lens, target_lens, blank_index, reduc
     raise Exception("Unexpected reduction {}".format(reduction))
 
 
+def rnnt_align(logits, targets, abs_input_lens, abs_target_lens, blank=0):
+    """Forced alignment of `targets` on the loss lattice (csrc/rnnt.hip rnnt_viterbi_kernel; no autograd).
+
+    Returns ``(frames int32 [B, U], scores float32 [B])`` with U = U1 - 1: ``frames[b, u]`` is the frame at which label u is emitted on
+    the most probable path (-1 for u >= the utterance's target length), ``scores[b]`` that path's log-probability. Among equally
+    probable paths the one that emits every label as early as possible is returned. Accepts what ``rnnt_costs`` accepts."""
+    C.require_gpu(logits, targets, abs_input_lens, abs_target_lens)
+    B, T, U1, V = logits.shape
+    lg = logits.detach()
+    lg = _as_padded_rows(lg.float() if lg.dtype != torch.float32 else lg, V)
+    tg = targets.to(torch.int32).contiguous()
+    tlen, ulen = abs_input_lens.to(torch.int32).contiguous(), abs_target_lens.to(torch.int32).contiguous()
+    if tg.dim() != 2 or tg.shape[0] != B or tg.shape[1] < U1 - 1:
+        raise ValueError(f"targets must be [B, >= U1-1] = [{B}, >= {U1 - 1}], got {tuple(tg.shape)}")
+    frames = torch.empty(B, max(U1 - 1, 1), dtype=torch.int32, device=lg.device)
+    scores = torch.empty(B, dtype=torch.float32, device=lg.device)
+    ws = _ws(C.lib().tsasr_rnnt_align_workspace_bytes(B, T, U1), lg.device)
+    with prof.region("rnnt_align"):
+        C.check(C.lib().tsasr_rnnt_align(C.ptr(lg), C.ptr(tg), tg.stride(0), C.ptr(tlen), C.ptr(ulen), C.ptr(frames), frames.stride(0),
+                                         C.ptr(scores), B, T, U1, V, lg.stride(-2), int(blank), C.ptr(ws), ws.numel(), C.stream_ptr()),
+                "tsasr_rnnt_align")
+    return frames[:, :U1 - 1], scores
+
+
+def transducer_align(logits, targets, input_lens, target_lens, blank_index):
+    """``rnnt_align`` with RELATIVE lengths, rounded exactly as ``transducer_loss`` rounds them."""
+    from .nnet import abs_lengths_round
+    tl = abs_lengths_round(input_lens, logits.shape[1])
+    ul = abs_lengths_round(target_lens, targets.shape[1])
+    return rnnt_align(logits, targets, tl, ul, blank_index)
+
+
 class Transducer_joint(torch.nn.Module):
     """Same constructor/forward as the reference joiner (transducer_joint.py:14-95) for joint="sum".
 
