@@ -170,6 +170,12 @@ int tsasr_dropout_add2_bwd(const void *dout, void *dx, void *dres, float *dbias,
  * activation (:95-97).  y2 [B,T,2D] io_dtype = bottleneck GEMM output without bias; b2 [2D] or NULL; conv_w [D,K] (the
  * [D,1,K] parameter); conv_b, gamma, beta [D]. D % 8 == 0, D <= 2048, K in {31,15,7,3}. c_save [B,T,D], mean/rstd [B*T] are
  * written by fwd and read by bwd. bwd: dparams fp32 = [dgamma D | dbeta D | dconv_b D | db2 2D | dconv_w D*K], overwritten.
+ * Pinned by tests/test_convmod_paths_gpu.py: slope < 0 means no activation, in both directions; any T >= 1 (shorter than the
+ * filter or its padding included); dparams and the workspace need NO initialisation - every word of dparams is written, db2
+ * also when b2 is NULL, and a workspace of exactly tsasr_convmod_bwd_workspace_bytes suffices; bwd leaves z, c_save, mean and
+ * rstd as they were; a rejected call (K not instantiated, D % 8 != 0, D > 2048, workspace too small) writes nothing. The
+ * io_dtype / D / TSASR_CONVMOD_FUSED dispatch (bf16 rows of 256 channels: one launch per direction) changes no output bit of
+ * z, c_save, mean, rstd and dy2.
  * ------------------------------------------------------------------------------------------ */
 int tsasr_convmod_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
                       const float *beta, void *z, void *c_save, float *mean, float *rstd, int B, int T, int D, int K, int causal,
@@ -551,7 +557,8 @@ int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, 
                                  int io_dtype, void *workspace, size_t workspace_bytes, void *stream);
 /* tsasr_convmod_fwd with causal = 1 on a chunk y2 [B,C,2D], no saved tensors: the K-1 GLU rows in front of the chunk come from
  * hist_in fp32 [B,K-1,D] (zeros = the offline zero pad), the last K-1 GLU rows of [history | chunk] are written to hist_out (a second
- * buffer: swap the two per chunk). z [B,C,D] (io_dtype). */
+ * buffer: swap the two per chunk). z [B,C,D] (io_dtype). Every row of hist_out is written by every call (rows carried over from
+ * hist_in bit for bit when C < K-1); slope < 0 means no activation, as in tsasr_convmod_fwd; hist_in == hist_out is rejected. */
 int tsasr_convmod_stream_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
                              const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
                              float slope, int io_dtype, void *stream);

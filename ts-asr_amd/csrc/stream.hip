@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void convmod_stream_kernel(const ConvStreamArg
     T *z = (T *)a.z + ((long long)b * a.C + r) * D;
     for (int d = tid; d < D; d += 256) {
         const float y = (crow[d] - mean) * rs * a.g[d] + a.be[d];
-        st1(z + d, y > 0.f ? y : y * a.slope);
+        st1(z + d, (a.slope < 0.f || y > 0.f) ? y : y * a.slope);   // slope < 0: no activation, as tsasr_convmod_fwd
     }
     for (int mrow = r; mrow < hk; mrow += a.C)        // next history row mrow = ext row C + mrow
         for (int d = tid; d < D; d += 256) hout[(long long)mrow * D + d] = ext_glu<T>(a, y2, hin, a.C + mrow, d);
