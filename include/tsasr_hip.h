@@ -114,6 +114,32 @@ int tsasr_rnnt_align(const float *logits, const int32_t *targets, int ldt, const
  *   SB/lobes/models/transformer/Conformer.py:73,93,194-217 and SB/lobes/models/convolution.py (norm over [F,C]);
  *   act_slope >= 0 fuses the LeakyReLU that follows it (Conformer.py:93-95, convolution.py ConvBlock); < 0 = none.
  * x,y: [M, D] io_dtype; gamma,beta,dgamma,dbeta: fp32 [D]; mean,rstd: fp32 [M] (saved for backward). D % 8 == 0.
+ *
+ * Row kernels: which kernel serves which width (csrc/elementwise.hip; tests/helpers/rowkern_ref.py expected_path() mirrors every rule
+ * and tests/test_rowkern_paths_gpu.py launches every instantiation). A lane moves 16 bytes: 8 bf16 or 4 fp32 elements.
+ *   tsasr_layernorm_fwd / _bwd         D (bf16)        D (fp32)       kernel
+ *                                      8 .. 256        8 .. 128       layernorm_{fwd,bwd}_kernel<T, 32, 1>   two rows per wave
+ *                                      264 .. 512      136 .. 256     <T, 64, 1>   one wave per row
+ *                                      520 .. 1024     264 .. 512     <T, 64, 2>
+ *                                      1032 .. 2048    520 .. 1024    <T, 64, 4>
+ *                                      .. 4096         .. 2048        layernorm_{fwd,bwd}_wide_kernel<T, 2>  one workgroup per row
+ *                                      .. 6144         .. 3072        <T, 3>
+ *                                      .. 8192         .. 4096        <T, 4>
+ *                                      .. 12288        .. 6144        <T, 6>
+ *                                      .. 16384        .. 8192        <T, 8>       larger D: rejected
+ *   tsasr_layernorm_bwd_add            the one-wave-per-row kernels only: D <= 2048 (bf16) / 1024 (fp32), larger D rejected
+ *   tsasr_add_layernorm_fwd / _bwd     bf16: D <= 256 <bf16, 1, half-wave>, <= 512 <1>, <= 1024 <2>, <= 2048 <4>; fp32: D <= 256 <1>, <= 512 <2>,
+ *                                      <= 1024 <4>, <= 2048 <8>; larger D rejected
+ *   tsasr_add_layernorm2_fwd / _bwd    the same table up to D <= 1024; larger D rejected
+ *   bias_act_dropout / dropout_add backward, tsasr_colsum: 256 threads = (256 / tpr) row slots x tpr column chunks, tpr = min(256, N / 8
+ *                                      (bf16) or N / 4 (fp32)); the row slots meet in LDS (at most 8 KB); tsasr_colsum: N <= 2048
+ * Backward workgroups walk rows_per_wg = max(16, ceil(M / 1024)) consecutive rows (the wide LayerNorm backward: max of that and
+ * ceil(M / 512); tsasr_colsum: max(64, ceil(M / 1024))) and leave one partial row of k x D floats each in the workspace (k = 2 LayerNorm,
+ * 3 add_layernorm, 5 add_layernorm2, 1 the bias-gradient producers and colsum), summed over workgroups in a fixed order.
+ * LDS per launch, static + dynamic: layernorm_bwd_kernel<T, TPR, .> 20 B + (256 / TPR) x 2 x D x 4 B (at most 64 KB + 20 B, bf16 D = 2048);
+ * add_layernorm_bwd 48 D B (half-wave: 96 D <= 24 KB), 96 KB at D = 2048; add_layernorm2_bwd 80 D B (half-wave: 160 D <= 40 KB), 80 KB at
+ * D = 1024; the forward kernels and the wide kernels 64 B or less. The three launches that pass 64 KB raise their kernel's dynamic-LDS
+ * limit first; all stay under the 160 KB of a gfx950 workgroup.
  * ------------------------------------------------------------------------------------------ */
 int tsasr_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd,
                         long long M, int D, float eps, float act_slope, int io_dtype, void *stream);
@@ -384,7 +410,8 @@ int tsasr_sentence_norm_fwd(const void *x, const int32_t *lens, void *y, int B, 
 
 /* Fused seam between two Conformer sub-blocks: s = res + alpha*timemask(dropout_p(x + bias)); y = LayerNorm(s)
  * (Dropout -> [0.5*]x + residual -> masked_fill_ -> nn.LayerNorm; Conformer.py:113-114,194-217,239-259) and its backward
- * (dres = LN_bwd(dy) + dout; dx = alpha*timemask*dropmask/(1-p)*dres; dgamma, dbeta, dbias). D % 8 == 0, D <= 2048. */
+ * (dres = LN_bwd(dy) + dout; dx = alpha*timemask*dropmask/(1-p)*dres; dgamma, dbeta, dbias; dout and any of the three parameter
+ * gradients may be NULL). D % 8 == 0, D <= 2048; kernel per width and LDS per launch: the "Row kernels" table above. */
 int tsasr_add_layernorm_fwd(const void *x, const float *bias, const void *res, void *s, void *y, float *mean, float *rstd,
                             const float *gamma, const float *beta, long long M, int D, float alpha, float p, unsigned long long seed,
                             const unsigned long long *seed_dev, const int32_t *valid_lens, int Trows, float eps, int io_dtype,
@@ -405,7 +432,8 @@ int tsasr_linear_add_layernorm_fwd(const void *A, long long lda, const void *W, 
                                    const int32_t *valid_lens, int Trows, float eps, void *stream);
 /* Two LayerNorms in a row with the residual tail in front - norm2 of a Conformer layer and the next layer's first LayerNorm (or the
  * encoder's final norm): Conformer.py:194-217,259, models/conformer.py:223-233. (s, y, z) bit-identical to tsasr_add_layernorm_fwd +
- * tsasr_layernorm_fwd; the backward takes dz and (optionally) the gradients reaching y and s along other paths. */
+ * tsasr_layernorm_fwd; the backward takes dz and (optionally) the gradients reaching y and s along other paths. D % 8 == 0, D <= 1024
+ * ("Row kernels" table above); any of the five parameter gradients may be NULL. */
 int tsasr_add_layernorm2_fwd(const void *x, const float *bias, const void *res, void *s, void *y, void *z, float *mean, float *rstd,
                              float *mean2, float *rstd2, const float *gamma, const float *beta, const float *gamma2, const float *beta2,
                              long long M, int D, float alpha, float p, unsigned long long seed, const unsigned long long *seed_dev,

@@ -1213,6 +1213,14 @@ static int pick_rows_per_wg(long long M, int min_rows) {
     return (int)r;
 }
 
+// Dynamic + static LDS of a launch above 64 KB (a workgroup of gfx950 may use 160 KB): the kernel's limit is raised first, as
+// csrc/frontend.hip does. `static_bytes`: the kernel's __shared__ arrays. Reached by layernorm_bwd_kernel<bf16, 64, 4> at D = 2048
+// (64 KB + 20 B), add_layernorm_bwd from D = 1368 (48 D bytes, 96 KB at 2048) and add_layernorm2_bwd from D = 824 (80 D bytes, 80 KB at 1024).
+template <typename K> static void allow_lds(K kernel, size_t dynamic_bytes, size_t static_bytes = 0) {
+    if (dynamic_bytes + static_bytes > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynamic_bytes);
+}
+
 template <typename T>
 static int launch_ln_fwd(const void *x, const float *g, const float *b, void *y, float *mean, float *rstd, long long M, int D,
                          float eps, float slope, hipStream_t st) {
@@ -1247,6 +1255,7 @@ static int launch_ln_bwd(const void *dy, const void *x, const float *g, const fl
     constexpr int N = Vec<T>::N;
     const int per_wave = 64 * N, per_wg = 256 * N;
 #define LN_BWD(TPR, IT)                                                                                                  \
+    allow_lds(layernorm_bwd_kernel<T, TPR, IT>, (size_t)(256 / TPR) * 2 * D * sizeof(float), 5 * sizeof(float)),         \
     layernorm_bwd_kernel<T, TPR, IT><<<nwg, 256, (TPR <= 64 ? (size_t)(256 / TPR) * 2 * D * sizeof(float) : 0), st>>>(   \
         (const T *)dy, (const T *)x, g, b, mean, rstd, (T *)dx, part, M, D, slope, rpw, (const T *)dadd)
 #define LN_BWD_WIDE(IT)                                                                                                   \
@@ -1509,7 +1518,7 @@ int tsasr_add_layernorm_bwd(const void *dy, const void *dout, const void *s, con
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
     const size_t lds = (size_t)12 * D * sizeof(float);
-#define ALN_B(TT, IT) add_layernorm_bwd_kernel<TT, IT><<<nwg, 256, lds, st>>>((const TT *)dy, (const TT *)dout, (const TT *)s, gamma, mean, rstd, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
+#define ALN_B(TT, IT) allow_lds(add_layernorm_bwd_kernel<TT, IT>, lds), add_layernorm_bwd_kernel<TT, IT><<<nwg, 256, lds, st>>>((const TT *)dy, (const TT *)dout, (const TT *)s, gamma, mean, rstd, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
     static const int half_rows = 1;
     if (io_dtype == TSASR_BF16) {
         if (half_rows && D <= 256)
@@ -1575,7 +1584,7 @@ int tsasr_add_layernorm2_bwd(const void *dz, const void *dy, const void *dout, c
     const int nwg = (int)((M + rpw - 1) / rpw);
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
-#define ALN2_B(TT, IT, HWV) add_layernorm2_bwd_kernel<TT, IT, HWV><<<nwg, 256, (size_t)(HWV ? 8 : 4) * 5 * D * sizeof(float), st>>>((const TT *)dz, (const TT *)dy, (const TT *)dout, (const TT *)s, gamma, beta, gamma2, mean, rstd, mean2, rstd2, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
+#define ALN2_B(TT, IT, HWV) allow_lds(add_layernorm2_bwd_kernel<TT, IT, HWV>, (size_t)(HWV ? 8 : 4) * 5 * D * sizeof(float)), add_layernorm2_bwd_kernel<TT, IT, HWV><<<nwg, 256, (size_t)(HWV ? 8 : 4) * 5 * D * sizeof(float), st>>>((const TT *)dz, (const TT *)dy, (const TT *)dout, (const TT *)s, gamma, beta, gamma2, mean, rstd, mean2, rstd2, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
     if (io_dtype == TSASR_BF16) {
         if (D <= 256) ALN2_B(bf16_t, 1, true); else if (D <= 512) ALN2_B(bf16_t, 1, false); else if (D <= 1024) ALN2_B(bf16_t, 2, false);
         else TSASR_CHECK_ARG(false, "tsasr_add_layernorm2_bwd: D=%d too large", D);
