@@ -329,7 +329,8 @@ void tsasr_relpos_attn_keepbits(void *bits);
  * Global-norm clipping + AdamW over the flat parameter arena: replaces SB/core.py:1082-1093
  * (torch.nn.utils.clip_grad_norm_ -> torch.optim.AdamW.step) with two launches; the norm stays on the device.
  * p, g, m, v: flat fp32 [n]; p_bf16 (may be NULL): bf16 shadow of p rewritten in the same pass; hyper: DEVICE float[3] = {lr, 1-beta1^t, 1-beta2^t} (graph-capturable Noam schedule).
- * norm_out (may be NULL): DEVICE float = L2 norm of g before clipping. skipped_out: NULL = the reference's behaviour on a non-finite norm (SB/core.py:1072-1093: the step is
+ * norm_out (may be NULL): DEVICE float = L2 norm of g before clipping (finite whenever the norm is an fp32 number: the squares are summed a second time in
+ * scaled form where they overflow). skipped_out: NULL = the reference's behaviour on a non-finite norm (SB/core.py:1072-1093: the step is
  * applied - clip_grad_norm_'s factor is NaN / 0 - and only the non-finite loss is counted); a DEVICE float = such a step is SKIPPED (parameters and moments untouched) and
  * counted there (+= 1): the build's `skip_nonfinite_step: True` option.
  * ------------------------------------------------------------------------------------------ */

@@ -1,6 +1,8 @@
 // Small device-side pieces of the recipe / training loop that the reference runs as chains of tiny ATen kernels (each one a launch in
 // the step's hipGraph): the masked mean-pool of the speaker encoder's output, the relative -> absolute length rounding, the
 // non-finite-loss counter.
+#include <float.h>
+
 #include "common.h"
 
 // ---- masked mean pool over time: out[b, d] = sum_{t < n_b} x[b, t, d] / n_b,  n_b = min(ceil(rel_b * T), T)
@@ -40,7 +42,7 @@ __global__ void abs_lengths_kernel(LenJobs j, int B) {
 // ---- counter += number of non-finite values among x[0..n)  (SB/core.py:1115-1150 check_gradients counts non-finite losses)
 __global__ void count_nonfinite_kernel(const float *__restrict__ x, int n, int *__restrict__ counter) {
     int c = 0;
-    for (int i = threadIdx.x; i < n; i += 64) c += !(fabsf(x[i]) <= 3.0e38f);
+    for (int i = threadIdx.x; i < n; i += 64) c += !(fabsf(x[i]) <= FLT_MAX);     // NaN and Inf only: every finite float counts as finite
     c = (int)wave_sum((float)c);
     if (threadIdx.x == 0 && c) *counter += c;
 }

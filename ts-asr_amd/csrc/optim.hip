@@ -3,12 +3,14 @@
 // Replaces speechbrain/core.py:1082-1093: torch.nn.utils.clip_grad_norm_(modules.parameters(), max_grad_norm) ->
 // optimizer.step() (torch.optim.AdamW, hparams conformer-t_scratch.yaml:267-271) -> zero_grad: ~190 tensors x several
 // foreach passes plus a host sync for grad_norm.item(). Here: two launches over four flat fp32 buffers
-//   (1) sumsq_partials: per-workgroup partial sums of g^2 (fixed partition -> deterministic);
+//   (1) sumsq_partials: per-workgroup partial sums of g^2 (fixed partition -> deterministic), and of (g 2^-64)^2 for norms above 1.8e19;
 //   (2) clip_adamw:     every workgroup re-reduces the partials (<= 1024 floats), derives the clip coefficient
 //                       min(1, max_norm / (norm + 1e-6)) exactly as clip_grad_norm_, and applies decoupled weight decay,
 //                       moment updates and the bias-corrected step in one read-modify-write pass (p, g, m, v: 7 x 4 B/elem).
 // lr and the bias corrections come from a tiny DEVICE array so the step can sit inside a captured hipGraph while the
 // Noam schedule keeps changing them from the host.
+#include <float.h>
+
 #include "common.h"
 
 #define OPT_PARTS 1024
@@ -40,7 +42,25 @@ __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float *__rest
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    const float tot = red[0] + red[1] + red[2] + red[3];        // (every thread: the branch below is workgroup-uniform)
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+    // Second row of partials, the same sums of (g 2^-64)^2: read only when the plain sum overflowed. A gradient whose norm is finite but above
+    // sqrt(FLT_MAX) = 1.8e19 squares to +Inf, and the step took it for a non-finite one. Normally that row is the plain partial scaled by
+    // 2^-128 (no second pass); a part that overflowed is summed again in scaled form. A NaN stays NaN, a real Inf stays Inf.
+    float sc = tot * 0x1p-128f;
+    if (tot == INFINITY) {
+        float t = 0.f;
+        for (long long k = lo + threadIdx.x; k < hi; k += 256) {
+            const float x = g[k] * 0x1p-64f;
+            t += x * x;
+        }
+        t = wave_sum(t);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+        __syncthreads();
+        sc = red[0] + red[1] + red[2] + red[3];
+    }
+    if (threadIdx.x == 0) part[OPT_PARTS + blockIdx.x] = sc;
 }
 
 // hyper = {lr, 1 - beta1^t, 1 - beta2^t}
@@ -54,7 +74,17 @@ __global__ __launch_bounds__(256) void clip_adamw_kernel(float *__restrict__ p, 
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+    const float sumsq = red[0] + red[1] + red[2] + red[3];
+    float norm = sqrtf(sumsq);
+    if (sumsq == INFINITY) {    // overflow of the squares, or a real Inf: the scaled partials tell which (workgroup-uniform branch)
+        float s2 = 0.f;
+        for (int i = threadIdx.x; i < OPT_PARTS; i += 256) s2 += part[OPT_PARTS + i];
+        s2 = wave_sum(s2);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s2;
+        __syncthreads();
+        norm = sqrtf(red[0] + red[1] + red[2] + red[3]) * 0x1p64f;     // +Inf again when the norm itself is not an fp32 number
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = norm;
     // A non-finite gradient norm (overflow, or a poisoned activation: csrc/lstm.hip raises NaN when its inter-workgroup wait times out).
     // Reference behaviour (SB/core.py:1072-1093): the step is applied all the same - clip_grad_norm_'s factor max_norm / (norm + 1e-6),
@@ -62,7 +92,7 @@ __global__ __launch_bounds__(256) void clip_adamw_kernel(float *__restrict__ p, 
     // moment; the non-finite LOSS was counted (check_gradients) and the run stops when nonfinite_patience is exhausted. That is what happens
     // here when skipped_out is NULL (`skip_nonfinite_step: False`, the default). With skipped_out (`skip_nonfinite_step: True`, a build
     // option) the step is skipped instead - parameters and moments untouched - and counted there.
-    const bool finite = fabsf(norm) <= 3.0e38f;
+    const bool finite = fabsf(norm) <= FLT_MAX;       // false for NaN and Inf only
     if (!finite && skipped_out) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *skipped_out += 1.f;   // skipped steps since the host last cleared it
         return;
@@ -196,7 +226,7 @@ int tsasr_accumulate_many(const void *table, int count, void *stream) {
     return 0;
 }
 
-size_t tsasr_clip_adamw_workspace_bytes(void) { return OPT_PARTS * sizeof(float); }
+size_t tsasr_clip_adamw_workspace_bytes(void) { return 2 * OPT_PARTS * sizeof(float); }   // plain and scaled partials
 
 /* p, g, m, v: flat fp32 [n] (16-byte aligned); p_bf16: optional bf16 shadow of p (GEMM operand copy), rewritten in the same pass; hyper: DEVICE float[3] = {lr, 1-beta1^t, 1-beta2^t}; norm_out: device float
  * (may be NULL) = total L2 norm of g before clipping; skipped_out: device float or NULL. NULL (reference behaviour, SB/core.py:1072-1093): a
@@ -211,7 +241,7 @@ int tsasr_clip_adamw_step(float *p, void *p_bf16, const float *g, float *m, floa
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
     sumsq_partials_kernel<<<OPT_PARTS, 256, 0, st>>>(g, part, n);
-    long long blocks = (n / 4 + 255) / 256;
+    long long blocks = ((n + 3) / 4 + 255) / 256;     // one thread per group of 4, the last partial group included (n < 4 gave an empty grid)
     if (blocks > 2048) blocks = 2048;
     clip_adamw_kernel<<<(unsigned)blocks, 256, 0, st>>>(p, (bf16_t *)p_bf16, g, m, v, part, hyper, norm_out, skipped_out, n, beta1, beta2, eps, weight_decay, max_norm);
     TSASR_CHECK_LAUNCH("tsasr_clip_adamw_step");

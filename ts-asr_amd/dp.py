@@ -150,9 +150,12 @@ class GradArena:
         self.direct = bool(world_size > 1 and direct_rccl_init(world_size, dist.get_rank() if is_initialized() else 0, params[0].device))
         self.comm_stream = None
         self.device = params[0].device
-        # every parameter starts at a multiple of _PAD (64) elements: its bf16 shadow (and transposed copy) is then line-aligned - what the
-        # GEMMs' 16-byte operand pieces and the vectorised transpose want (a 29-element bias early in the arena used to shift every
-        # weight behind it off that alignment). The pad words stay zero (parameters and gradients alike).
+        # every parameter starts at a multiple of _PAD (64) elements of the arena, and every transposed copy at a multiple of _PAD elements
+        # of flat_params16_t (refresh_shadow): the bf16 shadow and the transposed copy of every weight then start on a 128-byte line - what
+        # the GEMMs' 16-byte operand pieces and the vectorised transpose want (a 29-element bias early in the arena used to shift every
+        # weight behind it off that alignment; a [17, 241] matrix did the same to every transposed copy behind it while those were packed
+        # back to back). The pad words of the fp32 arena stay zero (parameters and gradients alike); those of flat_params16_t are never
+        # read or written.
         self.numel = sum(_pad8(p.numel()) for p in params)
         self.grads = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
         self.flat_params = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
@@ -230,7 +233,7 @@ class GradArena:
         self.flat_params16.copy_(self.flat_params)
         jobs, t_off, tiles = [], 0, 0
         mats = [p for p in self.params_ordered if (p.dim() == 2 or (p.dim() == 3 and p.shape[2] == 1)) and min(p.shape[:2]) >= 16 and p.numel() >= 4096]
-        total_t = sum(p.numel() for p in mats)
+        total_t = sum(_pad8(p.numel()) for p in mats)     # every transposed copy starts at a multiple of _PAD elements
         if getattr(self, "flat_params16_t", None) is None or self.flat_params16_t.numel() != total_t:
             self.flat_params16_t = torch.empty(max(total_t, 1), dtype=torch.bfloat16, device=self.device)
         for p in self.params_ordered:
@@ -242,7 +245,7 @@ class GradArena:
             r, c = p.shape[0], p.shape[1]
             jobs.append((self.offset[id(p)], t_off, r, c, tiles))
             p._bf16_t = self.flat_params16_t[t_off:t_off + r * c].view(c, r)
-            t_off += r * c
+            t_off += _pad8(r * c)
             tiles += ((r + 63) // 64) * ((c + 63) // 64)
         self._tr_njobs, self._tr_tiles = len(jobs), tiles
         self._tr_jobs = torch.tensor(jobs, dtype=torch.int32).reshape(-1).to(self.device) if jobs else None
