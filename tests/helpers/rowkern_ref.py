@@ -188,7 +188,7 @@ def lds_bytes(entry, io, D):
         if "wide" in path:
             return 64
         tpr = int(path.split(",")[1])
-        return 20 + (256 // tpr) * 2 * D * 4
+        return 16 + (256 // tpr) * 2 * D * 4
     if entry == "add_layernorm_bwd":
         return (24 if "true" in path else 12) * D * 4
     if entry == "add_layernorm2_bwd":

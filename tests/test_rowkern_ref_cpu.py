@@ -203,8 +203,8 @@ def test_rows_workgroups_and_workspace_bytes_by_hand():
 
 def test_lds_table():
     """static + dynamic LDS per launch; the three launches over 64 KB stay under the 160 KB a workgroup of gfx950 may use"""
-    assert R.lds_bytes("layernorm_bwd", "bf16", 2048) == 65536 + 20 and R.lds_bytes("layernorm_bwd", "f32", 1024) == 32768 + 20
-    assert R.lds_bytes("layernorm_bwd", "bf16", 256) == 8 * 2 * 256 * 4 + 20 and R.lds_bytes("layernorm_bwd", "bf16", 2056) == 64
+    assert R.lds_bytes("layernorm_bwd", "bf16", 2048) == 65536 + 16 and R.lds_bytes("layernorm_bwd", "f32", 1024) == 32768 + 16
+    assert R.lds_bytes("layernorm_bwd", "bf16", 256) == 8 * 2 * 256 * 4 + 16 and R.lds_bytes("layernorm_bwd", "bf16", 2056) == 64
     assert R.lds_bytes("add_layernorm_bwd", "bf16", 2048) == 96 * 1024 and R.lds_bytes("add_layernorm_bwd", "f32", 1368) == 65664
     assert R.lds_bytes("add_layernorm_bwd", "f32", 1360) == 65280 and R.lds_bytes("add_layernorm_bwd", "bf16", 256) == 24 * 1024
     assert R.lds_bytes("add_layernorm2_bwd", "bf16", 1024) == 80 * 1024 and R.lds_bytes("add_layernorm2_bwd", "f32", 824) == 65920

@@ -14,24 +14,7 @@
 
 #include <algorithm>
 
-#include "common.h"
-
-template <typename T> struct Vec;  // 16-byte vector of T
-template <> struct Vec<float> { static constexpr int N = 4; };
-template <> struct Vec<bf16_t> { static constexpr int N = 8; };
-
-template <typename T, int N> __device__ __forceinline__ void ldv(const T *p, float (&o)[N]);
-template <> __device__ __forceinline__ void ldv<float, 4>(const float *p, float (&o)[4]) {
-    const float4 a = *reinterpret_cast<const float4 *>(p);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-}
-template <> __device__ __forceinline__ void ldv<bf16_t, 8>(const bf16_t *p, float (&o)[8]) { ld8(p, o); }
-template <> __device__ __forceinline__ void ldv<float, 8>(const float *p, float (&o)[8]) { ld8(p, o); }   // fp32 parameters beside bf16 rows
-template <typename T, int N> __device__ __forceinline__ void stv(T *p, const float (&v)[N]);
-template <> __device__ __forceinline__ void stv<float, 4>(float *p, const float (&v)[4]) {
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void stv<bf16_t, 8>(bf16_t *p, const float (&v)[8]) { st8(p, v); }
+#include "rowpass.h"
 
 // block-wide sum for TPR (threads per row) = 64 (one wave) or 256 (one workgroup)
 template <int TPR> __device__ __forceinline__ float row_sum(float v, float *red) {
@@ -119,8 +102,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T *__restrict_
                                                             float slope, int rows_per_wg, const T *__restrict__ dadd) {
     constexpr int N = Vec<T>::N;
     __shared__ float red[4];
-    __shared__ float colred[(TPR == 64) ? 1 : 1];
-    (void)colred;
     const int rpb = 256 / TPR;
     const int sub = threadIdx.x / TPR, l = threadIdx.x % TPR;
     float ag[ITERS][N], abt[ITERS][N];
@@ -683,8 +664,122 @@ __global__ __launch_bounds__(256) void dropout_add_bwd_kernel(const T *__restric
 // replaces Dropout -> (0.5*)x + residual -> [masked_fill_] -> nn.LayerNorm, Conformer.py:113-114,239-259 + :73,194-217.
 // Backward: d_s = LayerNorm_bwd(dy) + dout (gradient arriving through the residual path);  dres = d_s ;
 //           dx = alpha * timemask * dropmask/(1-p) * d_s ;  column partials for dgamma, dbeta, dbias.
+//
+// The seam between two Conformer LAYERS is two LayerNorms in a row: norm2 of layer i (Conformer.py:259) and the first macaron FFN's
+// LayerNorm of layer i+1 (Conformer.py:194-217; after the last layer: the encoder's final norm, models/conformer.py:233). TWO: one pass
+//   s = res + alpha * timemask(dropout_p(x + bias)) ;  y = LN(s) * gamma + beta ;  z = LN(y) * gamma2 + beta2
+// with the statistics of z taken from the STORED (rounded) y, so (y, z) are bit-identical to add_layernorm + layernorm.
+// Backward:  dy_total = LN_bwd2(dz) + dy (gradient that reaches y along the residual path; may be NULL), rounded to the io dtype as
+// the tensor it replaces was; then exactly add_layernorm_bwd. y is recomputed from s (beta needed), never read.
+// The arithmetic is csrc/rowpass.h's. The two forward kernels are one body under the names that profiles, bench.py and the tests know;
+// the two backward kernels share the pieces and keep a body each: as one inlined body the one-LayerNorm backward loses an occupancy
+// step in three instantiations (profiles/rowpass_refactor_notes.md).
 // ---------------------------------------------------------------------------------------------------
-template <typename T, int ITERS, bool HW = false>   // HW: two rows per wave (D <= 32 lanes x 16 bytes)
+template <typename T, int ITERS, bool HW, bool TWO>   // HW: two rows per wave (D <= 32 lanes x 16 bytes); TWO: y and z
+__device__ __forceinline__ void add_layernorm_fwd_body(const T *x, const float *bias, const T *res, T *s_out, T *y, T *z, float *mean, float *rstd,
+                                                       float *mean2, float *rstd2, const float *gamma, const float *beta, const float *gamma2,
+                                                       const float *beta2, long long M, int D, float alpha, float p, unsigned long long seed,
+                                                       const unsigned long long *seed_dev, const int32_t *valid_lens, int Trows, float eps,
+                                                       float eps2) {
+    constexpr int N = Vec<T>::N, LPR = HW ? 32 : 64;   // lanes per row
+    long long row = HW ? ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + ((threadIdx.x >> 5) & 1) : (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int l = threadIdx.x & (LPR - 1);
+    if (!HW && row >= M) return;
+    const bool row_valid = row < M;                    // HW: the other half-wave may own a row (rowpass.h, lanes_sum)
+    if (HW && !row_valid) row = M - 1;
+    const TailOperands op = tail_operands(bias, seed_dev, valid_lens, Trows, gamma);
+    const unsigned long long seed_add = *op.seed_p;
+    const int vl = op.length_of(row);
+    float v[ITERS][N];
+    float gv[ITERS][N], bt[ITERS][N], gv2[ITERS][N], bt2[ITERS][N];      // requested with the row, used after the reductions
+    float xv[ITERS][N], rv[ITERS][N], bv[ITERS][N];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const int c = col_clamped<N, LPR>(it, l, D);
+        ldv<float, N>(gamma + c, gv[it]);
+        ldv<float, N>(beta + c, bt[it]);
+        if constexpr (TWO) {
+            ldv<float, N>(gamma2 + c, gv2[it]);
+            ldv<float, N>(beta2 + c, bt2[it]);
+        }
+        ldv<T, N>(x + row * D + c, xv[it]);
+        ldv<T, N>(res + row * D + c, rv[it]);
+        ldv<float, N>(op.bias_p + c, bv[it]);
+    }
+    if (seed_dev) seed += seed_add;
+    const unsigned thr = drop_thr16(p);
+    const DropKey dk = drop_key(seed);
+    const float ks = drop_scale16(thr);
+    const bool live = op.live(row, vl);
+    float sum = 0.f;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const int c = (it * LPR + l) * N;
+        if (c < D) {
+            const unsigned km = tail_keep_mask<N>(row, D, c, p, dk, thr);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                v[it][j] = tail_value<T>(xv[it][j], bv[it][j], rv[it][j], op.has_bias, p, (km >> j) & 1u, ks, live, alpha);
+                sum += v[it][j];
+            }
+            if (row_valid) stv<T, N>(s_out + row * D + c, v[it]);
+        }
+    }
+    const float mu = row_mean<LPR>(sum, D);
+    float q = 0.f;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        if ((it * LPR + l) * N < D) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) q += centred_sq(v[it][j], mu);
+        }
+    }
+    const float rs = row_rstd<LPR>(q, D, eps);
+    float mu2 = 0.f, rs2 = 0.f;
+    if constexpr (TWO) {
+        float sum2 = 0.f;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int c = (it * LPR + l) * N;
+            if (c < D) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    v[it][j] = ln_value<T, true>(v[it][j], mu, rs, gv[it][j], bt[it][j]);       // the second LayerNorm sees the stored row
+                    sum2 += v[it][j];
+                }
+                if (row_valid) stv<T, N>(y + row * D + c, v[it]);
+            }
+        }
+        mu2 = row_mean<LPR>(sum2, D);
+        float q2 = 0.f;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            if ((it * LPR + l) * N < D) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) q2 += centred_sq(v[it][j], mu2);
+            }
+        }
+        rs2 = row_rstd<LPR>(q2, D, eps2);
+    }
+    if (!row_valid) return;
+    if (l == 0) {
+        mean[row] = mu; rstd[row] = rs;
+        if constexpr (TWO) { mean2[row] = mu2; rstd2[row] = rs2; }
+    }
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const int c = (it * LPR + l) * N;
+        if (c < D) {
+            float o[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                o[j] = TWO ? ln_value<T, false>(v[it][j], mu2, rs2, gv2[it][j], bt2[it][j]) : ln_value<T, false>(v[it][j], mu, rs, gv[it][j], bt[it][j]);
+            stv<T, N>((TWO ? z : y) + row * D + c, o);
+        }
+    }
+}
+
+template <typename T, int ITERS, bool HW = false>
 __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const T *__restrict__ x, const float *__restrict__ bias,
                                                                 const T *__restrict__ res, T *__restrict__ s_out, T *__restrict__ y,
                                                                 float *__restrict__ mean, float *__restrict__ rstd,
@@ -692,83 +787,8 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const T *__restr
                                                                 long long M, int D, float alpha, float p, unsigned long long seed,
                                                                 const unsigned long long *__restrict__ seed_dev,
                                                                 const int32_t *__restrict__ valid_lens, int Trows, float eps) {
-    constexpr int N = Vec<T>::N, LPR = HW ? 32 : 64;   // lanes per row
-    long long row = HW ? ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + ((threadIdx.x >> 5) & 1) : (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & (LPR - 1);
-    if (!HW && row >= M) return;
-    const bool row_valid = row < M;                    // HW: no early exit, the other half-wave may own a row (loads clamped, stores guarded)
-    if (HW && !row_valid) row = M - 1;
-    // ONE round trip: every operand - the device seed, the utterance length, the parameters, the row - is requested up front,
-    // unconditionally (optional ones from a stand-in address, columns clamped) and masked afterwards. `if (seed_dev) seed += *seed_dev`,
-    // `valid_lens ? valid_lens[..] : ..` and `if (bias) load` are guarded loads: each was waited for where it stood, three dependent
-    // round trips in front of the row's own.
-    const bool has_bias = bias != nullptr, has_vl = valid_lens != nullptr;
-    const unsigned long long *seed_p = seed_dev ? seed_dev : reinterpret_cast<const unsigned long long *>(gamma);
-    const int32_t *vl_p = has_vl ? valid_lens : reinterpret_cast<const int32_t *>(gamma);
-    const float *bias_p = has_bias ? bias : gamma;
-    const int trows = has_vl ? max(Trows, 1) : 1;
-    const unsigned long long seed_add = *seed_p;
-    const int vl = vl_p[has_vl ? row / trows : 0];
-    float v[ITERS][N];
-    float gv[ITERS][N], bt[ITERS][N];      // requested with the row, used after the two reductions
-    float xv[ITERS][N], rv[ITERS][N], bv[ITERS][N];
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = min((it * LPR + l) * N, D - N);
-        ldv<float, N>(gamma + c, gv[it]);
-        ldv<float, N>(beta + c, bt[it]);
-        ldv<T, N>(x + row * D + c, xv[it]);
-        ldv<T, N>(res + row * D + c, rv[it]);
-        ldv<float, N>(bias_p + c, bv[it]);
-    }
-    if (seed_dev) seed += seed_add;
-    const unsigned thr = drop_thr16(p);
-    const DropKey dk = drop_key(seed);
-    const float ks = drop_scale16(thr);
-    const bool live = !has_vl || ((int)(row % trows) < vl);
-    float sum = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-            const unsigned long long idx = (unsigned long long)row * D + c;
-            const unsigned km = p > 0.f ? drop_keep_mask<N>((unsigned long long)idx, dk, thr) : ~0u;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                float t = xv[it][j] + (has_bias ? bv[it][j] : 0.f);
-                if (p > 0.f) t = ((km >> j) & 1u) ? t * ks : 0.f;
-                t = live ? t * alpha : 0.f;
-                t += rv[it][j];
-                if (sizeof(T) == 2) t = (float)(bf16_t)t;   // statistics of the STORED (rounded) row, as a separate LN would see
-                v[it][j] = t;
-                sum += t;
-            }
-            if (row_valid) stv<T, N>(s_out + row * D + c, v[it]);
-        }
-    }
-    const float mu = (HW ? half_wave_sum(sum) : wave_sum(sum)) / D;
-    float q = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) { const float d = v[it][j] - mu; q += d * d; }
-        }
-    }
-    const float rs = rsqrtf((HW ? half_wave_sum(q) : wave_sum(q)) / D + eps);
-    if (!row_valid) return;
-    if (l == 0) { mean[row] = mu; rstd[row] = rs; }
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-            float o[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) o[j] = (v[it][j] - mu) * rs * gv[it][j] + bt[it][j];
-            stv<T, N>(y + row * D + c, o);
-        }
-    }
+    add_layernorm_fwd_body<T, ITERS, HW, false>(x, bias, res, s_out, y, nullptr, mean, rstd, nullptr, nullptr, gamma, beta, nullptr, nullptr, M, D,
+                                                alpha, p, seed, seed_dev, valid_lens, Trows, eps, 0.f);
 }
 
 // part rows per workgroup: [dgamma D | dbeta D | dbias D]
@@ -806,8 +826,8 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const T *__restr
     const long long r0 = (long long)blockIdx.x * rows_per_wg, r1 = min(r0 + rows_per_wg, M);
     // a row slot (wave, or half-wave) walks rows r0 + slot, +RPP, ...: the next row (s, dy, dout, mean, rstd) is requested before this row's reductions
     float sn[ITERS][N], dn[ITERS][N], on[ITERS][N], mu_n = 0.f, rs_n = 0.f;
-    // optional operands are ALWAYS requested, from a stand-in address when absent (and ignored): `if (ptr) load` is a guarded load - it was
-    // waited for on the spot, and drained every other request of the row with it; the same for the utterance length read per row
+    // optional operands are ALWAYS requested, from a stand-in address when absent (and ignored), and so is the utterance length read per
+    // row: no guarded loads (rowpass.h, operand prologue)
     const bool has_dout = dout != nullptr, has_vl = valid_lens != nullptr;
     const T *dout_p = has_dout ? dout : dy;
     const int32_t *vl_p = has_vl ? valid_lens : reinterpret_cast<const int32_t *>(mean);
@@ -824,8 +844,8 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const T *__restr
         rs_n = rstd[row];
         vl_n = vl_p[row / trows];
     };
-    // HW: both halves of a wave stay in the loop together (the reductions are wave-wide instructions); a half without a row
-    // re-reads the last row and contributes nothing
+    // HW: both halves of a wave stay in the loop together (rowpass.h, lanes_sum); a half without a row re-reads the last row and
+    // contributes nothing
     if (HW ? r0 + (slot & ~1) < r1 : r0 + slot < r1) request(min(r0 + slot, r1 - 1));
     for (long long row_w = r0 + (HW ? (slot & ~1) : slot); row_w < r1; row_w += RPP) {
         const long long row_u = HW ? row_w + (slot & 1) : row_w;
@@ -844,30 +864,23 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const T *__restr
                 xh[it][j] = h;
                 ag[it][j] += dv * h;
                 abt[it][j] += dv;
-                const float g = dv * gm[it][j];
-                gd[it][j] = g;
-                s1 += g;
-                s2 += g * h;
+                gd[it][j] = ln_bwd_sums(dv, h, gm[it][j], s1, s2);
                 dov[it][j] = has_dout ? on[it][j] : 0.f;
             }
         }
         if (row_w + RPP < r1) request(min(row_u + RPP, r1 - 1));
-        const float m1 = (HW ? half_wave_sum(s1) : wave_sum(s1)) / D, m2 = (HW ? half_wave_sum(s2) : wave_sum(s2)) / D;
+        const float m1 = row_mean<LPR>(s1, D), m2 = row_mean<LPR>(s2, D);
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             if (HW ? (ok[it] && row_valid) : ok[it]) {
                 const int c = cc[it];
                 float ds[N], dxv[N];
-                const unsigned long long idx = (unsigned long long)row * D + c;
-                const unsigned km = p > 0.f ? drop_keep_mask<N>((unsigned long long)idx, dk, thr) : ~0u;
+                const unsigned km = tail_keep_mask<N>(row, D, c, p, dk, thr);
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
-                    const float d = rs * (gd[it][j] - m1 - xh[it][j] * m2) + dov[it][j];
-                    ds[j] = d;
-                    float g = live ? d * alpha : 0.f;
-                    if (p > 0.f) g = ((km >> j) & 1u) ? g * ks : 0.f;
-                    dxv[j] = g;
-                    abx[it][j] += g;
+                    ds[j] = ln_bwd_dx(gd[it][j], xh[it][j], rs, m1, m2) + dov[it][j];
+                    dxv[j] = tail_bwd_value(ds[j], p, (km >> j) & 1u, ks, live, alpha);
+                    abx[it][j] += dxv[j];
                 }
                 stv<T, N>(dres + row * D + c, ds);
                 stv<T, N>(dx + row * D + c, dxv);
@@ -895,15 +908,6 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const T *__restr
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// The seam between two Conformer LAYERS is two LayerNorms in a row: norm2 of layer i (Conformer.py:259) and the first macaron FFN's
-// LayerNorm of layer i+1 (Conformer.py:194-217; after the last layer: the encoder's final norm, models/conformer.py:233). One pass:
-//   s = res + alpha * timemask(dropout_p(x + bias)) ;  y = LN(s) * gamma + beta ;  z = LN(y) * gamma2 + beta2
-// with the statistics of z taken from the STORED (rounded) y, so (y, z) are bit-identical to add_layernorm + layernorm.
-// Backward:  dy_total = LN_bwd2(dz) + dy (gradient that reaches y along the residual path; may be NULL), rounded to the io dtype as
-// the tensor it replaces was; then exactly add_layernorm_bwd. y is recomputed from s (beta needed), never read.
-// part rows per workgroup: [dgamma D | dbeta D | dbias D | dgamma2 D | dbeta2 D]
-// ---------------------------------------------------------------------------------------------------
 template <typename T, int ITERS, bool HW>
 __global__ __launch_bounds__(256) void add_layernorm2_fwd_kernel(const T *__restrict__ x, const float *__restrict__ bias,
                                                                  const T *__restrict__ res, T *__restrict__ s_out, T *__restrict__ y,
@@ -914,107 +918,8 @@ __global__ __launch_bounds__(256) void add_layernorm2_fwd_kernel(const T *__rest
                                                                  long long M, int D, float alpha, float p, unsigned long long seed,
                                                                  const unsigned long long *__restrict__ seed_dev,
                                                                  const int32_t *__restrict__ valid_lens, int Trows, float eps, float eps2) {
-    constexpr int N = Vec<T>::N, LPR = HW ? 32 : 64;
-    long long row = HW ? ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + ((threadIdx.x >> 5) & 1) : (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & (LPR - 1);
-    if (!HW && row >= M) return;
-    const bool row_valid = row < M;                    // HW: no early exit (the reductions are wave-wide instructions); stores guarded
-    if (HW && !row_valid) row = M - 1;
-    // one round trip for every operand (see add_layernorm_fwd_kernel): optional ones from a stand-in address, columns clamped
-    const bool has_bias = bias != nullptr, has_vl = valid_lens != nullptr;
-    const unsigned long long *seed_p = seed_dev ? seed_dev : reinterpret_cast<const unsigned long long *>(gamma);
-    const int32_t *vl_p = has_vl ? valid_lens : reinterpret_cast<const int32_t *>(gamma);
-    const float *bias_p = has_bias ? bias : gamma;
-    const int trows = has_vl ? max(Trows, 1) : 1;
-    const unsigned long long seed_add = *seed_p;
-    const int vl = vl_p[has_vl ? row / trows : 0];
-    float v[ITERS][N], gv[ITERS][N], bt[ITERS][N], gv2[ITERS][N], bt2[ITERS][N];
-    float xv[ITERS][N], rv[ITERS][N], bv[ITERS][N];
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = min((it * LPR + l) * N, D - N);
-        ldv<float, N>(gamma + c, gv[it]);
-        ldv<float, N>(beta + c, bt[it]);
-        ldv<float, N>(gamma2 + c, gv2[it]);
-        ldv<float, N>(beta2 + c, bt2[it]);
-        ldv<T, N>(x + row * D + c, xv[it]);
-        ldv<T, N>(res + row * D + c, rv[it]);
-        ldv<float, N>(bias_p + c, bv[it]);
-    }
-    if (seed_dev) seed += seed_add;
-    const unsigned thr = drop_thr16(p);
-    const DropKey dk = drop_key(seed);
-    const float ks = drop_scale16(thr);
-    const bool live = !has_vl || ((int)(row % trows) < vl);
-    float sum = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-            const unsigned long long idx = (unsigned long long)row * D + c;
-            const unsigned km = p > 0.f ? drop_keep_mask<N>((unsigned long long)idx, dk, thr) : ~0u;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                float t = xv[it][j] + (has_bias ? bv[it][j] : 0.f);
-                if (p > 0.f) t = ((km >> j) & 1u) ? t * ks : 0.f;
-                t = live ? t * alpha : 0.f;
-                t += rv[it][j];
-                if (sizeof(T) == 2) t = (float)(bf16_t)t;
-                v[it][j] = t;
-                sum += t;
-            }
-            if (row_valid) stv<T, N>(s_out + row * D + c, v[it]);
-        }
-    }
-    const float mu = (HW ? half_wave_sum(sum) : wave_sum(sum)) / D;
-    float q = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) { const float d = v[it][j] - mu; q += d * d; }
-        }
-    }
-    const float rs = rsqrtf((HW ? half_wave_sum(q) : wave_sum(q)) / D + eps);
-    float sum2 = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                float t = (v[it][j] - mu) * rs * gv[it][j] + bt[it][j];
-                if (sizeof(T) == 2) t = (float)(bf16_t)t;       // the second LayerNorm sees the stored row
-                v[it][j] = t;
-                sum2 += t;
-            }
-            if (row_valid) stv<T, N>(y + row * D + c, v[it]);
-        }
-    }
-    const float mu2 = (HW ? half_wave_sum(sum2) : wave_sum(sum2)) / D;
-    float q2 = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) { const float d = v[it][j] - mu2; q2 += d * d; }
-        }
-    }
-    const float rs2 = rsqrtf((HW ? half_wave_sum(q2) : wave_sum(q2)) / D + eps2);
-    if (!row_valid) return;
-    if (l == 0) { mean[row] = mu; rstd[row] = rs; mean2[row] = mu2; rstd2[row] = rs2; }
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int c = (it * LPR + l) * N;
-        if (c < D) {
-            float o[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) o[j] = (v[it][j] - mu2) * rs2 * gv2[it][j] + bt2[it][j];
-            stv<T, N>(z + row * D + c, o);
-        }
-    }
+    add_layernorm_fwd_body<T, ITERS, HW, true>(x, bias, res, s_out, y, z, mean, rstd, mean2, rstd2, gamma, beta, gamma2, beta2, M, D, alpha, p, seed,
+                                               seed_dev, valid_lens, Trows, eps, eps2);
 }
 
 template <typename T, int ITERS, bool HW>
@@ -1053,7 +958,7 @@ __global__ __launch_bounds__(256) void add_layernorm2_bwd_kernel(const T *__rest
     }
     const long long r0 = (long long)blockIdx.x * rows_per_wg, r1 = min(r0 + rows_per_wg, M);
     float sn[ITERS][N], zn[ITERS][N], dn[ITERS][N], on[ITERS][N], mu_n = 0.f, rs_n = 0.f, mu2_n = 0.f, rs2_n = 0.f;
-    // optional operands always requested, from a stand-in address when absent (see add_layernorm_bwd_kernel)
+    // optional operands always requested, from a stand-in address when absent (rowpass.h, operand prologue)
     const bool has_dy = dy != nullptr, has_dout = dout != nullptr, has_vl = valid_lens != nullptr;
     const T *dy_p = has_dy ? dy : dz, *dout_p = has_dout ? dout : dz;
     const int32_t *vl_p = has_vl ? valid_lens : reinterpret_cast<const int32_t *>(mean);
@@ -1095,50 +1000,40 @@ __global__ __launch_bounds__(256) void add_layernorm2_bwd_kernel(const T *__rest
                 xh2[it][j] = h2;
                 ag2[it][j] += dzv * h2;
                 abt2[it][j] += dzv;
-                const float g2 = dzv * gm2[it][j];
-                gd[it][j] = g2;
-                t1 += g2;
-                t2 += g2 * h2;
+                gd[it][j] = ln_bwd_sums(dzv, h2, gm2[it][j], t1, t2);
                 dov[it][j] = has_dout ? on[it][j] : 0.f;
                 dyr[it][j] = (has_dy && use) ? dn[it][j] : 0.f;
             }
         }
         if (row_w + RPP < r1) request(min(row_u + RPP, r1 - 1));
-        const float n1 = (HW ? half_wave_sum(t1) : wave_sum(t1)) / D, n2 = (HW ? half_wave_sum(t2) : wave_sum(t2)) / D;
+        const float n1 = row_mean<LPR>(t1, D), n2 = row_mean<LPR>(t2, D);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 const bool use = HW ? (ok[it] && row_valid) : ok[it];
-                float dv = rs2 * (gd[it][j] - n1 - xh2[it][j] * n2) + dyr[it][j];   // gradient of y: through the second LayerNorm + the residual path
+                float dv = ln_bwd_dx(gd[it][j], xh2[it][j], rs2, n1, n2) + dyr[it][j];   // gradient of y: through the second LayerNorm + the residual path
                 if (sizeof(T) == 2) dv = (float)(bf16_t)dv;
                 dv = use ? dv : 0.f;
                 const float h = xh[it][j];
                 ag[it][j] += dv * h;
                 abt[it][j] += dv;
-                const float g = dv * gm[it][j];
-                gd[it][j] = g;
-                s1 += g;
-                s2 += g * h;
+                gd[it][j] = ln_bwd_sums(dv, h, gm[it][j], s1, s2);
             }
         }
-        const float m1 = (HW ? half_wave_sum(s1) : wave_sum(s1)) / D, m2 = (HW ? half_wave_sum(s2) : wave_sum(s2)) / D;
+        const float m1 = row_mean<LPR>(s1, D), m2 = row_mean<LPR>(s2, D);
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             if (HW ? (ok[it] && row_valid) : ok[it]) {
                 const int c = cc[it];
                 float ds[N], dxv[N];
-                const unsigned long long idx = (unsigned long long)row * D + c;
-                const unsigned km = p > 0.f ? drop_keep_mask<N>((unsigned long long)idx, dk, thr) : ~0u;
+                const unsigned km = tail_keep_mask<N>(row, D, c, p, dk, thr);
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
-                    const float d = rs * (gd[it][j] - m1 - xh[it][j] * m2) + dov[it][j];
-                    ds[j] = d;
-                    float g = live ? d * alpha : 0.f;
-                    if (p > 0.f) g = ((km >> j) & 1u) ? g * ks : 0.f;
-                    dxv[j] = g;
-                    abx[it][j] += g;
+                    ds[j] = ln_bwd_dx(gd[it][j], xh[it][j], rs, m1, m2) + dov[it][j];
+                    dxv[j] = tail_bwd_value(ds[j], p, (km >> j) & 1u, ks, live, alpha);
+                    abx[it][j] += dxv[j];
                 }
                 stv<T, N>(dres + row * D + c, ds);
                 stv<T, N>(dx + row * D + c, dxv);
@@ -1207,15 +1102,13 @@ static int pick_rows_per_wg(long long M, int min_rows) {
     // trips) unless rows are few; at least `min_rows` rows each so partial slabs stay small
     static const long long target = 1024;
     long long r = (M + target - 1) / target;
-    static const int min_env = 0;
-    if (min_env > 0) min_rows = min_env;
     if (r < min_rows) r = min_rows;
     return (int)r;
 }
 
 // Dynamic + static LDS of a launch above 64 KB (a workgroup of gfx950 may use 160 KB): the kernel's limit is raised first, as
 // csrc/frontend.hip does. `static_bytes`: the kernel's __shared__ arrays. Reached by layernorm_bwd_kernel<bf16, 64, 4> at D = 2048
-// (64 KB + 20 B), add_layernorm_bwd from D = 1368 (48 D bytes, 96 KB at 2048) and add_layernorm2_bwd from D = 824 (80 D bytes, 80 KB at 1024).
+// (64 KB + 16 B), add_layernorm_bwd from D = 1368 (48 D bytes, 96 KB at 2048) and add_layernorm2_bwd from D = 824 (80 D bytes, 80 KB at 1024).
 template <typename K> static void allow_lds(K kernel, size_t dynamic_bytes, size_t static_bytes = 0) {
     if (dynamic_bytes + static_bytes > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynamic_bytes);
@@ -1232,8 +1125,7 @@ static int launch_ln_fwd(const void *x, const float *g, const float *b, void *y,
     const int rpw = (int)std::max<long long>(4, (M + 1023) / 1024);      // wide rows: ~1024 workgroups walking rpw rows each
 #define LN_FWD_WIDE(IT)                                                                                                   \
     layernorm_fwd_wide_kernel<T, IT><<<(unsigned)((M + rpw - 1) / rpw), 256, 0, st>>>((const T *)x, g, b, (T *)y, mean, rstd, M, D, eps, slope, rpw)
-    static const int half_rows = 1;
-    if (half_rows && D <= per_wave / 2) LN_FWD(32, 1);
+    if (D <= per_wave / 2) LN_FWD(32, 1);
     else if (D <= per_wave) LN_FWD(64, 1);
     else if (D <= 2 * per_wave) LN_FWD(64, 2);
     else if (D <= 4 * per_wave) LN_FWD(64, 4);
@@ -1255,13 +1147,12 @@ static int launch_ln_bwd(const void *dy, const void *x, const float *g, const fl
     constexpr int N = Vec<T>::N;
     const int per_wave = 64 * N, per_wg = 256 * N;
 #define LN_BWD(TPR, IT)                                                                                                  \
-    allow_lds(layernorm_bwd_kernel<T, TPR, IT>, (size_t)(256 / TPR) * 2 * D * sizeof(float), 5 * sizeof(float)),         \
+    allow_lds(layernorm_bwd_kernel<T, TPR, IT>, (size_t)(256 / TPR) * 2 * D * sizeof(float), 4 * sizeof(float)),         \
     layernorm_bwd_kernel<T, TPR, IT><<<nwg, 256, (TPR <= 64 ? (size_t)(256 / TPR) * 2 * D * sizeof(float) : 0), st>>>(   \
         (const T *)dy, (const T *)x, g, b, mean, rstd, (T *)dx, part, M, D, slope, rpw, (const T *)dadd)
 #define LN_BWD_WIDE(IT)                                                                                                   \
     layernorm_bwd_wide_kernel<T, IT><<<nwg, 256, 0, st>>>((const T *)dy, (const T *)x, g, b, mean, rstd, (T *)dx, part, M, D, slope, rpw)
-    static const int half_rows = 1;
-    if (half_rows && D <= per_wave / 2) LN_BWD(32, 1);
+    if (D <= per_wave / 2) LN_BWD(32, 1);
     else if (D <= per_wave) LN_BWD(64, 1);
     else if (D <= 2 * per_wave) LN_BWD(64, 2);
     else if (D <= 4 * per_wave) LN_BWD(64, 4);
@@ -1273,6 +1164,34 @@ static int launch_ln_bwd(const void *dy, const void *x, const float *g, const fl
     else return -1;
 #undef LN_BWD_WIDE
 #undef LN_BWD
+    return 0;
+}
+
+// (io type, D) -> (T, ITERS, HW) of the add-LayerNorm family, the ladder written once: a lane holds ITERS 16-byte chunks of a row, a row
+// takes half a wave (HW: bf16, D <= 256) or one. Calls launch(RowShape<T, ITERS, HW>()); D_MAX: 2048, or 1024 for the two-LayerNorm kernels.
+template <typename T, int ITERS, bool HW> struct RowShape {
+    using type = T;
+    static constexpr int iters = ITERS;
+    static constexpr bool hw = HW;
+};
+template <int D_MAX, typename F> static int aln_dispatch(const char *name, int io_dtype, int D, F &&launch) {
+    if (io_dtype == TSASR_BF16) {
+        if (D <= 256) launch(RowShape<bf16_t, 1, true>());
+        else if (D <= 512) launch(RowShape<bf16_t, 1, false>());
+        else if (D <= 1024) launch(RowShape<bf16_t, 2, false>());
+        else if constexpr (D_MAX >= 2048) {
+            if (D <= 2048) launch(RowShape<bf16_t, 4, false>());
+            else TSASR_CHECK_ARG(false, "%s: D=%d too large", name, D);
+        } else TSASR_CHECK_ARG(false, "%s: D=%d too large", name, D);
+    } else if (io_dtype == TSASR_F32) {
+        if (D <= 256) launch(RowShape<float, 1, false>());
+        else if (D <= 512) launch(RowShape<float, 2, false>());
+        else if (D <= 1024) launch(RowShape<float, 4, false>());
+        else if constexpr (D_MAX >= 2048) {
+            if (D <= 2048) launch(RowShape<float, 8, false>());
+            else TSASR_CHECK_ARG(false, "%s: D=%d too large", name, D);
+        } else TSASR_CHECK_ARG(false, "%s: D=%d too large", name, D);
+    } else TSASR_CHECK_ARG(false, "bad io_dtype %d", io_dtype);
     return 0;
 }
 
@@ -1482,19 +1401,13 @@ int tsasr_add_layernorm_fwd(const void *x, const float *bias, const void *res, v
     TSASR_CHECK_ARG(M > 0 && D > 0 && D % 8 == 0 && p >= 0.f && p < 1.f, "tsasr_add_layernorm_fwd: bad shape/p");
     TSASR_CHECK_ARG(!valid_lens || (Trows > 0 && M % Trows == 0), "tsasr_add_layernorm_fwd: rows not a multiple of T");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((M + 3) / 4);
-#define ALN_F(TT, IT) add_layernorm_fwd_kernel<TT, IT><<<grid, 256, 0, st>>>((const TT *)x, bias, (const TT *)res, (TT *)s, (TT *)y, mean, rstd, gamma, beta, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, eps)
-    static const int half_rows = 1;
-    if (io_dtype == TSASR_BF16) {
-        if (half_rows && D <= 256)
-            add_layernorm_fwd_kernel<bf16_t, 1, true><<<(unsigned)((M + 7) / 8), 256, 0, st>>>((const bf16_t *)x, bias, (const bf16_t *)res, (bf16_t *)s, (bf16_t *)y, mean, rstd, gamma, beta, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, eps);
-        else if (D <= 512) ALN_F(bf16_t, 1); else if (D <= 1024) ALN_F(bf16_t, 2); else if (D <= 2048) ALN_F(bf16_t, 4);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm_fwd: D=%d too large", D);
-    } else if (io_dtype == TSASR_F32) {
-        if (D <= 256) ALN_F(float, 1); else if (D <= 512) ALN_F(float, 2); else if (D <= 1024) ALN_F(float, 4); else if (D <= 2048) ALN_F(float, 8);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm_fwd: D=%d too large", D);
-    } else TSASR_CHECK_ARG(false, "bad io_dtype %d", io_dtype);
-#undef ALN_F
+    const int rc = aln_dispatch<2048>("tsasr_add_layernorm_fwd", io_dtype, D, [&](auto sh) {
+        using S = decltype(sh);
+        using T = typename S::type;
+        add_layernorm_fwd_kernel<T, S::iters, S::hw><<<(unsigned)(S::hw ? (M + 7) / 8 : (M + 3) / 4), 256, 0, st>>>(
+            (const T *)x, bias, (const T *)res, (T *)s, (T *)y, mean, rstd, gamma, beta, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, eps);
+    });
+    if (rc) return rc;
     TSASR_CHECK_LAUNCH("tsasr_add_layernorm_fwd");
     return 0;
 }
@@ -1517,19 +1430,15 @@ int tsasr_add_layernorm_bwd(const void *dy, const void *dout, const void *s, con
     const int nwg = (int)((M + rpw - 1) / rpw);
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
-    const size_t lds = (size_t)12 * D * sizeof(float);
-#define ALN_B(TT, IT) allow_lds(add_layernorm_bwd_kernel<TT, IT>, lds), add_layernorm_bwd_kernel<TT, IT><<<nwg, 256, lds, st>>>((const TT *)dy, (const TT *)dout, (const TT *)s, gamma, mean, rstd, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
-    static const int half_rows = 1;
-    if (io_dtype == TSASR_BF16) {
-        if (half_rows && D <= 256)
-            add_layernorm_bwd_kernel<bf16_t, 1, true><<<nwg, 256, 2 * lds, st>>>((const bf16_t *)dy, (const bf16_t *)dout, (const bf16_t *)s, gamma, mean, rstd, (bf16_t *)dres, (bf16_t *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw);
-        else if (D <= 512) ALN_B(bf16_t, 1); else if (D <= 1024) ALN_B(bf16_t, 2); else if (D <= 2048) ALN_B(bf16_t, 4);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm_bwd: D=%d too large", D);
-    } else if (io_dtype == TSASR_F32) {
-        if (D <= 256) ALN_B(float, 1); else if (D <= 512) ALN_B(float, 2); else if (D <= 1024) ALN_B(float, 4); else if (D <= 2048) ALN_B(float, 8);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm_bwd: D=%d too large", D);
-    } else TSASR_CHECK_ARG(false, "bad io_dtype %d", io_dtype);
-#undef ALN_B
+    const int rc = aln_dispatch<2048>("tsasr_add_layernorm_bwd", io_dtype, D, [&](auto sh) {
+        using S = decltype(sh);
+        using T = typename S::type;
+        const size_t lds = (size_t)(S::hw ? 8 : 4) * 3 * D * sizeof(float);
+        allow_lds(add_layernorm_bwd_kernel<T, S::iters, S::hw>, lds);
+        add_layernorm_bwd_kernel<T, S::iters, S::hw><<<nwg, 256, lds, st>>>((const T *)dy, (const T *)dout, (const T *)s, gamma, mean, rstd, (T *)dres,
+                                                                            (T *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw);
+    });
+    if (rc) return rc;
     if (tsasr_reduce_deferring()) {
         tsasr_reduce_submit(part, dgamma, 3 * D, nwg, D, 0, st);
         tsasr_reduce_submit(part + D, dbeta, 3 * D, nwg, D, 0, st);
@@ -1550,17 +1459,14 @@ int tsasr_add_layernorm2_fwd(const void *x, const float *bias, const void *res, 
     TSASR_CHECK_ARG(M > 0 && D > 0 && D % 8 == 0 && p >= 0.f && p < 1.f, "tsasr_add_layernorm2_fwd: bad shape/p");
     TSASR_CHECK_ARG(!valid_lens || (Trows > 0 && M % Trows == 0), "tsasr_add_layernorm2_fwd: rows not a multiple of T");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((M + 3) / 4);
-#define ALN2_F(TT, IT, HWV, GR) add_layernorm2_fwd_kernel<TT, IT, HWV><<<GR, 256, 0, st>>>((const TT *)x, bias, (const TT *)res, (TT *)s, (TT *)y, (TT *)z, mean, rstd, mean2, rstd2, gamma, beta, gamma2, beta2, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, eps, eps2)
-    if (io_dtype == TSASR_BF16) {
-        if (D <= 256) ALN2_F(bf16_t, 1, true, (unsigned)((M + 7) / 8));
-        else if (D <= 512) ALN2_F(bf16_t, 1, false, grid); else if (D <= 1024) ALN2_F(bf16_t, 2, false, grid);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm2_fwd: D=%d too large", D);
-    } else if (io_dtype == TSASR_F32) {
-        if (D <= 256) ALN2_F(float, 1, false, grid); else if (D <= 512) ALN2_F(float, 2, false, grid); else if (D <= 1024) ALN2_F(float, 4, false, grid);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm2_fwd: D=%d too large", D);
-    } else TSASR_CHECK_ARG(false, "bad io_dtype %d", io_dtype);
-#undef ALN2_F
+    const int rc = aln_dispatch<1024>("tsasr_add_layernorm2_fwd", io_dtype, D, [&](auto sh) {
+        using S = decltype(sh);
+        using T = typename S::type;
+        add_layernorm2_fwd_kernel<T, S::iters, S::hw><<<(unsigned)(S::hw ? (M + 7) / 8 : (M + 3) / 4), 256, 0, st>>>(
+            (const T *)x, bias, (const T *)res, (T *)s, (T *)y, (T *)z, mean, rstd, mean2, rstd2, gamma, beta, gamma2, beta2, M, D, alpha, p, seed,
+            seed_dev, valid_lens, Trows, eps, eps2);
+    });
+    if (rc) return rc;
     TSASR_CHECK_LAUNCH("tsasr_add_layernorm2_fwd");
     return 0;
 }
@@ -1584,15 +1490,16 @@ int tsasr_add_layernorm2_bwd(const void *dz, const void *dy, const void *dout, c
     const int nwg = (int)((M + rpw - 1) / rpw);
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
-#define ALN2_B(TT, IT, HWV) allow_lds(add_layernorm2_bwd_kernel<TT, IT, HWV>, (size_t)(HWV ? 8 : 4) * 5 * D * sizeof(float)), add_layernorm2_bwd_kernel<TT, IT, HWV><<<nwg, 256, (size_t)(HWV ? 8 : 4) * 5 * D * sizeof(float), st>>>((const TT *)dz, (const TT *)dy, (const TT *)dout, (const TT *)s, gamma, beta, gamma2, mean, rstd, mean2, rstd2, (TT *)dres, (TT *)dx, part, M, D, alpha, p, seed, seed_dev, valid_lens, Trows, rpw)
-    if (io_dtype == TSASR_BF16) {
-        if (D <= 256) ALN2_B(bf16_t, 1, true); else if (D <= 512) ALN2_B(bf16_t, 1, false); else if (D <= 1024) ALN2_B(bf16_t, 2, false);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm2_bwd: D=%d too large", D);
-    } else if (io_dtype == TSASR_F32) {
-        if (D <= 256) ALN2_B(float, 1, false); else if (D <= 512) ALN2_B(float, 2, false); else if (D <= 1024) ALN2_B(float, 4, false);
-        else TSASR_CHECK_ARG(false, "tsasr_add_layernorm2_bwd: D=%d too large", D);
-    } else TSASR_CHECK_ARG(false, "bad io_dtype %d", io_dtype);
-#undef ALN2_B
+    const int rc = aln_dispatch<1024>("tsasr_add_layernorm2_bwd", io_dtype, D, [&](auto sh) {
+        using S = decltype(sh);
+        using T = typename S::type;
+        const size_t lds = (size_t)(S::hw ? 8 : 4) * 5 * D * sizeof(float);
+        allow_lds(add_layernorm2_bwd_kernel<T, S::iters, S::hw>, lds);
+        add_layernorm2_bwd_kernel<T, S::iters, S::hw><<<nwg, 256, lds, st>>>((const T *)dz, (const T *)dy, (const T *)dout, (const T *)s, gamma, beta,
+                                                                             gamma2, mean, rstd, mean2, rstd2, (T *)dres, (T *)dx, part, M, D, alpha, p,
+                                                                             seed, seed_dev, valid_lens, Trows, rpw);
+    });
+    if (rc) return rc;
     tsasr_reduce_submit(part, dgamma, 5 * D, nwg, D, 0, st);
     tsasr_reduce_submit(part + D, dbeta, 5 * D, nwg, D, 0, st);
     tsasr_reduce_submit(part + 2 * D, dbias, 5 * D, nwg, D, 0, st);

@@ -8,7 +8,7 @@
 // gemm_bf16_ring_kernel<128,64> (5.3 us at M = 8000) + add_layernorm_fwd_kernel (6.7 us): both are a launch and one round trip each,
 // and the 4 MB between them goes out to L2 / the Infinity Cache and comes back. Same arithmetic in the same order, so (s, y, mean, rstd)
 // are bit-identical to the pair (tests/test_blocks_gpu.py): the accumulators take the same v_mfma_f32_32x32x16_bf16 steps over k, are rounded to
-// bf16, and the row pass below is add_layernorm_fwd_kernel<bf16_t, 1, true>'s (two rows per wave, lane = 8 columns).
+// bf16, and the row pass below is made of the pieces of add_layernorm_fwd_kernel<bf16_t, 1, true> (csrc/rowpass.h: two rows per wave, lane = 8 columns).
 //
 // Workgroup = 256 threads = 4 waves, one 32-row x 256-column tile (250 workgroups at M = 8000): a row of the output needs all 256
 // columns, so a tile is a full row panel and every workgroup stages ALL of W (128 KiB, from L2) - affordable at K = 256 only (at K = 2048,
@@ -16,7 +16,7 @@
 // LDS-DMA as four k-tiles of [32 + 256 rows][64 k] (csrc/gemm_big.hip's layout: 128-byte rows, XOR swizzle on the source chunk), the
 // MFMAs of k-tile kt start when its 36 KiB have landed (counted s_waitcnt, one s_barrier per k-tile) while the later tiles stream in;
 // wave w owns columns [64 w, 64 w + 64). The fp32 accumulators then go through LDS (the space of k-tile 0) and leave row-major.
-#include "common.h"
+#include "rowpass.h"
 
 #define LL_BM 32
 #define LL_D 256
@@ -52,22 +52,18 @@ __global__ __launch_bounds__(256) void linear_add_layernorm_fwd_kernel(const bf1
     // thread = (wave, half hf, lane l of the half): rows 8 q + 2 wave + hf (q = 0 .. 3), columns [8 l, 8 l + 8) - the mapping of
     // add_layernorm_fwd_kernel<bf16_t, 1, true> (two rows per wave)
     const int l = lane & 31, hf = lane >> 5, c = l * 8;
-    const bool has_bias = bias != nullptr, has_vl = valid_lens != nullptr;
-    const unsigned long long *seed_p = seed_dev ? seed_dev : reinterpret_cast<const unsigned long long *>(gamma);
-    const int32_t *vl_p = has_vl ? valid_lens : reinterpret_cast<const int32_t *>(gamma);
-    const float *bias_p = has_bias ? bias : gamma;
-    const int trows = has_vl ? max(Trows, 1) : 1;
-    const unsigned long long seed_add = *seed_p;
+    const TailOperands op = tail_operands(bias, seed_dev, valid_lens, Trows, gamma);
+    const unsigned long long seed_add = *op.seed_p;
     float gv[8], bt[8], bv[8], rv[4][8];
     int vl[4];
     ld8(gamma + c, gv);
     ld8(beta + c, bt);
-    ld8(bias_p + c, bv);
+    ld8(op.bias_p + c, bv);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const long long row = min(m0 + 8 * q + 2 * wave + hf, M - 1);
         ld8(res + row * D + c, rv[q]);
-        vl[q] = vl_p[has_vl ? row / trows : 0];
+        vl[q] = op.length_of(row);
     }
 
     // ---- all four k-tiles by LDS-DMA: piece p = wave + 4 i covers LDS rows 8 p .. 8 p + 7 of the k-tile (rows 0-31: A, 32-287: W) ----
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(256) void linear_add_layernorm_fwd_kernel(const bf1
         for (int g = 0; g < 16; ++g) tile[((g & 3) + 8 * (g >> 2) + 4 * hh) * LL_LDF + wave * 64 + 32 * j + r] = acc[j][g];
     __syncthreads();
 
-    // ---- the row pass: add_layernorm_fwd_kernel<bf16_t, 1, true>, with x taken from the tile and rounded to bf16 first ----------------
+    // ---- the row pass: add_layernorm_fwd_kernel<bf16_t, 1, true>'s, with x taken from the tile and rounded to bf16 first ---------------
     if (seed_dev) seed += seed_add;
     const unsigned thr = drop_thr16(p);
     const DropKey dk = drop_key(seed);
@@ -129,33 +125,24 @@ __global__ __launch_bounds__(256) void linear_add_layernorm_fwd_kernel(const bf1
         if (!row_valid) row = M - 1;
         const float4 t_lo = *reinterpret_cast<const float4 *>(tile + rl * LL_LDF + c), t_hi = *reinterpret_cast<const float4 *>(tile + rl * LL_LDF + c + 4);
         const float xa[8] = {t_lo.x, t_lo.y, t_lo.z, t_lo.w, t_hi.x, t_hi.y, t_hi.z, t_hi.w};
-        const bool live = !has_vl || ((int)(row % trows) < vl[q]);
-        float v[8], sum = 0.f;
-        {
-            const unsigned long long idx = (unsigned long long)row * D + c;
-            const unsigned km = p > 0.f ? drop_keep_mask<8>((unsigned long long)idx, dk, thr) : ~0u;
+        const bool live = op.live(row, vl[q]);
+        const unsigned km = tail_keep_mask<8>(row, D, c, p, dk, thr);
+        float v[8], sum = 0.f, qq = 0.f;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float t = (float)(bf16_t)xa[j] + (has_bias ? bv[j] : 0.f);
-                if (p > 0.f) t = ((km >> j) & 1u) ? t * ks : 0.f;
-                t = live ? t * alpha : 0.f;
-                t += rv[q][j];
-                t = (float)(bf16_t)t;   // statistics of the STORED (rounded) row, as a separate LN would see
-                v[j] = t;
-                sum += t;
-            }
-            if (row_valid) st8(s_out + row * D + c, v);
+        for (int j = 0; j < 8; ++j) {
+            v[j] = tail_value<bf16_t>((float)(bf16_t)xa[j], bv[j], rv[q][j], op.has_bias, p, (km >> j) & 1u, ks, live, alpha);
+            sum += v[j];
         }
-        const float mu = half_wave_sum(sum) / D;
-        float qq = 0.f;
+        if (row_valid) st8(s_out + row * D + c, v);
+        const float mu = row_mean<32>(sum, D);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const float d = v[j] - mu; qq += d * d; }
-        const float rs = rsqrtf(half_wave_sum(qq) / D + eps);
+        for (int j = 0; j < 8; ++j) qq += centred_sq(v[j], mu);
+        const float rs = row_rstd<32>(qq, D, eps);
         if (row_valid) {
             if (l == 0) { mean[row] = mu; rstd[row] = rs; }
             float o[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (v[j] - mu) * rs * gv[j] + bt[j];
+            for (int j = 0; j < 8; ++j) o[j] = ln_value<bf16_t, false>(v[j], mu, rs, gv[j], bt[j]);
             st8(y + row * D + c, o);
         }
     }

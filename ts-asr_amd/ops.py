@@ -1087,38 +1087,55 @@ def lstm(x, rnn, hx=None):
 LSTM_F32_HIP = True       # (tests compare with the library module by switching it off)
 
 
+def _layernorm_fwd(x, weight, bias, eps, slope):
+    """y = LayerNorm(x) (+ LeakyReLU when slope >= 0) and what its backward needs: (y, (xc, g, b, mean, rstd))."""
+    C.require_gpu(x, weight, bias)
+    D = weight.numel()
+    xc = x.contiguous()
+    M = xc.numel() // D
+    g, b = _f32(weight).reshape(-1).contiguous(), _f32(bias).reshape(-1).contiguous()
+    y = torch.empty_like(xc)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    with prof.region("layernorm_fwd"):
+        C.check(C.lib().tsasr_layernorm_fwd(C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(y), C.ptr(mean), C.ptr(rstd), M, D, float(eps),
+                                            float(slope), C.io_dtype(xc), C.stream_ptr()), "tsasr_layernorm_fwd")
+    return y, (xc, g, b, mean, rstd)
+
+
+def _layernorm_bwd(dy, saved, slope, dadd=None):
+    """(dx, dgamma, dbeta) of _layernorm_fwd; ``dadd`` (a gradient that reached x along another path) is summed into dx by the kernel."""
+    xc, g, b, mean, rstd = saved
+    D = g.numel()
+    M = xc.numel() // D
+    dy = dy.contiguous()
+    dx = torch.empty_like(xc)
+    dg, db = torch.empty_like(g), torch.empty_like(b)
+    _keep(dg, db)
+    ws = _ws(C.lib().tsasr_layernorm_bwd_workspace_bytes(M, D), xc.device)
+    with prof.region("layernorm_bwd"):
+        if dadd is None:
+            C.check(C.lib().tsasr_layernorm_bwd(C.ptr(dy), C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(mean), C.ptr(rstd), C.ptr(dx), C.ptr(dg),
+                                                C.ptr(db), M, D, slope, C.io_dtype(xc), C.ptr(ws), ws.numel(), C.stream_ptr()),
+                    "tsasr_layernorm_bwd")
+        else:
+            C.check(C.lib().tsasr_layernorm_bwd_add(C.ptr(dy), C.ptr(dadd.contiguous()), C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(mean), C.ptr(rstd),
+                                                    C.ptr(dx), C.ptr(dg), C.ptr(db), M, D, slope, C.io_dtype(xc), C.ptr(ws), ws.numel(),
+                                                    C.stream_ptr()), "tsasr_layernorm_bwd_add")
+    return dx, dg, db
+
+
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, slope):
-        C.require_gpu(x, weight, bias)
-        D = weight.numel()
-        xc = x.contiguous()
-        M = xc.numel() // D
-        g, b = _f32(weight).reshape(-1).contiguous(), _f32(bias).reshape(-1).contiguous()
-        y = torch.empty_like(xc)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        with prof.region("layernorm_fwd"):
-            C.check(C.lib().tsasr_layernorm_fwd(C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(y), C.ptr(mean), C.ptr(rstd), M, D, float(eps),
-                                                float(slope), C.io_dtype(xc), C.stream_ptr()), "tsasr_layernorm_fwd")
-        ctx.save_for_backward(xc, g, b, mean, rstd)
+        y, saved = _layernorm_fwd(x, weight, bias, eps, slope)
+        ctx.save_for_backward(*saved)
         ctx.slope, ctx.params = float(slope), (weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        xc, g, b, mean, rstd = ctx.saved_tensors
-        D = g.numel()
-        M = xc.numel() // D
-        dy = dy.contiguous()
-        dx = torch.empty_like(xc)
-        dg, db = torch.empty_like(g), torch.empty_like(b)
-        _keep(dg, db)
-        ws = _ws(C.lib().tsasr_layernorm_bwd_workspace_bytes(M, D), xc.device)
-        with prof.region("layernorm_bwd"):
-            C.check(C.lib().tsasr_layernorm_bwd(C.ptr(dy), C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(mean), C.ptr(rstd), C.ptr(dx), C.ptr(dg),
-                                                C.ptr(db), M, D, ctx.slope, C.io_dtype(xc), C.ptr(ws), ws.numel(), C.stream_ptr()),
-                    "tsasr_layernorm_bwd")
+        dx, dg, db = _layernorm_bwd(dy, ctx.saved_tensors, ctx.slope)
         return dx, _pgrad(ctx.params[0], dg), _pgrad(ctx.params[1], db), None, None
 
 
@@ -1128,43 +1145,17 @@ class _LayerNormResFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
-        C.require_gpu(x, weight, bias)
         ctx.set_materialize_grads(False)
-        D = weight.numel()
-        xc = x.contiguous()
-        M = xc.numel() // D
-        g, b = _f32(weight).reshape(-1).contiguous(), _f32(bias).reshape(-1).contiguous()
-        y = torch.empty_like(xc)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        with prof.region("layernorm_fwd"):
-            C.check(C.lib().tsasr_layernorm_fwd(C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(y), C.ptr(mean), C.ptr(rstd), M, D, float(eps),
-                                                -1.0, C.io_dtype(xc), C.stream_ptr()), "tsasr_layernorm_fwd")
-        ctx.save_for_backward(xc, g, b, mean, rstd)
+        y, saved = _layernorm_fwd(x, weight, bias, eps, -1.0)
+        ctx.save_for_backward(*saved)
         ctx.params = (weight, bias)
-        return y, xc.view_as(xc)
+        return y, saved[0].view_as(saved[0])
 
     @staticmethod
     def backward(ctx, dy, dres):
-        xc, g, b, mean, rstd = ctx.saved_tensors
         if dy is None:
             return dres, None, None, None
-        D = g.numel()
-        M = xc.numel() // D
-        dy = dy.contiguous()
-        dx = torch.empty_like(xc)
-        dg, db = torch.empty_like(g), torch.empty_like(b)
-        _keep(dg, db)
-        ws = _ws(C.lib().tsasr_layernorm_bwd_workspace_bytes(M, D), xc.device)
-        with prof.region("layernorm_bwd"):
-            if dres is None:
-                C.check(C.lib().tsasr_layernorm_bwd(C.ptr(dy), C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(mean), C.ptr(rstd), C.ptr(dx), C.ptr(dg),
-                                                    C.ptr(db), M, D, -1.0, C.io_dtype(xc), C.ptr(ws), ws.numel(), C.stream_ptr()),
-                        "tsasr_layernorm_bwd")
-            else:
-                C.check(C.lib().tsasr_layernorm_bwd_add(C.ptr(dy), C.ptr(dres.contiguous()), C.ptr(xc), C.ptr(g), C.ptr(b), C.ptr(mean), C.ptr(rstd),
-                                                        C.ptr(dx), C.ptr(dg), C.ptr(db), M, D, -1.0, C.io_dtype(xc), C.ptr(ws), ws.numel(),
-                                                        C.stream_ptr()), "tsasr_layernorm_bwd_add")
+        dx, dg, db = _layernorm_bwd(dy, ctx.saved_tensors, -1.0, dres)
         return dx, _pgrad(ctx.params[0], dg), _pgrad(ctx.params[1], db), None
 
 
@@ -1177,10 +1168,6 @@ def layer_norm(x, weight, bias, eps, act_slope=None):
     """LayerNorm over the trailing dims covered by ``weight`` (1-D model width or the front-end's [F, C]),
     optionally fused with the LeakyReLU that follows it."""
     return _LayerNormFn.apply(x, weight, bias, eps, -1.0 if act_slope is None else act_slope)
-
-
-def layer_norm2(x, weight, bias, eps, act_slope=None):
-    return layer_norm(x, weight, bias, eps, act_slope)
 
 
 class _BiasActDropoutFn(torch.autograd.Function):
@@ -1278,6 +1265,28 @@ def dropout_add(x, bias=None, res=None, alpha=1.0, p=0.0, training=False, valid_
     return _DropoutAddFn.apply(x, bias, res, alpha, p, next_seed() if p > 0 else 0, valid_lens, trows, p2, next_seed() if p2 > 0 else 0)
 
 
+def _add_layernorm_bwd(ds_in, dy, s_out, g, mean, rstd, valid_lens, alpha, p, seed, trows, has_bias):
+    """tsasr_add_layernorm_bwd for the (ds_in, dy) that reach the (s, y) of an add-LayerNorm forward: (dres, dx, dgamma, dbeta, dbias)."""
+    D = s_out.shape[-1]
+    M = s_out.numel() // D
+    if dy is None:                                        # y unused downstream: only the residual tail has a gradient
+        dy = torch.zeros_like(s_out)
+    dy = dy.contiguous()
+    ds_in = None if ds_in is None else ds_in.contiguous()
+    dres, dx = torch.empty_like(s_out), torch.empty_like(s_out)
+    dg = torch.empty(D, dtype=torch.float32, device=s_out.device)
+    dbt = torch.empty_like(dg)
+    db = torch.empty_like(dg) if has_bias else None
+    _keep(dg, dbt, db)
+    ws = _ws(C.lib().tsasr_add_layernorm_bwd_workspace_bytes(M, D), s_out.device)
+    with prof.region("add_layernorm_bwd"):
+        C.check(C.lib().tsasr_add_layernorm_bwd(C.ptr(dy), C.ptr(ds_in), C.ptr(s_out), C.ptr(g), C.ptr(mean), C.ptr(rstd), C.ptr(dres),
+                                                C.ptr(dx), C.ptr(dg), C.ptr(dbt), C.ptr(db), M, D, alpha, p, seed,
+                                                C.ptr(seed_state(s_out.device)), C.ptr(valid_lens), trows, C.io_dtype(s_out),
+                                                C.ptr(ws), ws.numel(), C.stream_ptr()), "tsasr_add_layernorm_bwd")
+    return dres, dx, dg, dbt, db
+
+
 class _AddLayerNormFn(torch.autograd.Function):
     """(s, y) = (res + alpha*timemask(dropout(x + bias)), LayerNorm(s)) - the seam between two Conformer sub-blocks in one pass;
     the backward folds the residual-path gradient, the LayerNorm backward and the dropout/mask backward into one kernel."""
@@ -1307,23 +1316,7 @@ class _AddLayerNormFn(torch.autograd.Function):
     def backward(ctx, ds_in, dy):
         s_out, g, mean, rstd, valid_lens = ctx.saved_tensors
         alpha, p, seed, trows, bias_param, gamma, beta = ctx.cfg
-        D = s_out.shape[-1]
-        M = s_out.numel() // D
-        if dy is None:                                        # y unused downstream: only the residual tail has a gradient
-            dy = torch.zeros_like(s_out)
-        dy = dy.contiguous()
-        ds_in = None if ds_in is None else ds_in.contiguous()
-        dres, dx = torch.empty_like(s_out), torch.empty_like(s_out)
-        dg = torch.empty(D, dtype=torch.float32, device=s_out.device)
-        dbt = torch.empty_like(dg)
-        db = torch.empty_like(dg) if bias_param is not None else None
-        _keep(dg, dbt, db)
-        ws = _ws(C.lib().tsasr_add_layernorm_bwd_workspace_bytes(M, D), s_out.device)
-        with prof.region("add_layernorm_bwd"):
-            C.check(C.lib().tsasr_add_layernorm_bwd(C.ptr(dy), C.ptr(ds_in), C.ptr(s_out), C.ptr(g), C.ptr(mean), C.ptr(rstd), C.ptr(dres),
-                                                    C.ptr(dx), C.ptr(dg), C.ptr(dbt), C.ptr(db), M, D, alpha, p, seed,
-                                                    C.ptr(seed_state(s_out.device)), C.ptr(valid_lens), trows, C.io_dtype(s_out),
-                                                    C.ptr(ws), ws.numel(), C.stream_ptr()), "tsasr_add_layernorm_bwd")
+        dres, dx, dg, dbt, db = _add_layernorm_bwd(ds_in, dy, s_out, g, mean, rstd, valid_lens, alpha, p, seed, trows, bias_param is not None)
         return (dx, (_pgrad(bias_param, db) if bias_param is not None else None), dres, _pgrad(gamma, dg), _pgrad(beta, dbt),
                 None, None, None, None, None, None)
 
@@ -1373,24 +1366,8 @@ class _LinearAddLayerNormFn(torch.autograd.Function):
     def backward(ctx, ds_in, dy):
         x2, w16, s_out, g, mean, rstd, valid_lens = ctx.saved_tensors
         alpha, p, seed, trows, bias_param, gamma, beta, weight, xshape = ctx.cfg
-        D = s_out.shape[-1]
-        M = s_out.numel() // D
-        if dy is None:
-            dy = torch.zeros_like(s_out)
-        dy = dy.contiguous()
-        ds_in = None if ds_in is None else ds_in.contiguous()
-        dres, dx = torch.empty_like(s_out), torch.empty_like(s_out)
-        dg = torch.empty(D, dtype=torch.float32, device=s_out.device)
-        dbt = torch.empty_like(dg)
-        db = torch.empty_like(dg) if bias_param is not None else None
-        _keep(dg, dbt, db)
-        ws = _ws(C.lib().tsasr_add_layernorm_bwd_workspace_bytes(M, D), s_out.device)
-        with prof.region("add_layernorm_bwd"):
-            C.check(C.lib().tsasr_add_layernorm_bwd(C.ptr(dy), C.ptr(ds_in), C.ptr(s_out), C.ptr(g), C.ptr(mean), C.ptr(rstd), C.ptr(dres),
-                                                    C.ptr(dx), C.ptr(dg), C.ptr(dbt), C.ptr(db), M, D, alpha, p, seed,
-                                                    C.ptr(seed_state(s_out.device)), C.ptr(valid_lens), trows, C.io_dtype(s_out),
-                                                    C.ptr(ws), ws.numel(), C.stream_ptr()), "tsasr_add_layernorm_bwd")
-        N, K = weight.shape[0], weight.shape[1]
+        dres, dx, dg, dbt, db = _add_layernorm_bwd(ds_in, dy, s_out, g, mean, rstd, valid_lens, alpha, p, seed, trows, bias_param is not None)
+        M, N, K = x2.shape[0], weight.shape[0], weight.shape[1]
         dx2 = dx.view(M, N)
         dxin = _dgrad(dx2, weight, w16, M, N, K).view(xshape) if ctx.needs_input_grad[0] else None
         dw = None
