@@ -550,6 +550,26 @@ int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih
                              int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
                              double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
 
+/* The two searches with emission frames: the arguments of their untimed twins plus frames int32 [B,nbest,Lmax], frames[b,r,i] = index of
+ * the encoder frame whose joint emitted hyps[b,r,i], absolute from the start of the utterance or stream, written for the first
+ * min(len, Lmax) tokens. Frames are non-decreasing along a hypothesis (several tokens may share a frame); the offline search decodes
+ * padded frames too, so a frame may lie past an utterance's valid length. hyps, lens, scores and status are the bits of the untimed
+ * calls. The workspace has its own layout, the untimed one plus one int per tree node: tsasr_beam_search_timed_workspace_bytes =
+ * B * (untimed per-utterance bytes + align16(4 (1 + (max_frames + 1) beam + cap))), 0 for a non-positive argument. A timed stream
+ * resumes only a workspace that timed calls started (zeroed = start of the stream) and continued; a zero count leaves the state alone
+ * and reads the n-best and their frames out again. The kernel takes 4 cap bytes more LDS than the untimed one. */
+size_t tsasr_beam_search_timed_workspace_bytes(int B, int T, int H, int J, int beam, int cap);
+int tsasr_beam_search_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                            const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                            size_t workspace_bytes, int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V,
+                            int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype,
+                            int wdtype, void *stream, int *frames);
+int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                                   const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                                   size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B,
+                                   int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
+                                   double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames);
+
 /* ------------------------------------------------------------------------------------------
  * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:
  * 124-334, Kaldi's compute-wer order: the substitution / match only if strictly cheaper than both others, else the deletion if strictly

@@ -8,8 +8,14 @@ reported per utterance. Expansions per frame and predictor steps computed come f
 the device's own inputs (count only; the counts do not depend on which route ran).
 
     python tools/beam_bench.py [--reps 5] [--host-utts 2] [--frames 250]
+    python tools/beam_bench.py --times [--reps 50] [--ab-lib OTHER.so]     # the timed launch (tsasr_beam_search_timed) beside the untimed one
+
+--times: the launch alone, without the host read-back: the stream is pre-loaded, events sit around each launch, the two forms
+alternate, median of --reps after warm-up (the method of profiles/align_notes.md); B = 32, T' = --frames, beam 15, bf16 and fp32.
+--ab-lib: the untimed launch of another build of the library (e.g. the parent commit's) takes part in the same loop.
 """
 import argparse
+import ctypes
 import importlib
 import json
 import os
@@ -59,6 +65,71 @@ def counts(s, enc):
     return exp, len(memo), enc.shape[1]
 
 
+def times_bench(args):
+    """Timed against untimed launch on the TEST shape; prints one JSON line per dtype."""
+    dec = importlib.import_module("ts-asr_amd.decoders")
+    ops = importlib.import_module("ts-asr_amd.ops")
+    capi = importlib.import_module("ts-asr_amd._capi")
+    lib, P = capi.lib(), capi.ptr
+    results = []
+    for dtype in args.dtypes.split(","):
+        brain, h = entry._config1_brain("cuda:0", dtype, joint_dim=640, decoder_neurons=512)
+        brain._setup_dtype()
+        m = brain.modules
+        dt = torch.float32 if dtype == "fp32" else torch.bfloat16
+        g = np.load(os.path.join(ROOT, "tests", "golden", "c1_chain_cat.npz"))["enc_proj"]
+        B, T, beam, nbest, cap = 32, args.frames, 15, 5, dec.BEAM_CAP
+        enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (B, T, 640), float(np.std(g)))).to("cuda:0", dt)
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] += 3.0
+            s = dec.TransducerBeamSearcher([m.embedding, m.decoder, m.decoder_proj], m.joiner, [m.transducer_head], blank_id=0,
+                                           beam_size=beam, nbest=nbest, state_beam=2.3, expand_beam=2.3)
+            table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
+        H, J, E, V, Lmax = mats[1].shape[1], 640, table.shape[1], mats[3].shape[0], 2 * T + 16
+        ws = torch.zeros(ops.beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap), dtype=torch.uint8, device="cuda:0")
+        hyps, frames = (torch.empty(B, nbest, Lmax, dtype=torch.int32, device="cuda:0") for _ in range(2))
+        lens = torch.empty(B, nbest, dtype=torch.int32, device="cuda:0")
+        scores = torch.empty(B, nbest, dtype=torch.float64, device="cuda:0")
+        status = torch.empty(B, dtype=torch.int32, device="cuda:0")
+        head = (P(enc), P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]), P(b_head), P(ws), ws.numel(),
+                P(hyps), P(lens), P(scores), P(status), B, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01, capi.io_dtype(enc), wdt)
+
+        forms = {"untimed": lambda: capi.check(lib.tsasr_beam_search(*head, capi.stream_ptr()), "tsasr_beam_search"),
+                 "timed": lambda: capi.check(lib.tsasr_beam_search_timed(*head, capi.stream_ptr(), P(frames)), "tsasr_beam_search_timed")}
+        if args.ab_lib:                                      # the untimed launch of another build of the library, in the same loop
+            other = ctypes.CDLL(os.path.abspath(args.ab_lib)).tsasr_beam_search
+            other.restype, other.argtypes = lib.tsasr_beam_search.restype, lib.tsasr_beam_search.argtypes
+            forms["untimed_ab"] = lambda: capi.check(other(*head, capi.stream_ptr()), "tsasr_beam_search (--ab-lib)")
+        names = list(forms)
+        ms = {n: [] for n in names}
+        fill = torch.empty(256 << 20, dtype=torch.uint8, device="cuda:0")
+        for n in names * 2:                                  # warm-up
+            forms[n]()
+        torch.cuda.synchronize()
+        for rep in range(args.reps):
+            order = names[rep % len(names):] + names[:rep % len(names)]
+            for n in (order if (rep // len(names)) % 2 == 0 else order[::-1]):      # no form always follows the same other one
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                fill.fill_(rep % 200)                        # the stream is busy while the events and the launch are enqueued
+                fill.fill_(rep % 200 + 1)
+                e0.record()
+                forms[n]()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[n].append(e0.elapsed_time(e1))
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] -= 3.0
+        med = {n: float(np.median(v)) for n, v in ms.items()}
+        spread = lambda v: round(float(np.percentile(v, 90) - np.percentile(v, 10)), 3)  # noqa: E731
+        r = dict(dtype=dtype, B=B, T=T, beam=beam, reps=args.reps, ratio=round(med["timed"] / med["untimed"], 4),
+                 stopped_utts=int((status != 0).sum()))
+        for n in names:
+            r[n + "_ms"], r[n + "_p10_p90_ms"] = round(med[n], 3), spread(ms[n])
+        print(json.dumps(r), flush=True)
+        results.append(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -66,7 +137,11 @@ def main():
     ap.add_argument("--frames", type=int, default=250)
     ap.add_argument("--beams", default="4,15")
     ap.add_argument("--dtypes", default="fp32,bf16")
+    ap.add_argument("--times", action="store_true", help="time the timed launch beside the untimed one (launch only)")
+    ap.add_argument("--ab-lib", default=None, help="--times: also time tsasr_beam_search of this other build of the library")
     args = ap.parse_args()
+    if args.times:
+        return times_bench(args)
     dec = importlib.import_module("ts-asr_amd.decoders")
     ops = importlib.import_module("ts-asr_amd.ops")
     results = []

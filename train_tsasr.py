@@ -16,6 +16,9 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
   --align_file PATH : after the TEST stage the test batches are force-aligned to their reference transcripts (TSASR.align_batch: the best
         path through the RNN-T lattice) and a CTM is written there, "<utt> 1 <start> <dur> <word>" per word; without a tokenizer one
         line per token with the token id as the word. Works with --synthetic N.
+  --hyp_ctm PATH : the TEST stage decodes with TransducerBeamSearcher.forward_timed (the same hypotheses, plus the encoder frame that
+        emitted each token) and a CTM of the RECOGNISED words is written there after the stage, in the format and by the rules of
+        --align_file. Like --align_file, rank 0 writes, and with several processes only what its own process decoded.
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
 import importlib
 import os
@@ -34,7 +37,7 @@ tsasr = importlib.import_module(PKG + ".recipes.tsasr")
 
 EXTRA = {"synthetic": 0, "syn_batch": 8, "syn_seconds": 4.0, "syn_enroll_seconds": 2.0, "syn_tokens": 24, "hip_graph": False,
          "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None,
-         "align_file": None}
+         "align_file": None, "hyp_ctm": None}
 
 
 def synthetic_loader(n_batches, hparams, opts, seed, device):
@@ -64,12 +67,30 @@ def write_alignments(brain, batches, hparams, path):
     for n, batch in enumerate(batches):
         frames, _ = align.fetch(*brain.align_batch(batch))
         refs = batch.tokens.data.tolist()      # whole rows: frames are -1 beyond an utterance's tokens, the spans stop there
-        utts = getattr(batch, "id", None) or [f"utt{len(ids) + k}" for k in range(len(refs))]
-        if len(set(utts) & set(ids)):      # synthetic batches reuse their ids: keep the CTM's utterance names apart
-            utts = [f"{u}-{n}" for u in utts]
-        for utt, fr, ref in zip(utts, frames, refs):
+        for utt, fr, ref in zip(_ctm_names(getattr(batch, "id", None), ids, n, len(refs)), frames, refs):
             ids.append(utt)
             spans.append(align.word_spans(fr, ref, pieces, fs) if pieces is not None else align.token_spans(fr, ref, fs))
+    return align.write_ctm(path, ids, spans)
+
+
+def _ctm_names(utts, ids, n, count):
+    """Utterance names of batch ``n`` for a CTM: the batch's ids (numbered when it has none), kept apart from those already in ``ids``
+    (synthetic batches reuse theirs)."""
+    utts = utts or [f"utt{len(ids) + k}" for k in range(count)]
+    return [f"{u}-{n}" for u in utts] if len(set(utts) & set(ids)) else list(utts)
+
+
+def write_hyp_ctm(brain, hparams, path):
+    """One CTM of the hypotheses the TEST stage recognised (brain.hyp_times, kept by compute_forward under hparams.hyp_ctm): word spans
+    from the emission frame of each token; returns the number of lines."""
+    align = importlib.import_module(PKG + ".align")
+    fs = align.frame_seconds(hparams)
+    pieces = getattr(getattr(brain, "tokenizer", None), "pieces", None)
+    ids, spans = [], []
+    for n, (utts, hyps, frames) in enumerate(getattr(brain, "hyp_times", [])):
+        for utt, hyp, fr in zip(_ctm_names(utts, ids, n, len(hyps)), hyps, frames):
+            ids.append(utt)
+            spans.append(align.word_spans(fr, hyp, pieces, fs) if pieces is not None else align.token_spans(fr, hyp, fs))
     return align.write_ctm(path, ids, spans)
 
 
@@ -80,6 +101,8 @@ def main(argv=None):
         hparams = hp_mod.load_hyperpyyaml(f, overrides)
     if opts["wer_file"]:
         hparams["wer_file"] = str(opts["wer_file"])
+    if opts["hyp_ctm"]:
+        hparams["hyp_ctm"] = str(opts["hyp_ctm"])
     dp.ddp_init_group(run_opts)                                           # one process per GPU (SB/utils/distributed.py:123-201)
     brain = tsasr.TSASR(hparams["modules"], hparams["opt_class"], hparams, run_opts)
     if opts["hip_graph"]:
@@ -104,6 +127,8 @@ def main(argv=None):
         result["test_stats"] = getattr(brain, "test_stats", None)
         if opts["align_file"] and rank == 0:
             result["align_lines"] = write_alignments(brain, test, hparams, str(opts["align_file"]))
+        if opts["hyp_ctm"] and rank == 0:
+            result["hyp_ctm_lines"] = write_hyp_ctm(brain, hparams, str(opts["hyp_ctm"]))
     if valid is not None:
         result["valid_stats"] = getattr(brain, "valid_stats", None)
     if rank == 0:

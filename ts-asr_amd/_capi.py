@@ -144,6 +144,9 @@ _PROTOS = {
     "tsasr_beam_search_workspace_bytes": (c_size_t, [c_int] * 6),
     "tsasr_beam_search": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
     "tsasr_beam_search_stream": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
+    "tsasr_beam_search_timed_workspace_bytes": (c_size_t, [c_int] * 6),
+    "tsasr_beam_search_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
+    "tsasr_beam_search_stream_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
     "tsasr_edit_distance_workspace_bytes": (c_size_t, [c_int, c_ll]),
     "tsasr_edit_distance": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_ll] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),

@@ -206,6 +206,15 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
 // end of a frame the new nodes on the beam's paths are promoted into the tree (in creation order), all other new nodes and every slot
 // not held by the beam are recycled. Workspace of one utterance: header (16 ints: primed, status, nbeam, tree size, frames) + beam
 // entries | tree | slots; a zeroed header is the start of a stream.
+//
+// TIMES (tsasr_beam_search_timed / _stream_timed): the search also reports the encoder frame at which each token was emitted. The search
+// never merges paths, so a tree node is one concrete path and its emission frame is one value: an extension appended to A at loop index t
+// records (frames of this stream decoded by earlier calls) + t in Afrm, beside Atok / Alen; the promotion step copies it into a node-frame
+// array parallel to the tree (after the slots in the workspace: the timed layout is the untimed one plus align16(4 * nodes) bytes per
+// utterance), and the n-best read-out walks it up the tree beside the tokens. Nothing the search decides reads a frame: hypotheses and
+// scores are those of the untimed form, bit for bit. The frames of a stream are absolute only if its header was zeroed as a whole at the
+// start: the stream form takes "frames decoded so far" from hdr[4] whether or not the stream is primed, so hdr[0] == 0 over a stale
+// hdr[4] would shift every frame of the stream by that stale count (the untimed form only ever adds to the word).
 constexpr int BEAM_THREADS = 1024;
 constexpr int BEAM_MAXK = 64;            // beam_size <= V <= 63
 
@@ -229,6 +238,10 @@ __host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam,
     L.per_utt = L.hdr + L.tree + (size_t)L.ns * (size_t)(J + 2 * H) * sizeof(float);
     return L;
 }
+// TIMES: the node-frame array (one int per tree node) follows the untimed layout of each utterance
+__host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times) {
+    return L.per_utt + (times ? beam_align16(sizeof(int) * (size_t)L.nn) : 0);
+}
 
 struct BeamArgs {
     const void *enc;            // [B, T, J] io dtype (T = frames of this call)
@@ -248,6 +261,7 @@ struct BeamArgs {
     int B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames;
     double state_beam, expand_beam;
     float slope;
+    int *frames;                // TIMES: [B, nbest, Lmax] emission frame of each token of hyps (absolute in the stream)
 };
 
 // (key, index) of the larger key; equal keys: the lower index (Python max: the first maximal entry)
@@ -257,7 +271,7 @@ __device__ __forceinline__ void beam_argmax_step(double &k, int &i, int mask) {
     if (k2 > k || (k2 == k && i2 < i)) { k = k2; i = i2; }
 }
 
-template <typename T, typename WT>
+template <typename T, typename WT, bool TIMES>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArgs A) {
     extern __shared__ __attribute__((aligned(16))) float bsm[];
     const int H = A.H, J = A.J, cap = A.cap;
@@ -265,6 +279,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
     double *Alp = reinterpret_cast<double *>(lg + 64), *Akey = Alp + cap;
     int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
         *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
+    int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
     __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
     __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
     __shared__ float s_lp[64];
@@ -274,16 +289,18 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
     __shared__ int s_ctl[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap);
-    unsigned char *wsu = A.ws + (size_t)b * L.per_utt;
+    unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES);
     int *hdr = reinterpret_cast<int *>(wsu);
     BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
     int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
     float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
+    int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
     const int SW = J + 2 * H;                                // floats per slot: pn | h | c
     const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
     const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
     const bool fresh = A.n_valid == nullptr;
     const int tend = fresh ? A.T : min(max(A.n_valid[b], 0), A.T);
+    const int fbase = (TIMES && !fresh) ? hdr[4] : 0;        // frames of this stream decoded before this call (written after the last frame)
 
     if (tid == 0) {
         const bool primed = !fresh && hdr[0] != 0;
@@ -437,6 +454,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
                             Aslot[nA] = -1;
                             Anode[nA] = -1;
                             Aflag[nA] = 1;
+                            if (TIMES) Afrm[nA] = fbase + t;
                             ++nA;
                         }
                     }
@@ -471,7 +489,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             for (int i = lane; i < nA; i += 64)
-                if (Aflag[i] & 2) tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
+                if (Aflag[i] & 2) {
+                    tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
+                    if (TIMES) nfrm[Anode[i]] = Afrm[i];
+                }
             if (lane == 0) s_ctl[7] = base;
         }
         __syncthreads();
@@ -527,9 +548,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
         if (lane == 0 && e >= 0) {
             int node = Anode[e];
             int *out = A.hyps + ((size_t)b * A.nbest + r) * A.Lmax;
+            int *fout = TIMES ? A.frames + ((size_t)b * A.nbest + r) * A.Lmax : nullptr;
             for (int d = Alen[e] - 2; d >= 0 && node > 0; --d) {
                 const int2 nd = tree[node];
-                if (d < A.Lmax) out[d] = nd.x;
+                if (d < A.Lmax) {
+                    out[d] = nd.x;
+                    if (TIMES) fout[d] = nfrm[node];
+                }
                 node = nd.y;
             }
         }
@@ -608,28 +633,39 @@ size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, i
     return (size_t)B * beam_layout(T, H, J, beam, cap).per_utt;
 }
 
+static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times) {
+    if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
+    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap), times);
+}
+
+/* The timed searches' workspace: the untimed layout of each utterance plus one int per tree node (align16(4 (1 + (T + 1) beam + cap))). */
+size_t tsasr_beam_search_timed_workspace_bytes(int B, int T, int H, int J, int beam, int cap) {
+    return beam_workspace_bytes(B, T, H, J, beam, cap, true);
+}
+
 static int beam_launch(const char *name, const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih,
                        const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                       size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                       int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                       double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status, "%s: null pointer", name);
+                       size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores,
+                       int *status, int B, int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
+                       double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
+    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status && (frames || !times),
+                    "%s: null pointer", name);
     TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
                     "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
     TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
     TSASR_CHECK_ARG(beam >= 2 && beam <= V && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
                     "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
     TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
-    const size_t need = tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap);
+    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times);
     TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
-    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + 6 * sizeof(int));
+    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int));
     TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
     BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
-               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope};
+               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope, frames};
     hipStream_t st = (hipStream_t)stream;
 #define BEAM(TT, WW)                                                                                                            \
     {                                                                                                                           \
-        auto kern = beam_search_kernel<TT, WW>;                                                                                 \
+        auto kern = times ? beam_search_kernel<TT, WW, true> : beam_search_kernel<TT, WW, false>;                               \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         kern<<<B, BEAM_THREADS, lds, st>>>(a);                                                                                  \
     }
@@ -650,8 +686,8 @@ int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const
                       int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
                       int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
     return beam_launch("tsasr_beam_search", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
-                       nullptr, hyps, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam, expand_beam, slope,
-                       io_dtype, wdtype, stream);
+                       nullptr, hyps, nullptr, false, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
+                       expand_beam, slope, io_dtype, wdtype, stream);
 }
 
 /* The same search over one chunk of a stream: the beam, token tree and predictor slots are resumed from the workspace (laid out for
@@ -664,8 +700,36 @@ int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih
                              double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
     TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream: null n_valid");
     return beam_launch("tsasr_beam_search_stream", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
-                       workspace_bytes, n_valid, hyps, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap, Lmax,
-                       state_beam, expand_beam, slope, io_dtype, wdtype, stream);
+                       workspace_bytes, n_valid, hyps, nullptr, false, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
+                       cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
+}
+
+/* tsasr_beam_search that also reports when each token was emitted: frames int32 [B,nbest,Lmax], frames[b,r,i] = index of the encoder
+ * frame whose joint emitted hyps[b,r,i] (non-decreasing along a hypothesis; several tokens may share a frame), written for the first
+ * min(len, Lmax) tokens. workspace >= tsasr_beam_search_timed_workspace_bytes(...). Hypotheses, lengths, scores and status are the
+ * bits of tsasr_beam_search. */
+int tsasr_beam_search_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                            const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                            size_t workspace_bytes, int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V,
+                            int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype,
+                            int wdtype, void *stream, int *frames) {
+    return beam_launch("tsasr_beam_search_timed", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+                       nullptr, hyps, frames, true, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
+                       expand_beam, slope, io_dtype, wdtype, stream);
+}
+
+/* tsasr_beam_search_stream with frames (absolute from the start of the stream). The workspace has the timed layout and must have been
+ * started (zeroed, or by tsasr_beam_search_timed) and continued by timed calls only: an untimed call records no frames for the nodes it
+ * adds. A zero count leaves the state alone and reads the n-best and their frames out again. */
+int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                                   const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                                   size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B,
+                                   int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
+                                   double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames) {
+    TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream_timed: null n_valid");
+    return beam_launch("tsasr_beam_search_stream_timed", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
+                       workspace_bytes, n_valid, hyps, frames, true, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
+                       cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,12 @@ no LM fusion). For the recipes' networks one launch of csrc/search.hip decodes t
 reference's list order, one predictor step per hypothesis node); utterances that need more than ``cap`` hypotheses in a frame, and
 every other network shape, run the host loop: host-side hypothesis bookkeeping exactly as specified there (SURVEY.md section 8f
 row f1), device-side predictor / joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
+
+Timestamps (forward_timed, greedy_stream / beam_stream with return_frames=True): frames[i] = index of the encoder frame whose joint
+emitted token i, absolute from the start of the utterance or stream. Greedy emits at most one symbol per frame, so the frame is the
+token's column in the kernel's ``preds``; the beam search never merges paths, so each hypothesis carries one frame list (the device
+search records it per tree node, tsasr_beam_search_timed; the host loop carries it with the hypothesis). Seconds and word spans:
+align.frame_seconds / align.word_spans.
 """
 import os
 import warnings
@@ -35,6 +41,28 @@ class TransducerBeamSearcher(torch.nn.Module):
         if self.beam_size <= 1:
             return self.transducer_greedy_decode(tn_output)
         return self.transducer_beam_search_decode(tn_output)
+
+    def forward_timed(self, tn_output):
+        """forward's four values (the same lists, the same score bits) and then ``frames`` and ``nbest_frames``: frames[b][i] is the
+        encoder frame that emitted hyps[b][i], nbest_frames[b][r][i] that of nbest_hyps[b][r][i] (None for greedy). Every frame of
+        tn_output is decoded, padding included, so a frame may lie past an utterance's valid length."""
+        if self.beam_size <= 1:
+            return self.transducer_greedy_decode(tn_output, timed=True)
+        return self.transducer_beam_search_decode(tn_output, timed=True)
+
+    @staticmethod
+    def _unpack_preds(preds, base=None):
+        """preds [B,T] (symbol emitted at each frame or -1) -> (symbol lists, frame lists) with one device-to-host copy; ``base`` int
+        [B] on the device = frames decoded before column 0 (travels as an extra column)."""
+        if base is not None:
+            preds = torch.cat([preds, base.to(preds.dtype)[:, None]], dim=1)
+        rows = preds.cpu()
+        off = [0] * rows.shape[0] if base is None else rows[:, -1].tolist()
+        if base is not None:
+            rows = rows[:, :-1]
+        hyps = [[int(v) for v in row[row >= 0]] for row in rows]
+        frames = [[int(t) + int(o) for t in torch.nonzero(row >= 0).flatten()] for row, o in zip(rows, off)]
+        return hyps, frames
 
     def _pn(self, tok, hidden):
         emb, dec, proj = self.decode_network_lst
@@ -72,7 +100,7 @@ class TransducerBeamSearcher(torch.nn.Module):
         return bool(ok)
 
     @torch.no_grad()
-    def _greedy_on_device(self, tn_output):
+    def _greedy_on_device(self, tn_output, timed=False):
         from . import _capi as C
         B, T, J = tn_output.shape
         enc = tn_output.contiguous()
@@ -84,6 +112,9 @@ class TransducerBeamSearcher(torch.nn.Module):
                                             C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, rnn.hidden_size,
                                             table.shape[1], mats[3].shape[0], int(self.blank_id), float(self.tjoint.nonlinearity.negative_slope),
                                             C.io_dtype(enc), wdt, C.stream_ptr()), "tsasr_greedy_decode")
+        if timed:
+            hyps, frames = self._unpack_preds(preds)
+            return hyps, logp.exp().mean(), None, None, frames, None
         rows = preds.cpu()
         hyps = [[int(v) for v in row[row >= 0]] for row in rows]
         return hyps, logp.exp().mean(), None, None
@@ -104,18 +135,23 @@ class TransducerBeamSearcher(torch.nn.Module):
         b_ih, b_hh = (f(rnn.bias_ih_l0), f(rnn.bias_hh_l0)) if rnn.bias else (None, None)
         return f(emb.Embedding.weight), mats, b_ih, b_hh, f(proj.w.bias), f(head.w.bias), wdt
 
-    def greedy_stream(self, enc_chunk, state=None, n_valid=None):
+    def greedy_stream(self, enc_chunk, state=None, n_valid=None, return_frames=False):
         """Greedy search over the next frames of a batch of streams: enc_chunk [B,C,J] (the encoder_proj output of one chunk), ``state``
         the value returned by the previous call (None: start of the streams, the predictor is primed with blank as in the one-call
         search), n_valid int32 [B] = frames of this chunk that belong to each stream (None: all C). Frames past a stream's count are not
         decoded and leave its state untouched. Returns (new symbols of each stream, state); state["logp_sum"] is the running sum of
         the emitted symbols' log-probabilities. Decoding a sequence in chunks gives the same symbols as one call over it: the
-        device kernel (csrc/search.hip) carries the predictor state bit for bit, the step-wise loop carries it as tensors."""
+        device kernel (csrc/search.hip) carries the predictor state bit for bit, the step-wise loop carries it as tensors.
+        return_frames=True (fixed at the first call of a stream; a later call with the other value raises ValueError): returns (new symbols, their frames, state); a frame is absolute in its stream,
+        the token's column in this chunk plus state["frames_done"], the frames of the stream decoded by earlier calls."""
         if torch.is_grad_enabled():
             raise RuntimeError("greedy_stream is inference only: run it under torch.no_grad()")
         B, T, _ = enc_chunk.shape
         dev = enc_chunk.device
         nv = torch.full((B,), T, dtype=torch.int32, device=dev) if n_valid is None else n_valid.to(device=dev, dtype=torch.int32)
+        if state is not None and ("frames_done" in state) != bool(return_frames):      # (an untimed call would not advance the count)
+            raise ValueError(f"greedy_stream: this stream was started with return_frames={'frames_done' in state}")
+        done = (torch.zeros(B, dtype=torch.int32, device=dev) if state is None else state["frames_done"]) if return_frames else None
         if self._device_greedy_ok(enc_chunk):
             from . import ops
             enc = enc_chunk.contiguous()
@@ -126,6 +162,9 @@ class TransducerBeamSearcher(torch.nn.Module):
             preds, logp = ops.greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state["dev"], nv, self.blank_id,
                                                    self.tjoint.nonlinearity.negative_slope, wdt)
             state["logp_sum"] = logp
+            if return_frames:
+                state["frames_done"] = done + nv.clamp(0, T)
+                return self._unpack_preds(preds, done) + (state,)
             rows = preds.cpu()
             return [[int(v) for v in row[row >= 0]] for row in rows], state
         if state is None:
@@ -149,13 +188,16 @@ class TransducerBeamSearcher(torch.nn.Module):
             hidden = tuple(torch.where(upd.view(1, B, 1), nh, h) for nh, h in zip(new_hidden, hidden))
             tok = new_tok
         state = {"tok": tok, "out_pn": out_pn, "hidden": hidden, "logp_sum": logp_sum}
+        if return_frames:
+            state["frames_done"] = done + nv.clamp(0, T)
+            return self._unpack_preds(preds, done) + (state,)
         rows = preds.cpu()
         return [[int(v) for v in row[row >= 0]] for row in rows], state
 
     @torch.no_grad()
-    def transducer_greedy_decode(self, tn_output):
+    def transducer_greedy_decode(self, tn_output, timed=False):
         if self._device_greedy_ok(tn_output):
-            return self._greedy_on_device(tn_output)
+            return self._greedy_on_device(tn_output, timed)
         B, T, _ = tn_output.shape
         dev = tn_output.device
         tok = torch.full((B, 1), self.blank_id, dtype=torch.long, device=dev)
@@ -176,37 +218,47 @@ class TransducerBeamSearcher(torch.nn.Module):
             out_pn = torch.where(m, new_out, out_pn)
             hidden = tuple(torch.where(upd.view(1, B, 1), nh, h) for nh, h in zip(new_hidden, hidden))
             tok = new_tok
+        if timed:
+            hyps, frames = self._unpack_preds(preds)
+            return hyps, logp_sum.exp().mean(), None, None, frames, None
         table = preds.cpu()
         hyps = [[int(x) for x in row[row >= 0]] for row in table]
         return hyps, logp_sum.exp().mean(), None, None
 
     @torch.no_grad()
-    def transducer_beam_search_decode(self, tn_output):
+    def transducer_beam_search_decode(self, tn_output, timed=False):
         """Returns (best hyps, mean exp(normalised score), n-best hyps, n-best normalised log-scores) like the reference.
         A = hypotheses still to be extended at this frame, B = those that emitted blank here (the next frame's A). Until
         |B| >= beam: take the best a in A by logp / len(prediction); stop once the best b in B has logp >= state_beam + logp(a);
         run the predictor on a's last token, score the beam best symbols of the joint at this frame; blank closes a copy of
         a into B, a non-blank symbol within expand_beam of the best non-blank extends a (new predictor state) back into A.
         The recipes' networks run on the device (_device_beam_ok); an utterance the device search could not finish within ``cap``
-        hypotheses per frame is decoded again by the host loop (counted in BEAM_HOST_REDECODES)."""
+        hypotheses per frame is decoded again by the host loop (counted in BEAM_HOST_REDECODES). ``timed`` (forward_timed): two more
+        values, the best hypotheses' emission frames and the n-best's."""
         if self._device_beam_ok(tn_output):
-            return self._beam_on_device(tn_output)
-        return self._beam_host_loop(tn_output)
+            # (the untimed call keeps its one-argument form: callers and tests wrap _beam_on_device(tn_output))
+            return self._beam_on_device(tn_output, timed=True) if timed else self._beam_on_device(tn_output)
+        return self._beam_host_loop(tn_output, timed)
 
-    def _beam_host_loop(self, tn_output):
-        nbest_batch, nbest_scores = [], []
+    def _beam_host_loop(self, tn_output, timed=False):
+        nbest_batch, nbest_scores, nbest_frames = [], [], []
         for b in range(tn_output.shape[0]):
-            beam = [([self.blank_id], 0.0, None)]           # (prediction incl. the blank prefix, logp, predictor state)
+            # (prediction incl. the blank prefix, logp, predictor state); timed: + the emission frames of the prediction's tokens
+            beam = [([self.blank_id], 0.0, None, [])] if timed else [([self.blank_id], 0.0, None)]
             for t in range(tn_output.shape[1]):
-                beam = self._beam_frame(beam, tn_output[b, t, :])
-            hyps, scores = self._beam_rank(beam)
-            nbest_batch.append(hyps)
-            nbest_scores.append(scores)
+                beam = self._beam_frame(beam, tn_output[b, t, :], t if timed else None)
+            ranked = self._beam_rank(beam, timed)
+            nbest_batch.append(ranked[0])
+            nbest_scores.append(ranked[1])
+            if timed:
+                nbest_frames.append(ranked[2])
         best = [n[0] for n in nbest_batch]
-        return best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+        out = best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+        return out + ([n[0] for n in nbest_frames], nbest_frames) if timed else out
 
-    def _beam_frame(self, A, enc_t):
-        """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it."""
+    def _beam_frame(self, A, enc_t, t=None):
+        """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it. ``t`` (not None: the hypotheses are
+        4-tuples that carry their frame lists) = absolute index of this frame, recorded for every token emitted here."""
         key = lambda hyp: hyp[1] / len(hyp[0])  # noqa: E731
         dev = enc_t.device
         frame = enc_t.view(1, 1, 1, -1)
@@ -226,26 +278,31 @@ class TransducerBeamSearcher(torch.nn.Module):
             best_nonblank = logp[0] if pos[0] != self.blank_id else logp[1]
             for lp, sym in zip(logp, pos):
                 if sym == self.blank_id:
-                    beam.append((a[0][:], a[1] + lp, a[2]))
+                    beam.append((a[0][:], a[1] + lp, a[2]) + a[3:])
                 elif lp >= best_nonblank - self.expand_beam:
-                    A.append((a[0] + [sym], a[1] + lp, new_state))
+                    A.append((a[0] + [sym], a[1] + lp, new_state) + (() if t is None else (a[3] + [t],)))
         return beam
 
-    def _beam_rank(self, beam):
-        """(n-best symbol lists, their logp / len) of a beam: sorted(beam, key, reverse=True)[:nbest] (stable, as the reference)."""
+    def _beam_rank(self, beam, timed=False):
+        """(n-best symbol lists, their logp / len) of a beam: sorted(beam, key, reverse=True)[:nbest] (stable, as the reference);
+        ``timed``: and their frame lists."""
         ranked = sorted(beam, key=lambda hyp: hyp[1] / len(hyp[0]), reverse=True)[: self.nbest]
-        return [h[0][1:] for h in ranked], [h[1] / len(h[0]) for h in ranked]
+        out = [h[0][1:] for h in ranked], [h[1] / len(h[0]) for h in ranked]
+        return out + ([list(h[3]) for h in ranked],) if timed else out
 
-    def _device_beam_call(self, enc, fn, *extra):
+    def _device_beam_call(self, enc, fn, *extra, **kw):
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
         return fn(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id, self.tjoint.nonlinearity.negative_slope, wdt, self.beam_size,
-                  self.nbest, self.state_beam, self.expand_beam, self.cap, *extra)
+                  self.nbest, self.state_beam, self.expand_beam, self.cap, *extra, **kw)
 
     @torch.no_grad()
-    def _beam_on_device(self, tn_output):
+    def _beam_on_device(self, tn_output, timed=False):
         from . import ops
         enc = tn_output.contiguous()
-        nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search)
+        if timed:
+            nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search, frames=True)
+        else:
+            nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search)
         bad = [b for b in range(enc.shape[0]) if int(status[b]) != 0]
         if bad:
             if BEAM_HOST_REDECODES["utterances"] == 0:
@@ -254,49 +311,72 @@ class TransducerBeamSearcher(torch.nn.Module):
                               f"loop (counted in decoders.BEAM_HOST_REDECODES)", RuntimeWarning, stacklevel=3)
             BEAM_HOST_REDECODES["utterances"] += len(bad)
             for b in bad:
-                _, _, hyps, scores = self._beam_host_loop(enc[b:b + 1])
-                nbest_batch[b], nbest_scores[b] = hyps[0], scores[0]
+                redo = self._beam_host_loop(enc[b:b + 1], timed)
+                nbest_batch[b], nbest_scores[b] = redo[2][0], redo[3][0]
+                if timed:
+                    nbest_frames[b] = redo[5][0]
         best = [n[0] for n in nbest_batch]
-        return best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+        out = best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
+        return out + ([n[0] for n in nbest_frames], nbest_frames) if timed else out
 
-    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None):
+    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None, return_frames=False):
         """Beam search over the next frames of a batch of streams, the counterpart of greedy_stream: enc_chunk [B,C,J], ``state`` the
         value returned by the previous call (None: start of the streams), n_valid int32 [B] = frames of this chunk that belong to each
         stream (None: all C); max_frames = frames a stream may reach (device route; default BEAM_STREAM_FRAMES), read at the first call.
         Returns (current best hypothesis of each stream, state); state["nbest"] / state["scores"] hold the n-best lists and their
         logp / len. Under beam search the best prefix can change, so the whole hypothesis is returned, not new symbols. Decoding a
         sequence in chunks gives the bits of one call over it: the device route resumes its workspace (csrc/search.hip), the host
-        route carries the beam lists. A stream past ``cap`` hypotheses in a frame cannot be re-decoded chunk by chunk: RuntimeError."""
+        route carries the beam lists. A stream past ``cap`` hypotheses in a frame cannot be re-decoded chunk by chunk: RuntimeError.
+        return_frames=True: the state also carries state["frames"], the n-best lists of emission frames (absolute in the stream) that
+        match state["nbest"]. The flag is fixed at the first call of a stream (the timed device workspace has its own layout, the
+        host hypotheses carry their frames): a later call with the other value raises ValueError."""
         if torch.is_grad_enabled():
             raise RuntimeError("beam_stream is inference only: run it under torch.no_grad()")
         B, T, _ = enc_chunk.shape
         dev = enc_chunk.device
         nv = torch.full((B,), T, dtype=torch.int32, device=dev) if n_valid is None else n_valid.to(device=dev, dtype=torch.int32)
+        timed = bool(return_frames)
+        if state is not None and ("frames" in state) != timed:
+            raise ValueError(f"beam_stream: this stream was started with return_frames={'frames' in state}")
         if self._device_beam_ok(enc_chunk):
             from . import ops
             enc = enc_chunk.contiguous()
             if state is None:
                 mf = int(max_frames or BEAM_STREAM_FRAMES)
-                nbytes = ops.beam_stream_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
+                size = ops.beam_stream_timed_workspace_bytes if timed else ops.beam_stream_workspace_bytes
+                nbytes = size(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
                 state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf}
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")
-            nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"])
+            if timed:
+                nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv,
+                                                                                         state["max_frames"], frames=True)
+            else:
+                nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"])
             bad = [b for b in range(B) if int(status[b]) != 0]
             if bad:
                 raise RuntimeError(f"beam_stream: stream(s) {bad} stopped ({sorted({ops.BEAM_STATUS[int(status[b])] for b in bad})}) with "
                                    f"cap={self.cap} hypotheses per frame and max_frames={state['max_frames']}; restart the stream with a "
                                    f"larger cap (TransducerBeamSearcher(cap=...)) or max_frames")
             state["nbest"], state["scores"] = nbest_batch, nbest_scores
+            if timed:
+                state["frames"] = nbest_frames
             return [n[0] for n in nbest_batch], state
         if state is None:
-            state = {"beams": [[([self.blank_id], 0.0, None)] for _ in range(B)]}
+            state = {"beams": [[([self.blank_id], 0.0, None) + (([],) if timed else ())] for _ in range(B)]}
+            if timed:
+                state["frames_done"] = [0] * B
         elif "beams" not in state:
             raise ValueError("beam_stream: this state was made by the device route")
         counts = nv.cpu().tolist()
         for b in range(B):
-            for t in range(min(max(int(counts[b]), 0), T)):
-                state["beams"][b] = self._beam_frame(state["beams"][b], enc_chunk[b, t, :])
-        ranked = [self._beam_rank(beam) for beam in state["beams"]]
+            n = min(max(int(counts[b]), 0), T)
+            for t in range(n):
+                state["beams"][b] = self._beam_frame(state["beams"][b], enc_chunk[b, t, :], state["frames_done"][b] + t if timed else None)
+            if timed:
+                state["frames_done"][b] += n
+        ranked = [self._beam_rank(beam, timed) for beam in state["beams"]]
         state["nbest"], state["scores"] = [r[0] for r in ranked], [r[1] for r in ranked]
+        if timed:
+            state["frames"] = [r[2] for r in ranked]
         return [n[0] for n in state["nbest"]], state

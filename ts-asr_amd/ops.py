@@ -2276,6 +2276,16 @@ def beam_stream_workspace_bytes(B, T, H, J, beam, cap):
     return B * (a16(64 + 24 * beam) + a16(8 * (1 + (T + 1) * beam + cap)) + 4 * (cap + beam) * (J + 2 * H))
 
 
+def beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap):
+    """Bytes of the timed searches' workspace (beam_search / beam_search_stream with ``frames=True``): the untimed layout of each
+    utterance plus one int32 per token-tree node, the frame at which the node's token was emitted."""
+    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
+    B, T, H, J, beam, cap = (int(v) for v in (B, T, H, J, beam, cap))
+    if min(B, T, H, J, beam, cap) <= 0:
+        return 0
+    return beam_stream_workspace_bytes(B, T, H, J, beam, cap) + B * a16(4 * (1 + (T + 1) * beam + cap))
+
+
 def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype):
     """Shapes and settings tsasr_beam_search takes (ValueError before any device call)."""
     if not isinstance(enc, torch.Tensor) or enc.dim() != 3 or enc.dtype not in (torch.float32, torch.bfloat16):
@@ -2310,25 +2320,33 @@ def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, 
     return B, T, J, H, E, V
 
 
-def _beam_read(run, B, nbest, Lmax, device):
-    """Launch ``run(hyps, lens, scores, status, Lmax, readout)``; when a hypothesis is longer than Lmax, read the n-best out again (a
-    zero-count stream call on the workspace the first launch left). Returns (n-best token lists, n-best fp64 scores, status) on the host."""
+def _beam_read(run, B, nbest, Lmax, device, times=False):
+    """Launch ``run(hyps, lens, scores, status, Lmax, readout, frames)``; when a hypothesis is longer than Lmax, read the n-best out again
+    (a zero-count stream call on the workspace the first launch left). Returns (n-best token lists, n-best fp64 scores, status) on the
+    host; ``times``: ``frames`` is an int32 tensor shaped like hyps (else None) and the n-best frame lists are returned as a fourth value."""
     hyps = torch.empty(B, nbest, Lmax, dtype=torch.int32, device=device)
+    frames = torch.empty(B, nbest, Lmax, dtype=torch.int32, device=device) if times else None
     lens = torch.empty(B, nbest, dtype=torch.int32, device=device)
     scores = torch.empty(B, nbest, dtype=torch.float64, device=device)
     status = torch.empty(B, dtype=torch.int32, device=device)
-    run(hyps, lens, scores, status, Lmax, False)
+    run(hyps, lens, scores, status, Lmax, False, frames)
     lens_h, st_h = lens.cpu(), status.cpu()
     longest = int(lens_h.max())
     if longest > Lmax:
         hyps = torch.empty(B, nbest, longest, dtype=torch.int32, device=device)
-        run(hyps, lens, scores, status, longest, True)
+        frames = torch.empty(B, nbest, longest, dtype=torch.int32, device=device) if times else None
+        run(hyps, lens, scores, status, longest, True, frames)
     hy, sc = hyps.cpu(), scores.cpu()
     out, out_sc = [], []
     for b in range(B):
         rows = [r for r in range(nbest) if int(lens_h[b, r]) >= 0] if int(st_h[b]) == 0 else []
         out.append([hy[b, r, : int(lens_h[b, r])].tolist() for r in rows])
         out_sc.append([float(sc[b, r]) for r in rows])
+    if times:
+        fr = frames.cpu()
+        out_fr = [[fr[b, r, : int(lens_h[b, r])].tolist() for r in range(nbest) if int(lens_h[b, r]) >= 0] if int(st_h[b]) == 0 else []
+                  for b in range(B)]
+        return out, out_sc, st_h, out_fr
     return out, out_sc, st_h
 
 
@@ -2338,13 +2356,15 @@ def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
 
 
 def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                workspace=None):
+                workspace=None, frames=False):
     """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
     lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
-    n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap)."""
+    n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap).
+    ``frames=True`` (tsasr_beam_search_timed): a fourth value, the n-best lists of the encoder frame that emitted each token; the
+    workspace then has beam_stream_timed_workspace_bytes; the first three values are the bits of the untimed call."""
     _no_grad_only("beam_search")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
-    need = beam_stream_workspace_bytes(B, T, H, J, beam_size, cap)
+    need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, T, H, J, beam_size, cap)
     if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
         raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
     C.require_gpu(enc, table, *mats)
@@ -2353,27 +2373,33 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
     zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws)
 
-    def run(hyps, lens, scores, status, Lmax, readout):
+    def run(hyps, lens, scores, status, Lmax, readout, fr):
         tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
                 C.io_dtype(encc), wdtype, C.stream_ptr())
         outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
-        if readout:
-            C.check(C.lib().tsasr_beam_search_stream(C.ptr(encc), *ptrs, C.ptr(zero), *outs, B, T, T, J, H, E, V, *tail), "tsasr_beam_search_stream")
+        if frames:
+            tail += (C.ptr(fr),)
+            stream_fn, fn, sfx = C.lib().tsasr_beam_search_stream_timed, C.lib().tsasr_beam_search_timed, "_timed"
         else:
-            C.check(C.lib().tsasr_beam_search(C.ptr(encc), *ptrs, *outs, B, T, J, H, E, V, *tail), "tsasr_beam_search")
+            stream_fn, fn, sfx = C.lib().tsasr_beam_search_stream, C.lib().tsasr_beam_search, ""
+        if readout:
+            C.check(stream_fn(C.ptr(encc), *ptrs, C.ptr(zero), *outs, B, T, T, J, H, E, V, *tail), "tsasr_beam_search_stream" + sfx)
+        else:
+            C.check(fn(C.ptr(encc), *ptrs, *outs, B, T, J, H, E, V, *tail), "tsasr_beam_search" + sfx)
 
     with prof.region("beam_search"):
-        return _beam_read(run, B, int(nbest), 2 * T + 16, enc.device)
+        return _beam_read(run, B, int(nbest), 2 * T + 16, enc.device, bool(frames))
 
 
 def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                       workspace, n_valid, max_frames):
+                       workspace, n_valid, max_frames, frames=False):
     """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
     (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
-    beam_search returns, for the beam after the chunk."""
+    beam_search returns, for the beam after the chunk. ``frames=True`` (tsasr_beam_search_stream_timed): also the n-best frame lists,
+    absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed."""
     _no_grad_only("beam_search_stream")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
-    need = beam_stream_workspace_bytes(B, max_frames, H, J, beam_size, cap)
+    need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, max_frames, H, J, beam_size, cap)
     if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
         raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
     if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
@@ -2384,14 +2410,15 @@ def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slop
     zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
 
-    def run(hyps, lens, scores, status, Lmax, readout):
-        C.check(C.lib().tsasr_beam_search_stream(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores),
-                                                 C.ptr(status), B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size), int(nbest),
-                                                 int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
-                                                 wdtype, C.stream_ptr()), "tsasr_beam_search_stream")
+    def run(hyps, lens, scores, status, Lmax, readout, fr):
+        fn, extra = (C.lib().tsasr_beam_search_stream_timed, (C.ptr(fr),)) if frames else (C.lib().tsasr_beam_search_stream, ())
+        C.check(fn(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status), B, T,
+                   int(max_frames), J, H, E, V, int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam),
+                   float(expand_beam), float(slope), C.io_dtype(encc), wdtype, C.stream_ptr(), *extra),
+                "tsasr_beam_search_stream_timed" if frames else "tsasr_beam_search_stream")
 
     with prof.region("beam_search_stream"):
-        return _beam_read(run, B, int(nbest), 256, enc.device)
+        return _beam_read(run, B, int(nbest), 256, enc.device, bool(frames))
 
 
 EditResult = __import__("collections").namedtuple("EditResult", ["counts", "align_op", "align_i", "align_j", "align_len", "totals"])

@@ -222,7 +222,11 @@ class TSASR(core.Brain):
             if epoch % getattr(hp, "valid_search_freq", 1) == 0 and hasattr(hp, "greedy_searcher"):
                 hyps, _, _, _ = hp.greedy_searcher(enc_out)
         elif stage == Stage.TEST and hasattr(hp, "beam_searcher"):
-            hyps, _, _, _ = hp.beam_searcher(enc_out)
+            if getattr(hp, "hyp_ctm", None):      # timestamps of the recognised tokens: the same hypotheses, plus their emission frames
+                hyps, _, _, _, frames, _ = hp.beam_searcher.forward_timed(enc_out)
+                self.hyp_times.append((getattr(batch, "id", None), hyps, frames))
+            else:
+                hyps, _, _, _ = hp.beam_searcher(enc_out)
         return logits, hyps
 
     def align_batch(self, batch):
@@ -282,6 +286,8 @@ class TSASR(core.Brain):
         super().on_stage_start(stage, epoch)
         if stage != Stage.TRAIN:
             self.cer_metric, self.wer_metric = self._metric("cer_computer"), self._metric("wer_computer")
+        if stage == Stage.TEST:
+            self.hyp_times = []      # (utterance ids, hypotheses, emission frames) per batch when hparams.hyp_ctm is set
 
     def on_stage_end(self, stage, stage_loss, epoch=None):
         super().on_stage_end(stage, stage_loss, epoch)

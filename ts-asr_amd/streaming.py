@@ -11,6 +11,10 @@ StreamingTranscriber(brain, search="beam") decodes with the recipe's beam search
 then returns each stream's best hypothesis so far as a whole token list (its prefix may change), finish() the best hypotheses and
 nbest() the n-best lists with their logp / len.
 
+start(..., timestamps=True) also keeps when each token was emitted: frames() returns, per stream, the absolute encoder frame of every
+token of the hypothesis finish() would return now (greedy: the accumulated list; beam: the current best hypothesis's), nbest_frames()
+goes with nbest(). Seconds are frames x align.frame_seconds(hparams); word spans come from align.word_spans.
+
 Every block of such a model is causal: the front-end pads time on the left only, the depthwise convolution is left-padded, the
 attention mask (look-ahead or block-causal on absolute frame indices) never looks past the current chunk, and RelPosEncXL's table is
 symmetric, so one half table serves every offset. A push therefore costs the new frames only: the front-end carries the last 2 input
@@ -71,11 +75,12 @@ class StreamingTranscriber:
         self._copies = []
 
     # ------------------------------------------------------------------------------------------------------------------------------
-    def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False):
+    def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False):
         """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
         ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
         ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
-        every chunk's encoder output (before encoder_proj) for encoder_out()."""
+        every chunk's encoder output (before encoder_proj) for encoder_out(). timestamps: keep the emission frame of every token
+        (frames(), nbest_frames())."""
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
         if hasattr(self.brain, "_setup_dtype"):      # the brain's compute dtype (as fit / evaluate set it)
@@ -108,6 +113,8 @@ class StreamingTranscriber:
         self.fe_state, self.search_state = None, None
         self.mel = None
         self.hyps = [[] for _ in range(self.B)]
+        self.timestamps = bool(timestamps)
+        self.hyp_frames = [[] for _ in range(self.B)]
         self.closed = False
         self.keep = bool(keep_encoder_out)
         self.enc_chunks = []
@@ -154,11 +161,19 @@ class StreamingTranscriber:
         e = self.encoder_proj(e)
         n_valid = (valid - t0).clamp(0, e.shape[1]).to(torch.int32)
         if self.search == "beam":                 # the best hypothesis so far (its prefix may change with later frames)
-            best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames)
+            best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames,
+                                                                return_frames=self.timestamps)
             self.hyps = [list(h) for h in best]
+            if self.timestamps:
+                self.hyp_frames = [list(f[0]) for f in self.search_state["frames"]]
             self.closed = bool(last)
             return best
-        new, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid)
+        if self.timestamps:
+            new, new_frames, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid, return_frames=True)
+            for b, fr in enumerate(new_frames):
+                self.hyp_frames[b].extend(fr)
+        else:
+            new, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid)
         for b, toks in enumerate(new):
             self.hyps[b].extend(toks)
         self.closed = bool(last)
@@ -177,6 +192,23 @@ class StreamingTranscriber:
         if self.search_state is None:
             return [[[]] for _ in range(self.B)], [[0.0] for _ in range(self.B)]
         return [[list(h) for h in n] for n in self.search_state["nbest"]], [list(s) for s in self.search_state["scores"]]
+
+    def frames(self):
+        """start(timestamps=True): per stream, the absolute encoder frame that emitted each token of the hypothesis finish() would return
+        now. Seconds: frame x align.frame_seconds(hparams); words: align.word_spans(frames, tokens, pieces, frame_seconds)."""
+        if not getattr(self, "timestamps", False):
+            raise RuntimeError("frames() needs start(..., timestamps=True)")
+        return [list(f) for f in self.hyp_frames]
+
+    def nbest_frames(self):
+        """start(timestamps=True), search="beam": the emission frames of nbest()'s symbol lists, in the same order."""
+        if self.search != "beam":
+            raise RuntimeError("nbest_frames() needs StreamingTranscriber(brain, search='beam')")
+        if not getattr(self, "timestamps", False):
+            raise RuntimeError("nbest_frames() needs start(..., timestamps=True)")
+        if self.search_state is None:
+            return [[[]] for _ in range(self.B)]
+        return [[list(f) for f in n] for n in self.search_state["frames"]]
 
     def _drop_copies(self):
         for p, copy in self._copies:
