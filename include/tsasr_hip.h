@@ -409,6 +409,21 @@ int tsasr_fbank_fwd(const float *wav, const float *window, const float *melmat, 
 int tsasr_sentence_norm_fwd(const void *x, const int32_t *lens, void *y, int B, int T, int F, float eps, int in_dtype, int out_dtype,
                             void *stream);
 
+/* Causal features for streams (build extension; csrc/features_stream.hip).
+ * tsasr_fbank_frames: seg [B,Lseg] fp32, a slice of the zero-padded signal -> out_db [B, F = (Lseg-512)/hop + 1, n_mels] fp32, the raw dB
+ * of the frames seg[i*hop, i*hop+512): the bits tsasr_fbank_fwd computes for the same samples before its floor.
+ * tsasr_running_norm_fwd: db [B,F,n_mels] fp32 -> y (out_dtype): x = max(db, running max over frames so far and bins - top_db);
+ * y = (x - mean)/max(std, eps) with the running per-bin mean / unbiased std over the frames so far (fp64 sums in frame order; fewer than
+ * 2 frames: std 1), rounded once to fp32 (bf16: that value rounded again). state: per stream 2*n_mels + 2 doubles = S1[n_mels],
+ * S2[n_mels], the count (a prior's pseudo-frames included), {float running max, int32 maximum-seen}; all zero = a fresh stream. It
+ * advances by the first n_valid[b] frames of stream b only; later frames are normalised with it frozen. n_mels <= 128. */
+size_t tsasr_fbank_frames_workspace_bytes(int n_mels);
+int tsasr_fbank_frames(const float *seg, const float *window, const float *melmat, float *out_db, int B, int Lseg, int F, int n_mels, int hop,
+                       float amin, void *workspace, size_t workspace_bytes, void *stream);
+size_t tsasr_running_norm_state_bytes(int B, int n_mels);
+int tsasr_running_norm_fwd(const float *db, const int32_t *n_valid, void *state, void *y, int B, int F, int n_mels, float top_db, double eps,
+                           int out_dtype, void *stream);
+
 /* Fused seam between two Conformer sub-blocks: s = res + alpha*timemask(dropout_p(x + bias)); y = LayerNorm(s)
  * (Dropout -> [0.5*]x + residual -> masked_fill_ -> nn.LayerNorm; Conformer.py:113-114,194-217,239-259) and its backward
  * (dres = LN_bwd(dy) + dout; dx = alpha*timemask*dropmask/(1-p)*dres; dgamma, dbeta, dbias; dout and any of the three parameter

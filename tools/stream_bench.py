@@ -2,12 +2,16 @@
 4 heads), causal encoder with block-causal attention over chunks of 40 frames, bf16, deterministic weights.
 
     python tools/stream_bench.py [--B 1 32] [--t0 0 1000 3960] [--reps 20] [--json out.json]
+    python tools/stream_bench.py --audio                                  # also: the same push fed 1.6 s of waveform (push_audio)
     python tools/stream_bench.py --profile-chunks 20 --B 32 --t0 3960     # under rocprofv3 --kernel-trace --stats: 20 chunks and nothing else timed
 
 A chunk is one push of 160 mel frames = 40 encoder frames = 1.6 s of audio. The time of a push is host wall-clock from the call to
 the return of its new tokens (the push reads its symbols back, so the device work is included), the median over --reps pushes. For
 each offset t0 the stream is moved there by setting its frame counter (the cost of a chunk does not depend on what the cache holds).
 Kernel launches per chunk are counted with torch.profiler. Real-time factor = time per chunk / 1.6 s.
+--audio: a second stream of the same model started with audio=True is pushed 25600 samples at a time (in the steady state every such
+push completes exactly one group of 160 causal feature frames: nnet.CausalFeatures, then the same push()); its median is reported beside
+the feature push's, with the median of the feature stage alone (CausalFeatures.forward_chunk on a stream of its own).
 """
 import argparse
 import importlib
@@ -23,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PKG = "ts-asr_amd"
 CHUNK_MEL, CHUNK_ENC, AUDIO_MS = 160, 40, 1600.0
+CHUNK_SAMPLES = 160 * CHUNK_MEL
 
 
 def build(device):
@@ -48,6 +53,36 @@ def make_stream(streaming, brain, B, max_frames, device):
     st.start(B, max_frames, speaker_embs=spk)
     feats = torch.randn(B, CHUNK_MEL, 80, generator=g).to(device)
     return st, feats
+
+
+def make_audio_stream(streaming, brain, B, max_frames, device):
+    D = brain.modules.encoder.d_model
+    g = torch.Generator(device="cpu").manual_seed(7)
+    spk = (torch.randn(B, 1, D, generator=g) * 0.5).to(device)
+    st = streaming.StreamingTranscriber(brain)
+    st.start(B, max_frames, speaker_embs=spk, audio=True)
+    wav = (torch.randn(B, CHUNK_SAMPLES, generator=g) * 0.05).to(device)
+    return st, wav
+
+
+def time_audio(st, wav, t0, reps):
+    """Median ms of push_audio (features + push) and of the feature stage alone, at encoder offset t0."""
+    both, alone = [], []
+    fs = st.features.init_stream(wav.shape[0], wav.device)
+    st.features.forward_chunk(wav, fs, group=CHUNK_MEL)
+    for _ in range(reps):
+        place(st, t0)
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        st.push_audio(wav)
+        both.append((time.perf_counter() - s) * 1e3)
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        f, _, fs = st.features.forward_chunk(wav, fs, group=CHUNK_MEL)
+        torch.cuda.synchronize()
+        alone.append((time.perf_counter() - s) * 1e3)
+        assert f.shape[1] == CHUNK_MEL
+    return statistics.median(both), statistics.median(alone)
 
 
 def place(st, t0):
@@ -79,6 +114,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-frames", type=int, default=4000)
     ap.add_argument("--no-split", action="store_true", help="attention without the key split (prices the split)")
+    ap.add_argument("--audio", action="store_true", help="also time push_audio of 1.6 s of waveform (causal features + the same push)")
     ap.add_argument("--profile-chunks", type=int, default=0)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -103,6 +139,10 @@ def main():
                 torch.cuda.synchronize()
                 print(json.dumps({"profiled_chunks": a.profile_chunks, "B": B, "t0": a.t0}))
                 continue
+            if a.audio:
+                sta, wav = make_audio_stream(streaming, brain, B, a.max_frames, device)
+                for _ in range(4):                              # (the first push completes no group of 160 frames: 16 ms of look-ahead)
+                    sta.push_audio(wav)
             for t0 in a.t0:
                 times = []
                 for _ in range(a.reps):
@@ -118,6 +158,9 @@ def main():
                 med = statistics.median(times)
                 r = {"B": B, "t0": t0, "ms_per_chunk_median": round(med, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
                      "kernel_launches_per_chunk": n, "rtf": round(med / AUDIO_MS, 5), "split": not a.no_split}
+                if a.audio:
+                    med_a, med_f = time_audio(sta, wav, t0, a.reps)
+                    r.update({"ms_per_audio_chunk_median": round(med_a, 3), "ms_features_median": round(med_f, 3), "rtf_audio": round(med_a / AUDIO_MS, 5)})
                 print(json.dumps(r), flush=True)
                 results.append(r)
     if a.json:

@@ -27,7 +27,9 @@ __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i
 __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wav, const float *__restrict__ window,
                                                     const float *__restrict__ melmat /*[257][n_mels]*/, float *__restrict__ out_db,
                                                     int *__restrict__ umax, const int *__restrict__ band, int L, int Tn, int n_mels,
-                                                    int hop, float amin) {
+                                                    int hop, float amin, int origin) {
+    // origin: sample offset of frame 0's window start (FB_N / 2 = center=True over the unpadded signal; 0 = frames of a segment that
+    // carries its own padding, tsasr_fbank_frames). umax may be null there: the causal floor is running_norm's business
     __shared__ float2 buf[4][FB_N];
     __shared__ float2 tw[FB_N / 2];
     __shared__ float pw[4][FB_N / 2 + 1];
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
     const bool live = frame < Tn;
     float2 *x = buf[wave];
     if (live) {
-        const long long start = frame * hop - FB_N / 2;  // center=True: frame t covers [t*hop - 256, t*hop + 256)
+        const long long start = frame * hop - origin;  // center=True (origin 256): frame t covers [t*hop - 256, t*hop + 256)
         for (int i = lane; i < FB_N; i += 64) {
             const long long p = start + i;
             const float v = (p >= 0 && p < L) ? wav[(long long)b * L + p] * window[i] : 0.f;
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
         }
     }
     mx = wave_max(mx);
-    if (live && lane == 0) atomicMax(umax + b, f2ord(mx));
+    if (live && lane == 0 && umax) atomicMax(umax + b, f2ord(mx));
 }
 
 template <typename T>
@@ -170,6 +172,13 @@ __global__ __launch_bounds__(SN_NT) void sentence_norm_kernel(const TI *__restri
     }
 }
 
+// csrc/features_stream.hip (tsasr_fbank_frames): the raw dB of the F frames that start at seg[i * hop], no floor, no maximum
+void tsasr_fbank_launch_frames(const float *seg, const float *window, const float *melmat, float *out_db, int *band, int B, int Lseg, int F,
+                               int n_mels, int hop, float amin, hipStream_t st) {
+    fbank_bands_kernel<<<cdiv(n_mels, 64), 64, 0, st>>>(melmat, band, n_mels);
+    fbank_kernel<<<dim3(cdiv(F, 4), B), 256, 0, st>>>(seg, window, melmat, out_db, nullptr, band, Lseg, F, n_mels, hop, amin, 0);
+}
+
 extern "C" {
 
 size_t tsasr_fbank_workspace_bytes(int B, int T, int n_mels) {
@@ -189,7 +198,7 @@ int tsasr_fbank_fwd(const float *wav, const float *window, const float *melmat, 
     int *band = (int *)((char *)umax + align_up((size_t)B * sizeof(int), 256));
     fbank_init_kernel<<<cdiv(B, 64), 64, 0, st>>>(umax, B);
     fbank_bands_kernel<<<cdiv(n_mels, 64), 64, 0, st>>>(melmat, band, n_mels);
-    fbank_kernel<<<dim3(cdiv(T, 4), B), 256, 0, st>>>(wav, window, melmat, db, umax, band, L, T, n_mels, hop, amin);
+    fbank_kernel<<<dim3(cdiv(T, 4), B), 256, 0, st>>>(wav, window, melmat, db, umax, band, L, T, n_mels, hop, amin, FB_N / 2);
     const long long per = (long long)T * n_mels;
     dim3 g2((unsigned)min((long long)64, (per + 255) / 256), B);
     if (out_dtype == TSASR_F32) fbank_floor_kernel<float><<<g2, 256, 0, st>>>(db, umax, (float *)out, per, top_db);

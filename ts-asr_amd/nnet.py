@@ -205,6 +205,103 @@ class InputNormalization(nn.Module):
         return ops.sentence_norm(x, abs_lengths_round(lengths, x.shape[1]), self.eps)
 
 
+class CausalFeatures(nn.Module):
+    """Causal log-mel features with a running floor and running normalisation (build extension; the reference has no such mode): what a
+    live stream can compute, and what a model meant for one is trained on (hparams ``causal_features: True``). ``fbank``: the recipe's
+    Fbank (its window, filters, hop, top_db, amin are used; it is not called). The signal is padded with n_fft/2 zeros on the left
+    and, at its end, on the right; frame k covers padded samples [k*hop, k*hop + n_fft) - the offline center=True frame, bit for bit,
+    before the floor - and exists once sample k*hop + n_fft/2 - 1 has arrived (16 ms of look-ahead). Frame k is floored at top_db below
+    the maximum of frames 0..k and normalised with the per-bin mean / unbiased deviation of the floored frames 0..k (fp64 sums in
+    frame order; fewer than 2 frames: deviation 1), so no frame depends on later audio or on how the audio is cut into pushes.
+    ``prior`` = (mean [n_mels], std [n_mels], n0): n0 pseudo-frames of those statistics start the sums (Kaldi's online-CMVN prior).
+
+    forward(wav, rel_lens): whole utterances in one call. init_stream / forward_chunk: the same frames push by push."""
+
+    def __init__(self, fbank, prior=None, out_dtype=torch.float32):
+        super().__init__()
+        if fbank.n_fft != 512 or fbank.win_length != 512:
+            raise NotImplementedError("ts-asr_amd.CausalFeatures: n_fft = win_length = 512 samples (as ops.fbank)")
+        self.fbank, self.eps, self.out_dtype = fbank, 1e-10, out_dtype
+        self.pad, self.hop, self.n_mels = fbank.n_fft // 2, fbank.hop_length, fbank.n_mels
+        self.prior_n = 0.0
+        if prior is not None:
+            mu, sd, n0 = prior
+            self.prior_n = float(n0)
+            self.register_buffer("prior_mean", torch.as_tensor(mu, dtype=torch.float64).reshape(self.n_mels).clone(), persistent=False)
+            self.register_buffer("prior_std", torch.as_tensor(sd, dtype=torch.float64).reshape(self.n_mels).clone(), persistent=False)
+
+    def _norm_state(self, B, device):
+        prior = (self.prior_mean, self.prior_std, self.prior_n) if self.prior_n > 0 else None
+        return ops.running_norm_state(B, self.n_mels, device, prior)
+
+    def _frames(self, seg):
+        return ops.fbank_frames(seg, self.fbank.window, self.fbank.fbank_matrix, self.hop, self.fbank.amin)
+
+    def forward(self, wav, rel_lens):
+        """wav [B,L], rel_lens [B] -> [B, 1 + L//hop, n_mels]; row b's statistics stop at abs_lengths_round(rel_lens, T)[b] frames.
+        Every call starts from a fresh state (one zero fill; with a prior three more element-wise launches): no host copy, capturable."""
+        C.require_gpu(wav, rel_lens)
+        db = self._frames(F.pad(wav.detach().float(), (self.pad, self.pad)))
+        n_valid = abs_lengths_round(rel_lens, db.shape[1]).to(torch.int32).contiguous()
+        return ops.running_norm(db, self._norm_state(wav.shape[0], wav.device), n_valid, self.fbank.top_db, self.eps, self.out_dtype)
+
+    def init_stream(self, B, device):
+        """State of B streams that start together: the samples not yet consumed (the left padding to begin with), the normaliser's
+        state, and per stream whether and where it ended."""
+        return {"buf": torch.zeros(B, self.pad, dtype=torch.float32, device=device), "norm": self._norm_state(B, device),
+                "samples": 0, "emitted": 0, "valid": [None] * B, "closed": False}
+
+    def forward_chunk(self, wav_chunk, state, wav_lens=None, last=False, group=4):
+        """Next N samples of every stream, wav_chunk [B,N] (any N >= 0) -> (feats [B,F,n_mels], n_valid [B] int32, state). F is the
+        largest multiple of ``group`` of frames whose samples have arrived (every remaining frame when ``last``: the right padding is
+        appended; no push may follow), possibly 0; it depends on the number of samples pushed to the batch only. wav_lens [B]: valid
+        samples of this push per stream (default N); fewer than N ends that stream - the rest of its row is taken as zeros, its later
+        pushes must carry 0, and its frames past 1 + (its samples)//hop are not counted in n_valid and leave its statistics alone.
+        The state is updated in place; a push that raises leaves it as it was."""
+        B = state["buf"].shape[0]
+        if wav_chunk.ndim != 2 or wav_chunk.shape[0] != B:
+            raise ValueError(f"wav_chunk must be [B={B}, N], got {tuple(wav_chunk.shape)}")
+        if state["closed"]:
+            raise ValueError("forward_chunk after the last push of the stream")
+        if int(group) < 1:
+            raise ValueError(f"group must be >= 1, got {group}")
+        N = wav_chunk.shape[1]
+        lens = [N] * B if wav_lens is None else [int(v) for v in torch.as_tensor(wav_lens).reshape(-1).tolist()]
+        if len(lens) != B or any(v < 0 or v > N for v in lens):
+            raise ValueError(f"wav_lens must hold B={B} counts in [0, {N}], got {lens}")
+        for b, v in enumerate(lens):
+            if state["valid"][b] is not None and v != 0:
+                raise ValueError(f"stream {b} ended at sample {state['valid'][b]}: its later pushes carry 0 valid samples, got {v}")
+        C.require_gpu(wav_chunk)
+        # ---- checked: from here on the state moves
+        chunk = wav_chunk.detach().float()
+        if any(v < N for v in lens):
+            keep = torch.arange(N, device=chunk.device)[None, :] < torch.tensor(lens, device=chunk.device)[:, None]
+            chunk = chunk * keep
+        for b, v in enumerate(lens):
+            if state["valid"][b] is None and v < N:
+                state["valid"][b] = state["samples"] + v
+        state["samples"] += N
+        P, e0 = state["samples"], state["emitted"]
+        parts = [state["buf"], chunk] + ([chunk.new_zeros(B, self.pad)] if last else [])
+        buf = torch.cat(parts, dim=1)
+        if last:
+            e1 = 1 + P // self.hop
+            state["closed"] = True
+        else:
+            avail = (P - self.pad) // self.hop + 1 if P >= self.pad else 0
+            e1 = e0 + max(avail - e0, 0) // int(group) * int(group)
+        nf = e1 - e0
+        ends = [e1 if a is None else min(max(1 + a // self.hop, e0), e1) for a in state["valid"]]
+        n_valid = torch.tensor([e - e0 for e in ends], dtype=torch.int32, device=chunk.device)
+        if nf == 0:
+            state["buf"] = buf
+            return torch.empty(B, 0, self.n_mels, dtype=self.out_dtype, device=chunk.device), n_valid, state
+        db = self._frames(buf[:, :(nf - 1) * self.hop + 2 * self.pad])
+        feats = ops.running_norm(db, state["norm"], n_valid, self.fbank.top_db, self.eps, self.out_dtype)
+        state["buf"] = buf[:, nf * self.hop:].contiguous()
+        state["emitted"] = e1
+        return feats, n_valid, state
 
 # ------------------------------------------------------------------------------------------------------
 # A17 / A18 the two augmenters of compute_forward (TRAIN stage, ``augment: True``; train_librispeechmix_scratch.py:82-94)

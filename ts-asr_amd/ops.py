@@ -22,7 +22,7 @@ STATUS = {
     "frontend block 2 (bf16, C_out = 128)": "HIP implicit GEMMs (conv_s2_fwd / conv_s2_wgrad / conv_s2_dgrad)",
     "matmul(bf16)": "HIP (gemm_bf16: fwd, dgrad, wgrad-into-arena)", "matmul(fp32 parity mode)": "HIP (gemm_f32: fp32 matrix cores; fwd, dgrad, wgrad)", "lstm(bf16 training)": "HIP persistent whole-sequence kernels (per-step kernels for other H)", "lstm(decoding / fp32 parity)": "HIP (lstm_f32: exact fp32, optional initial state)",
     "attention(fp32 parity, cross_attention injection)": "HIP (attention_f32: exact fp32)", "joint(fp32 parity)": "HIP (joint_f32)",
-    "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP",
+    "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP", "fbank_frames": "HIP", "running_norm": "HIP (features_stream.hip)",
     "relpos_attention": "HIP (forward: everything-in-LDS kernel for T <= 256 and, per chunk of 256 keys, for long sequences in small batches, streaming kernel otherwise; backward = query-major, key-major, d(pk) and partial-sum kernels)",
     # What is NOT hand-written: shapes / modes none of the three recipes reaches. Each of these routes goes through lib_fallback(): counted in
     # LIB_FALLBACKS, announced once (warnings), refused with TsasrHipMissing when ops.STRICT_HIP (env TSASR_STRICT_HIP=1) is set.
@@ -1588,6 +1588,65 @@ def sentence_norm(x, abs_lens, eps, out_dtype=None):
     with prof.region("sentence_norm"):
         C.check(C.lib().tsasr_sentence_norm_fwd(C.ptr(xc), C.ptr(abs_lens.to(torch.int32).contiguous()), C.ptr(y), B, T, Fq, float(eps),
                                                 C.io_dtype(xc), C.io_dtype(y), C.stream_ptr()), "tsasr_sentence_norm_fwd")
+    return y
+
+
+def fbank_frames(seg, window, fbank_matrix, hop, amin):
+    """seg [B,Lseg] (a slice of the zero-padded signal) -> raw log-mel dB [B, (Lseg-512)//hop + 1, n_mels] fp32 of the frames
+    seg[i*hop : i*hop+512]: the offline fbank kernel without the floor - the bits ops.fbank(..., top_db=inf) gives for those samples."""
+    C.require_gpu(seg)
+    s = seg.detach().float().contiguous()
+    B, Lseg = s.shape
+    if Lseg < 512:
+        raise ValueError(f"fbank_frames: a segment holds at least one window of 512 samples, got {Lseg}")
+    F = (Lseg - 512) // int(hop) + 1
+    n_mels = fbank_matrix.shape[1]
+    out = torch.empty(B, F, n_mels, dtype=torch.float32, device=s.device)
+    ws = _ws(C.lib().tsasr_fbank_frames_workspace_bytes(n_mels), s.device)
+    with prof.region("fbank_frames"):
+        C.check(C.lib().tsasr_fbank_frames(C.ptr(s), C.ptr(window.float().contiguous()), C.ptr(fbank_matrix.float().contiguous()), C.ptr(out),
+                                           B, Lseg, F, n_mels, int(hop), float(amin), C.ptr(ws), ws.numel(), C.stream_ptr()),
+                "tsasr_fbank_frames")
+    return out
+
+
+def running_norm_state(B, n_mels, device, prior=None):
+    """The state ops.running_norm advances: [B, 2*n_mels + 2] float64 = S1, S2 per bin, the frame count, {running max, seen} (layout:
+    include/tsasr_hip.h). Zero = a fresh stream; ``prior`` = (mean [n_mels], std [n_mels], n0) starts the sums at n0 pseudo-frames of
+    those statistics (Kaldi's online CMVN prior). The running maximum has no prior."""
+    nbytes = C.lib().tsasr_running_norm_state_bytes(B, n_mels)
+    state = torch.zeros(B, nbytes // (8 * B), dtype=torch.float64, device=device)
+    if prior is not None:
+        mu, sd, n0 = prior
+        n0 = float(n0)
+        if n0 < 0:
+            raise ValueError(f"running_norm_state: the prior's count must be >= 0, got {n0}")
+        mu = torch.as_tensor(mu, dtype=torch.float64, device=device).reshape(n_mels)
+        sd = torch.as_tensor(sd, dtype=torch.float64, device=device).reshape(n_mels)
+        state[:, :n_mels] = n0 * mu
+        state[:, n_mels:2 * n_mels] = n0 * (sd * sd + mu * mu)
+        state[:, 2 * n_mels] = n0
+    return state
+
+
+def running_norm(db, state, n_valid, top_db, eps, out_dtype=torch.float32):
+    """Causal floor + running mean / deviation normalisation of raw dB frames db [B,F,n_mels] fp32 (HIP kernel, one workgroup per stream,
+    fp64 sums in frame order: the result does not depend on how the frames are cut into calls). ``state`` (running_norm_state) is
+    advanced IN PLACE by the first n_valid[b] frames of stream b; frames past them are normalised with the state frozen."""
+    C.require_gpu(db, state, n_valid)
+    if db.dtype != torch.float32 or not db.is_contiguous():
+        raise ValueError("running_norm: db is a contiguous fp32 tensor (the raw dB of ops.fbank_frames)")
+    B, F, n_mels = db.shape
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() * 8 != C.lib().tsasr_running_norm_state_bytes(B, n_mels):
+        raise ValueError(f"running_norm: state must be running_norm_state({B}, {n_mels}), got {tuple(state.shape)} {state.dtype}")
+    if n_valid.dtype != torch.int32 or n_valid.shape != (B,) or not n_valid.is_contiguous():
+        raise ValueError(f"running_norm: n_valid must be int32 [{B}]")
+    y = torch.empty(B, F, n_mels, dtype=out_dtype, device=db.device)
+    if F == 0:
+        return y
+    with prof.region("running_norm"):
+        C.check(C.lib().tsasr_running_norm_fwd(C.ptr(db), C.ptr(n_valid), C.ptr(state), C.ptr(y), B, F, n_mels, float(top_db), float(eps),
+                                               C.io_dtype(y), C.stream_ptr()), "tsasr_running_norm_fwd")
     return y
 
 

@@ -118,6 +118,15 @@ class TSASR(core.Brain):
                 prof.stamp("early weight gradients done [main]")
         return None
 
+    def _causal_features(self):
+        """hparams ``causal_features: True``: the mixture's features are the causal ones (running floor, running normalisation) over the
+        recipe's own Fbank tables; the enrolment keeps the sentence-level pair (it is whole before a stream starts)."""
+        cf = getattr(self, "_causal_feats", None)
+        if cf is None:
+            from ..nnet import CausalFeatures
+            cf = self._causal_feats = CausalFeatures(self.modules.feature_extractor)
+        return cf
+
     def _forward_logits(self, batch, stage):
         """The forward up to the fused joint logits, shared by compute_forward and align_batch: (logits, enc_out, tlen, ulen, epoch)."""
         hp = self.hparams
@@ -183,8 +192,11 @@ class TSASR(core.Brain):
         else:
             if augment and "speed_perturb" in self.modules:      # train_librispeechmix_scratch.py:82-85
                 mixed = self.modules.speed_perturb(mixed)
-            feats = self.modules.feature_extractor(mixed)
-            feats = self.modules.normalizer(feats, mixed_lens, epoch=epoch)
+            if getattr(hp, "causal_features", False):            # BUILD EXTENSION: the features a live stream sees (nnet.CausalFeatures)
+                feats = self._causal_features()(mixed, mixed_lens)
+            else:
+                feats = self.modules.feature_extractor(mixed)
+                feats = self.modules.normalizer(feats, mixed_lens, epoch=epoch)
         if augment and "augmentation" in self.modules:           # train_librispeechmix_scratch.py:91-94
             feats = self.modules.augmentation(feats)
         feats = self.modules.frontend(feats)

@@ -5,6 +5,7 @@
     with torch.no_grad():
         for feats in chunks:                        # [B, F, 80] normalised fbank frames, F a multiple of 4
             new_tokens = st.push(feats)             # list (per stream) of the symbols emitted for these frames
+        # or, after start(..., audio=True): st.push_audio(wav) with wav [B, N] samples, any N
         hyps = st.finish()
 
 StreamingTranscriber(brain, search="beam") decodes with the recipe's beam searcher instead (TransducerBeamSearcher.beam_stream): push()
@@ -22,11 +23,15 @@ frames of each block, every encoder layer a K/V cache and the K-1 GLU rows of it
 (ConvolutionFrontEnd.forward_chunk, ConformerEncoder.forward_chunk, TransducerBeamSearcher.greedy_stream). The valid encoder rows
 equal those of the offline causal encoder over the whole utterance.
 
-Features are an INPUT of the stream, not part of it. The recipe's Fbank clamps each utterance at ``top_db`` below its own maximum and
-InputNormalization (``norm_type: sentence``) subtracts the utterance's mean and divides by its deviation: both use statistics of the
-whole utterance, so a waveform-in stream would change what the model sees. The caller provides normalised feature frames (for example
-the offline front-end's output for an utterance, or features normalised with statistics it chooses); this class does not approximate
-the sentence-level steps.
+Features reach the stream by one of two routes. push(feats) takes normalised feature frames the caller computed: the recipe's Fbank
+clamps each utterance at ``top_db`` below its own maximum and InputNormalization (``norm_type: sentence``) uses the utterance's mean and
+deviation - statistics of the whole utterance, which a live signal does not have yet; this route serves recorded utterances (the offline
+pair's output) or features normalised with statistics the caller chooses. start(..., audio=True) + push_audio(wav) takes the waveform, any
+number of samples per push: nnet.CausalFeatures computes each frame from the samples so far (16 ms of look-ahead), floors it at ``top_db``
+below the running maximum and normalises it with the running mean and deviation (optionally started from ``feature_prior``), buffers
+samples until a whole group of frames is complete and hands those to push(). Its frames do not depend on how the audio is cut into pushes.
+A model trained with the sentence-level features sees different inputs under audio=True: train with ``causal_features: True`` (the
+mixture branch then runs the same CausalFeatures) for a match.
 
 With block-causal attention (``attention_chunk_size`` c > 1) a push holds a multiple of 4c feature frames (a frame attends its
 whole block, so a push cannot end inside one).
@@ -75,12 +80,14 @@ class StreamingTranscriber:
         self._copies = []
 
     # ------------------------------------------------------------------------------------------------------------------------------
-    def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False):
+    def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False,
+              audio=False, feature_prior=None):
         """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
         ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
         ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
         every chunk's encoder output (before encoder_proj) for encoder_out(). timestamps: keep the emission frame of every token
-        (frames(), nbest_frames())."""
+        (frames(), nbest_frames()). audio: the stream is fed waveforms (push_audio) - causal features over the recipe's Fbank tables,
+        ``feature_prior`` = (mean [n_mels], std [n_mels], n0) optionally starting their running statistics (nnet.CausalFeatures)."""
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
         if hasattr(self.brain, "_setup_dtype"):      # the brain's compute dtype (as fit / evaluate set it)
@@ -118,8 +125,46 @@ class StreamingTranscriber:
         self.closed = False
         self.keep = bool(keep_encoder_out)
         self.enc_chunks = []
+        self.features, self.feat_state = None, None
+        if audio:
+            from .nnet import CausalFeatures
+            mods = self.brain.modules
+            fbank = mods["feature_extractor"] if isinstance(mods, dict) else mods.feature_extractor
+            self.features = CausalFeatures(fbank, prior=feature_prior).to(fbank.window.device)
+        elif feature_prior is not None:
+            raise ValueError("feature_prior goes with audio=True")
         self._started = True
         return self
+
+    def push_audio(self, wav, wav_lens=None, last=False):
+        """start(..., audio=True): feed the next N samples of every stream, wav [B, N], any N. wav_lens [B]: valid samples of this push per
+        stream (default N; fewer ends that stream, whose later pushes carry 0). The frames whose samples have arrived are computed in
+        whole groups of 4 (4 x attention_chunk_size with block-causal attention) and pushed; the rest waits for the next push, every
+        remaining frame goes with the ``last`` one. Returns what push() returns (for no frames when no group is complete yet). A push that
+        raises (bad wav_lens, past max_frames) leaves the stream, its buffered samples and running statistics included, as it was."""
+        if not self._started:
+            raise RuntimeError("push_audio() before start()")
+        if self.features is None:
+            raise RuntimeError("push_audio() needs start(..., audio=True)")
+        if self.closed:
+            raise RuntimeError("push_audio() after the last push of the stream")
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        if wav.ndim != 2 or wav.shape[0] != self.B:
+            raise ValueError(f"wav must be [B={self.B}, N], got {tuple(wav.shape)}")
+        if self.feat_state is None:
+            self.feat_state = self.features.init_stream(self.B, wav.device)
+        blk = max(int(getattr(self.encoder.layers[0], "chunk_size", 0) or 0), 1)
+        # forward_chunk moves the feature state (in place; the normaliser's sums on the device) before push() has checked its own
+        # arguments (max_frames): keep what a refused push must find again
+        fs = self.feat_state
+        saved = dict(fs, norm=fs["norm"].clone(), valid=list(fs["valid"]))
+        feats, n_valid, self.feat_state = self.features.forward_chunk(wav, fs, wav_lens=wav_lens, last=last, group=4 * blk)
+        try:
+            return self.push(feats, mel_lens=n_valid, last=last)
+        except Exception:
+            self.feat_state = saved
+            raise
 
     def push(self, feats, mel_lens=None, enc_lens=None, last=False):
         """Feed the next F feature frames of every stream, feats [B, F, 80]; F must be a multiple of 4 unless ``last`` (no push may
