@@ -585,6 +585,38 @@ int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void
                                    int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
                                    double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames);
 
+/* Beam search with LM fusion (SB/decoders/transducer.py:264-266, 311-351, 386-409 with SB/lobes/models/RNNLM.py): beside the predictor, a
+ * recurrent LM = embedding -> `layers` stacked LSTM cells -> `dnn_blocks` blocks of Linear, LayerNorm, LeakyReLU -> Linear to V, evaluated
+ * once per hypothesis node on the node's token (blank = the LM's BOS) from the parent's LM state. A non-blank extension by sym scores
+ * (logp(a) + logp_joint[sym]) + lm_weight * log_softmax(lm)[sym] in fp64; the top-k, the expand_beam test and the blank copies read the
+ * joint alone. 1 <= layers <= 4, 0 <= dnn_blocks <= 2; hidden, emb_dim, dnn_neurons multiples of 4 <= 1024 (dnn_blocks == 0: dnn_neurons
+ * == hidden). Matrices in the call's wdtype, torch layouts (w_ih[l] [4 hidden, l == 0 ? emb_dim : hidden], w_hh[l] [4 hidden, hidden],
+ * w_dnn[k] [dnn_neurons, k == 0 ? hidden : dnn_neurons], w_out [V, dnn_neurons]); emb [V, emb_dim], biases and LayerNorm vectors fp32
+ * (NULL: none). The function takes tsasr_beam_search_stream_timed's arguments, then the LM and its weight: n_valid NULL = the offline search (the
+ * workspace is started afresh, max_frames = T), frames NULL = untimed. Each predictor slot of the workspace also holds 64 + 2 layers
+ * hidden floats (lm_logp | lm_h | lm_c): the workspace-bytes function below = B * (align16(64 + 24 beam) + align16(8 nodes) + 4 (cap + beam)
+ * (J + 2H + 64 + 2 layers hidden) + (times ? align16(4 nodes) : 0)), nodes = 1 + (T + 1) beam + cap. LDS: the search's own plus
+ * 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden, dnn_neurons) + 130) bytes, together <= 152 KB. */
+typedef struct tsasr_lm_desc {
+    const float *emb;
+    const void *w_ih[4], *w_hh[4];
+    const float *b_ih[4], *b_hh[4];
+    const void *w_dnn[2];
+    const float *b_dnn[2], *ln_g[2], *ln_b[2];
+    const void *w_out;
+    const float *b_out;
+    float ln_eps[2];
+    int layers, hidden, emb_dim, dnn_blocks, dnn_neurons;
+    float slope; /* LeakyReLU of the dnn blocks */
+} tsasr_lm_desc;
+size_t tsasr_beam_search_lm_workspace_bytes(int B, int T, int H, int J, int beam, int cap, int lm_layers, int lm_hidden, int times);
+int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                         size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                         int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                         double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                         double lm_weight);
+
 /* ------------------------------------------------------------------------------------------
  * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:
  * 124-334, Kaldi's compute-wer order: the substitution / match only if strictly cheaper than both others, else the deletion if strictly

@@ -13,6 +13,12 @@ the device's own inputs (count only; the counts do not depend on which route ran
 --times: the launch alone, without the host read-back: the stream is pre-loaded, events sit around each launch, the two forms
 alternate, median of --reps after warm-up (the method of profiles/align_notes.md); B = 32, T' = --frames, beam 15, bf16 and fp32.
 --ab-lib: the untimed launch of another build of the library (e.g. the parent commit's) takes part in the same loop.
+
+    python tools/beam_bench.py --lm [--reps 5] [--host-utts 1] [--lm-weight 0.3] [--ab-lib OTHER.so]
+
+--lm: the LM-fused launch (tsasr_beam_search_lm, the reference-default RNNLM: 2 x 1024 LSTM, embedding 128, one 512 block; seeded initial
+weights) beside the unfused launch in the same loop, by the method of --times; then the host loop with the same LM (TSASR_BEAM_KERNEL=0)
+over --host-utts utterances, wall clock per utterance. LM steps per frame = hypothesis nodes expanded (one LM step each, as predictor steps).
 """
 import argparse
 import ctypes
@@ -130,6 +136,101 @@ def times_bench(args):
     return results
 
 
+def lm_bench(args):
+    """Fused against unfused launch on the TEST shape, and the host loop with the same LM; prints one JSON line per dtype."""
+    dec = importlib.import_module("ts-asr_amd.decoders")
+    ops = importlib.import_module("ts-asr_amd.ops")
+    nnet = importlib.import_module("ts-asr_amd.nnet")
+    capi = importlib.import_module("ts-asr_amd._capi")
+    lib, P = capi.lib(), capi.ptr
+    results = []
+    for dtype in args.dtypes.split(","):
+        brain, h = entry._config1_brain("cuda:0", dtype, joint_dim=640, decoder_neurons=512)
+        brain._setup_dtype()
+        m = brain.modules
+        dt = torch.float32 if dtype == "fp32" else torch.bfloat16
+        g = np.load(os.path.join(ROOT, "tests", "golden", "c1_chain_cat.npz"))["enc_proj"]
+        B, T, beam, nbest, cap = 32, args.frames, 15, 5, dec.BEAM_CAP
+        enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (B, T, 640), float(np.std(g)))).to("cuda:0", dt)
+        torch.manual_seed(0)
+        lm = nnet.RNNLM(29, return_hidden=True).to("cuda:0").eval()
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] += 3.0
+            s = dec.TransducerBeamSearcher([m.embedding, m.decoder, m.decoder_proj], m.joiner, [m.transducer_head], blank_id=0,
+                                           beam_size=beam, nbest=nbest, lm_module=lm, lm_weight=args.lm_weight, state_beam=2.3, expand_beam=2.3)
+            assert s._device_beam_ok(enc)
+            table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
+            lm_args = s._device_lm_args(enc)
+        H, J, E, V, Lmax = mats[1].shape[1], 640, table.shape[1], mats[3].shape[0], 2 * T + 16
+        desc, weight, lm_layers, lm_hidden = ops._beam_lm_desc(lm_args, V, wdt)
+        ws = torch.zeros(ops.beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, lm_layers, lm_hidden), dtype=torch.uint8, device="cuda:0")
+        hyps = torch.empty(B, nbest, Lmax, dtype=torch.int32, device="cuda:0")
+        lens = torch.empty(B, nbest, dtype=torch.int32, device="cuda:0")
+        scores = torch.empty(B, nbest, dtype=torch.float64, device="cuda:0")
+        status, status_lm = (torch.empty(B, dtype=torch.int32, device="cuda:0") for _ in range(2))
+        wptrs = (P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]), P(b_head), P(ws), ws.numel())
+        head = (P(enc),) + wptrs + (P(hyps), P(lens), P(scores), P(status), B, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01,
+                                    capi.io_dtype(enc), wdt)
+        outs_lm = (P(hyps), P(lens), P(scores), P(status_lm))
+        forms = {"unfused": lambda: capi.check(lib.tsasr_beam_search(*head, capi.stream_ptr()), "tsasr_beam_search"),
+                 "fused": lambda: capi.check(ops._beam_lm_launch(enc, wptrs, None, outs_lm, B, T, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3,
+                                                                 0.01, wdt, None, desc, weight), "tsasr_beam_search_lm")}
+        if args.ab_lib:
+            other = ctypes.CDLL(os.path.abspath(args.ab_lib)).tsasr_beam_search
+            other.restype, other.argtypes = lib.tsasr_beam_search.restype, lib.tsasr_beam_search.argtypes
+            forms["unfused_ab"] = lambda: capi.check(other(*head, capi.stream_ptr()), "tsasr_beam_search (--ab-lib)")
+        names = list(forms)
+        ms = {n: [] for n in names}
+        fill = torch.empty(256 << 20, dtype=torch.uint8, device="cuda:0")
+        for n in names:                                      # warm-up
+            forms[n]()
+        torch.cuda.synchronize()
+        for rep in range(args.reps):
+            order = names[rep % len(names):] + names[:rep % len(names)]
+            for n in (order if (rep // len(names)) % 2 == 0 else order[::-1]):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                fill.fill_(rep % 200)
+                fill.fill_(rep % 200 + 1)
+                e0.record()
+                forms[n]()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[n].append(e0.elapsed_time(e1))
+        med = {n: float(np.median(v)) for n, v in ms.items()}
+        spread = lambda v: round(float(np.percentile(v, 90) - np.percentile(v, 10)), 3)  # noqa: E731
+        r = dict(dtype=dtype, B=B, T=T, beam=beam, reps=args.reps, lm_weight=args.lm_weight, fused_over_unfused=round(med["fused"] / med["unfused"], 2),
+                 stopped_utts=int((status != 0).sum()), stopped_utts_fused=int((status_lm != 0).sum()))
+        for n in names:
+            r[n + "_ms"], r[n + "_p10_p90_ms"] = round(med[n], 3), spread(ms[n])
+        ok = [b for b in range(B) if int(status_lm[b]) == 0][: args.host_utts]
+        if ok:
+            os.environ["TSASR_BEAM_KERNEL"] = "0"
+            try:
+                with torch.no_grad():
+                    steps = [0]
+                    lm_forward = lm.forward
+
+                    def counted(*a, **k):
+                        steps[0] += 1
+                        return lm_forward(*a, **k)
+                    lm.forward = counted
+                    t0 = time.perf_counter()
+                    s(enc[ok])
+                    torch.cuda.synchronize()
+                    r["host_lm_ms_per_utt"] = round((time.perf_counter() - t0) * 1e3 / len(ok), 1)
+                    r["host_lm_steps_per_frame"] = round(steps[0] / (len(ok) * T), 2)        # one per expansion on the host route
+                    lm.forward = lm_forward
+                    r["nodes_per_frame"] = round(counts(s, enc[ok[:1]])[1] / T, 2)             # (the unfused search's; one LM step each when fused)
+                    r["fused_speedup_batch"] = round(r["host_lm_ms_per_utt"] * B / med["fused"], 1)
+            finally:
+                del os.environ["TSASR_BEAM_KERNEL"]
+        with torch.no_grad():
+            m.transducer_head.w.bias[0] -= 3.0
+        print(json.dumps(r), flush=True)
+        results.append(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -139,9 +240,13 @@ def main():
     ap.add_argument("--dtypes", default="fp32,bf16")
     ap.add_argument("--times", action="store_true", help="time the timed launch beside the untimed one (launch only)")
     ap.add_argument("--ab-lib", default=None, help="--times: also time tsasr_beam_search of this other build of the library")
+    ap.add_argument("--lm", action="store_true", help="time the LM-fused launch beside the unfused one, and the host loop with the same LM")
+    ap.add_argument("--lm-weight", type=float, default=0.3)
     args = ap.parse_args()
     if args.times:
         return times_bench(args)
+    if args.lm:
+        return lm_bench(args)
     dec = importlib.import_module("ts-asr_amd.decoders")
     ops = importlib.import_module("ts-asr_amd.ops")
     results = []

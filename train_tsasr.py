@@ -19,6 +19,9 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
   --hyp_ctm PATH : the TEST stage decodes with TransducerBeamSearcher.forward_timed (the same hypotheses, plus the encoder frame that
         emitted each token) and a CTM of the RECOGNISED words is written there after the stage, in the format and by the rules of
         --align_file. Like --align_file, rank 0 writes, and with several processes only what its own process decoded.
+  --lm_ckpt FILE --lm_weight W : the TEST stage's beam search fuses a recurrent LM (decoders.py: LM fusion): FILE is a local state_dict
+        of an RNNLM (the reference's keys; torch.save), its shape is read from the tensors; W > 0 is the LM's weight in the score. YAMLs
+        that name lm_model / lm_weight themselves need neither option.
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
 import importlib
 import os
@@ -37,7 +40,22 @@ tsasr = importlib.import_module(PKG + ".recipes.tsasr")
 
 EXTRA = {"synthetic": 0, "syn_batch": 8, "syn_seconds": 4.0, "syn_enroll_seconds": 2.0, "syn_tokens": 24, "hip_graph": False,
          "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None,
-         "align_file": None, "hyp_ctm": None}
+         "align_file": None, "hyp_ctm": None, "lm_ckpt": None, "lm_weight": 0.0}
+
+
+def load_lm(path, device):
+    """An nnet.RNNLM (return_hidden=True, eval mode) built to fit the state_dict saved at ``path`` and loaded from it, strictly."""
+    nnet = importlib.import_module(PKG + ".nnet")
+    sd = torch.load(path, map_location="cpu")
+    if not isinstance(sd, dict) or "embedding.Embedding.weight" not in sd or "rnn.rnn.weight_hh_l0" not in sd or "out.w.weight" not in sd:
+        raise SystemExit(f"--lm_ckpt {path}: not the state_dict of an RNNLM with an LSTM")
+    vocab, emb_dim = sd["embedding.Embedding.weight"].shape
+    layers = sum(1 for k in sd if k.startswith("rnn.rnn.weight_hh_l"))
+    blocks = sum(1 for k in sd if k.startswith("dnn.linear") and k.endswith(".w.weight"))
+    lm = nnet.RNNLM(vocab, embedding_dim=emb_dim, rnn_layers=layers, rnn_neurons=sd["rnn.rnn.weight_hh_l0"].shape[1], return_hidden=True,
+                    dnn_blocks=blocks, dnn_neurons=sd["out.w.weight"].shape[1])
+    lm.load_state_dict(sd, strict=True)
+    return lm.to(device).eval()
 
 
 def synthetic_loader(n_batches, hparams, opts, seed, device):
@@ -107,6 +125,11 @@ def main(argv=None):
     brain = tsasr.TSASR(hparams["modules"], hparams["opt_class"], hparams, run_opts)
     if opts["hip_graph"]:
         brain.enable_hip_graph()
+    if opts["lm_ckpt"]:
+        searcher = hparams.get("beam_searcher")
+        if searcher is None or float(opts["lm_weight"]) <= 0:
+            raise SystemExit("--lm_ckpt needs a beam_searcher in the YAML and --lm_weight W with W > 0")
+        searcher.lm, searcher.lm_weight = load_lm(str(opts["lm_ckpt"]), brain.device), float(opts["lm_weight"])
     rank = int(os.environ.get("RANK", 0))
     if opts["synthetic"]:
         train = synthetic_loader(int(opts["synthetic"]), hparams, opts, 1234 + 1000 * rank, brain.device)

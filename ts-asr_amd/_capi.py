@@ -151,6 +151,9 @@ _PROTOS = {
     "tsasr_beam_search_timed_workspace_bytes": (c_size_t, [c_int] * 6),
     "tsasr_beam_search_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
     "tsasr_beam_search_stream_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
+    "tsasr_beam_search_lm_workspace_bytes": (c_size_t, [c_int] * 9),
+    "tsasr_beam_search_lm": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_double]),
     "tsasr_edit_distance_workspace_bytes": (c_size_t, [c_int, c_ll]),
     "tsasr_edit_distance": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_ll] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),
@@ -185,6 +188,14 @@ _PROTOS = {
     "tsasr_mix_sources_out_len": (c_ll, [c_void_p, c_void_p, c_int, c_ll, c_ll]),
     "tsasr_mix_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_ll, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+
+
+class LmDesc(ctypes.Structure):
+    """tsasr_lm_desc of include/tsasr_hip.h (the LM of tsasr_beam_search_lm), field for field."""
+    _fields_ = [("emb", c_void_p), ("w_ih", c_void_p * 4), ("w_hh", c_void_p * 4), ("b_ih", c_void_p * 4), ("b_hh", c_void_p * 4),
+                ("w_dnn", c_void_p * 2), ("b_dnn", c_void_p * 2), ("ln_g", c_void_p * 2), ("ln_b", c_void_p * 2), ("w_out", c_void_p),
+                ("b_out", c_void_p), ("ln_eps", c_float * 2), ("layers", c_int), ("hidden", c_int), ("emb_dim", c_int), ("dnn_blocks", c_int),
+                ("dnn_neurons", c_int), ("slope", c_float)]
 
 
 def exported_symbols():

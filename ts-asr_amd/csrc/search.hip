@@ -14,6 +14,8 @@
 // value lands in LDS. All arithmetic fp32; weights fp32 (master parameters) or bf16 (the training step's shadow copies).
 #include "common.h"
 
+#include <algorithm>
+
 namespace {
 
 constexpr int GREEDY_THREADS = 1024;   // 16 waves: the matrix-vector products are latency chains per wave
@@ -49,7 +51,8 @@ template <> __device__ __forceinline__ void ld4w<bf16_t>(const bf16_t *p, float 
 // out[r] = bias[r] (+ bias2[r]) + sum_k W[r][k] x[k]  (+ sum_e W2[r][e] x2[e], E2 <= 64), r < rows; x in LDS, K % 4 == 0, K <= 1024.
 // A wave takes RB rows per pass: all their 16-byte pieces are requested before the first is used (one memory round trip per RB rows,
 // not per row: with one row at a time a predictor step took 380 us), the lane's slice of x sits in registers for the whole call.
-template <typename WT, int RB, int NC>                // NC = pieces of 256 columns per row (K <= 256 * NC)
+// ACC (the LM's LSTM cells: the input and the recurrent product are two calls): out[r] += the row's value.
+template <typename WT, int RB, int NC, bool ACC = false>   // NC = pieces of 256 columns per row (K <= 256 * NC)
 __device__ __forceinline__ void gemv_rows_nc(const WT *__restrict__ W, int rows, int K, const float *x, const float *__restrict__ bias,
                                              const float *__restrict__ bias2, const WT *__restrict__ W2, int E2, const float *x2, float *out) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -84,7 +87,11 @@ __device__ __forceinline__ void gemv_rows_nc(const WT *__restrict__ W, int rows,
                 acc += w[i][c][0] * xr[c][0] + w[i][c][1] * xr[c][1] + w[i][c][2] * xr[c][2] + w[i][c][3] * xr[c][3];
             acc = wave_sum(acc);
             const int r = r0 + i;
-            if (lane == 0 && r < rows) out[r] = acc + (bias ? bias[r] : 0.f) + (bias2 ? bias2[r] : 0.f);
+            if constexpr (ACC) {
+                if (lane == 0 && r < rows) out[r] += acc;
+            } else {
+                if (lane == 0 && r < rows) out[r] = acc + (bias ? bias[r] : 0.f) + (bias2 ? bias2[r] : 0.f);
+            }
         }
     }
 }
@@ -95,6 +102,14 @@ __device__ __forceinline__ void gemv_rows(const WT *__restrict__ W, int rows, in
     if (K <= 512) gemv_rows_nc<WT, 8, 2>(W, rows, K, x, bias, bias2, W2, E2, x2, out);         // (registers: RB * NC * 4 weights in flight)
     else if (K <= 768) gemv_rows_nc<WT, 4, 3>(W, rows, K, x, bias, bias2, W2, E2, x2, out);
     else gemv_rows_nc<WT, 4, 4>(W, rows, K, x, bias, bias2, W2, E2, x2, out);
+}
+
+// out[r] += sum_k W[r][k] x[k]: the second operand of a sum whose width is past gemv_rows' 64-column side operand
+template <typename WT>
+__device__ __forceinline__ void gemv_rows_acc(const WT *__restrict__ W, int rows, int K, const float *x, float *out) {
+    if (K <= 512) gemv_rows_nc<WT, 8, 2, true>(W, rows, K, x, nullptr, nullptr, nullptr, 0, nullptr, out);
+    else if (K <= 768) gemv_rows_nc<WT, 4, 3, true>(W, rows, K, x, nullptr, nullptr, nullptr, 0, nullptr, out);
+    else gemv_rows_nc<WT, 4, 4, true>(W, rows, K, x, nullptr, nullptr, nullptr, 0, nullptr, out);
 }
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
@@ -229,15 +244,17 @@ struct BeamLayout {
 };
 
 __host__ __device__ inline size_t beam_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-__host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam, int cap) {
+// lmw (LM fusion): floats a slot holds after pn | h | c, the LM step of the node: lm_logp[64] | lm_h[L * Hl] | lm_c[L * Hl]
+__host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam, int cap, int lmw = 0) {
     BeamLayout L;
     L.nn = 1 + (T + 1) * beam + cap;                          // tree nodes: root + (typically <= beam promoted per frame) + slack
     L.ns = cap + beam;                                         // slots: the beam's + one per node expanded in a frame (<= cap)
     L.hdr = beam_align16(64 + sizeof(BeamEnt) * (size_t)beam);
     L.tree = beam_align16(8 * (size_t)L.nn);
-    L.per_utt = L.hdr + L.tree + (size_t)L.ns * (size_t)(J + 2 * H) * sizeof(float);
+    L.per_utt = L.hdr + L.tree + (size_t)L.ns * (size_t)(J + 2 * H + lmw) * sizeof(float);
     return L;
 }
+__host__ __device__ inline int beam_lm_slot_floats(int layers, int hidden) { return 64 + 2 * layers * hidden; }
 // TIMES: the node-frame array (one int per tree node) follows the untimed layout of each utterance
 __host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times) {
     return L.per_utt + (times ? beam_align16(sizeof(int) * (size_t)L.nn) : 0);
@@ -264,6 +281,95 @@ struct BeamArgs {
     int *frames;                // TIMES: [B, nbest, Lmax] emission frame of each token of hyps (absolute in the stream)
 };
 
+// LM fusion (tsasr_beam_search_lm; transducer.py:264-266, 311-351, 386-409 with lobes/models/RNNLM.py): a second recurrent network beside
+// the predictor, embedding -> L stacked LSTM cells -> nb blocks of Linear, LayerNorm, LeakyReLU -> Linear to V -> log_softmax. Its step is a
+// function of (token, parent's LM state) like the predictor's, so it runs once per node, in the node's predictor phase, into the node's
+// slot; a non-blank extension by sym scores (logp(a) + logp_joint[sym]) + weight * lm_logp[sym]; the top-k, the expand_beam test and the
+// blank copies read the joint alone. The kernel's arguments grow only for the LM instantiations (BeamKernArgs<true>).
+struct BeamLmArgs {
+    const float *emb;                     // [V, E] fp32
+    const void *w_ih[4], *w_hh[4];        // layer l: [4 Hl, l == 0 ? E : Hl], [4 Hl, Hl] (wdtype)
+    const float *b_ih[4], *b_hh[4];       // [4 Hl] fp32 or NULL
+    const void *w_dnn[2];                 // block k: [D, k == 0 ? Hl : D] (wdtype)
+    const float *b_dnn[2], *ln_g[2], *ln_b[2];   // [D] fp32 (NULL: no bias / no affine)
+    const void *w_out;                    // [V, nb > 0 ? D : Hl] (wdtype)
+    const float *b_out;
+    float ln_eps[2];
+    int L, Hl, E, nb, D;
+    float slope;
+    double weight;
+};
+template <bool LM> struct BeamKernArgs : BeamArgs {};
+template <> struct BeamKernArgs<true> : BeamArgs { BeamLmArgs lm; };
+
+template <typename P> __device__ __forceinline__ P beam_pick4(const P (&a)[4], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
+
+// One LM step of a node, by the whole workgroup: token, the parent's LM state plm (a slot's LM part, or null: zeros) -> this node's LM part
+// slm = lm_logp[64] | lm_h[L Hl] | lm_c[L Hl] and s_lmlp[64]. LDS: lx[max(E, Hl, D)], lh[2 Hl] (h | c of the layer), lgt[max(4 Hl, D)],
+// llg[64], s_stat[2]. Ends behind a barrier.
+template <typename WT>
+__device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok, const float *plm, float *slm, float *lx, float *lh,
+                                             float *lgt, float *llg, float *s_lmlp, float *s_stat) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Hl = M.Hl, L = M.L, D = M.D;
+    for (int e = tid; e < M.E; e += BEAM_THREADS) lx[e] = M.emb[(size_t)tok * M.E + e];
+    for (int l = 0; l < L; ++l) {
+        const WT *w_ih = (const WT *)beam_pick4(M.w_ih, l), *w_hh = (const WT *)beam_pick4(M.w_hh, l);
+        const float *b_ih = beam_pick4(M.b_ih, l), *b_hh = beam_pick4(M.b_hh, l);
+        for (int i = tid; i < 2 * Hl; i += BEAM_THREADS)
+            lh[i] = plm ? plm[64 + (i < Hl ? l * Hl + i : (L + l) * Hl + (i - Hl))] : 0.f;
+        __syncthreads();
+        gemv_rows<WT>(w_ih, 4 * Hl, l == 0 ? M.E : Hl, lx, b_ih, b_hh, nullptr, 0, nullptr, lgt);
+        __syncthreads();
+        gemv_rows_acc<WT>(w_hh, 4 * Hl, Hl, lh, lgt);
+        __syncthreads();
+        for (int u = tid; u < Hl; u += BEAM_THREADS) {
+            const float ig = sigmoid_f(lgt[u]), fg = sigmoid_f(lgt[Hl + u]), gg = tanhf(lgt[2 * Hl + u]), og = sigmoid_f(lgt[3 * Hl + u]);
+            const float cn = fg * lh[Hl + u] + ig * gg;
+            const float hn = og * tanhf(cn);
+            lx[u] = hn;                                      // the next layer's input
+            slm[64 + l * Hl + u] = hn;
+            slm[64 + (L + l) * Hl + u] = cn;
+        }
+        __syncthreads();
+    }
+    int K = Hl;
+    for (int k = 0; k < M.nb; ++k) {                        // Linear -> LayerNorm (two passes) -> LeakyReLU
+        const WT *w = (const WT *)(k == 0 ? M.w_dnn[0] : M.w_dnn[1]);
+        const float *bv = k == 0 ? M.b_dnn[0] : M.b_dnn[1], *g = k == 0 ? M.ln_g[0] : M.ln_g[1], *be = k == 0 ? M.ln_b[0] : M.ln_b[1];
+        const float eps = k == 0 ? M.ln_eps[0] : M.ln_eps[1];
+        gemv_rows<WT>(w, D, K, lx, bv, nullptr, nullptr, 0, nullptr, lgt);
+        __syncthreads();
+        if (wave == 0) {
+            float s = 0.f;
+            for (int i = lane; i < D; i += 64) s += lgt[i];
+            const float mean = wave_sum(s) / (float)D;
+            float q = 0.f;
+            for (int i = lane; i < D; i += 64) { const float d = lgt[i] - mean; q += d * d; }
+            const float var = wave_sum(q) / (float)D;
+            if (lane == 0) { s_stat[0] = mean; s_stat[1] = 1.f / sqrtf(var + eps); }
+        }
+        __syncthreads();
+        for (int i = tid; i < D; i += BEAM_THREADS) {
+            const float v = (lgt[i] - s_stat[0]) * s_stat[1] * (g ? g[i] : 1.f) + (be ? be[i] : 0.f);
+            lx[i] = v > 0.f ? v : v * M.slope;
+        }
+        __syncthreads();
+        K = D;
+    }
+    gemv_rows<WT>((const WT *)M.w_out, V, K, lx, M.b_out, nullptr, nullptr, 0, nullptr, llg);
+    __syncthreads();
+    if (wave == 0) {
+        const float v = lane < V ? llg[lane] : -INFINITY;
+        const float m = wave_max(v);
+        const float s = wave_sum(lane < V ? expf(v - m) : 0.f);
+        const float lp = lane < V ? (v - m) - logf(s) : 0.f;
+        s_lmlp[lane] = lp;
+        slm[lane] = lp;
+    }
+    __syncthreads();
+}
+
 // (key, index) of the larger key; equal keys: the lower index (Python max: the first maximal entry)
 __device__ __forceinline__ void beam_argmax_step(double &k, int &i, int mask) {
     const double k2 = __shfl_xor(k, mask);
@@ -271,8 +377,8 @@ __device__ __forceinline__ void beam_argmax_step(double &k, int &i, int mask) {
     if (k2 > k || (k2 == k && i2 < i)) { k = k2; i = i2; }
 }
 
-template <typename T, typename WT, bool TIMES>
-__global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArgs A) {
+template <typename T, typename WT, bool TIMES, bool LM>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamKernArgs<LM> A) {
     extern __shared__ __attribute__((aligned(16))) float bsm[];
     const int H = A.H, J = A.J, cap = A.cap;
     float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + 64;
@@ -280,6 +386,19 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
     int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
         *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
     int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
+    // LM: the LM step's own LDS after the A arrays: lx[max(E, Hl, D)] | lh[2 Hl] | lgt[max(4 Hl, D)] | llg[64] (beam_lm_step) |
+    // s_lmlp[64] (lm_logp of the node being expanded) | s_stat[2] (LayerNorm mean, rstd)
+    float *lx = nullptr, *lh = nullptr, *lgt = nullptr, *llg = nullptr, *s_lmlp = nullptr, *s_stat = nullptr;
+    int lmw = 0;
+    if constexpr (LM) {
+        lx = reinterpret_cast<float *>(Aflag + cap + (TIMES ? cap : 0));
+        lh = lx + max(max(A.lm.E, A.lm.Hl), A.lm.D);
+        lgt = lh + 2 * A.lm.Hl;
+        llg = lgt + max(4 * A.lm.Hl, A.lm.D);
+        s_lmlp = llg + 64;
+        s_stat = s_lmlp + 64;
+        lmw = beam_lm_slot_floats(A.lm.L, A.lm.Hl);
+    }
     __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
     __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
     __shared__ float s_lp[64];
@@ -288,14 +407,15 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
     //        one phase and read right after that phase's barrier, so that no wave reads a word another wave is writing.
     __shared__ int s_ctl[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap);
+    const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap, lmw);
     unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES);
     int *hdr = reinterpret_cast<int *>(wsu);
     BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
     int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
     float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
     int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
-    const int SW = J + 2 * H;                                // floats per slot: pn | h | c
+    const int SWP = J + 2 * H;                               // floats per slot: pn | h | c
+    const int SW = SWP + lmw;                                // LM: | lm_logp[64] | lm_h | lm_c
     const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
     const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
     const bool fresh = A.n_valid == nullptr;
@@ -401,9 +521,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
                 __syncthreads();
                 gemv_rows<WT>(w_proj, J, H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
                 __syncthreads();
-                for (int i = tid; i < SW; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];     // slot = pn | h | c (h, c adjacent in LDS)
+                for (int i = tid; i < SWP; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];    // slot = pn | h | c (h, c adjacent in LDS)
+                if constexpr (LM)                            // the LM step of the same token from the parent slot's LM state
+                    beam_lm_step<WT>(A.lm, A.V, tok, pst ? pst + SWP : nullptr, sl + SWP, lx, lh, lgt, llg, s_lmlp, s_stat);
             } else {
                 for (int k = tid; k < J; k += BEAM_THREADS) pn[k] = sl[k];
+                if constexpr (LM)
+                    if (tid < 64) s_lmlp[tid] = sl[SWP + tid];
                 __syncthreads();
             }
             for (int k = tid; k < J; k += BEAM_THREADS) {
@@ -446,8 +570,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamArg
                             ++nb;
                         } else if (s_tlp[j] >= bnb - A.expand_beam) {
                             if (nA >= cap) { s_ctl[4] = 1; s_ctl[11] = 1; break; }
-                            Alp[nA] = sc;
-                            Akey[nA] = sc / (double)(alen + 1);
+                            double sx = sc;                  // LM: (alp + joint) + weight * lm, a product and a sum (no fused multiply-add)
+                            if constexpr (LM) sx = __dadd_rn(sc, __dmul_rn(A.lm.weight, (double)s_lmlp[sym]));
+                            Alp[nA] = sx;
+                            Akey[nA] = sx / (double)(alen + 1);
                             Apar[nA] = a;
                             Atok[nA] = sym;
                             Alen[nA] = alen + 1;
@@ -633,9 +759,16 @@ size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, i
     return (size_t)B * beam_layout(T, H, J, beam, cap).per_utt;
 }
 
-static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times) {
+static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times, int lmw = 0) {
     if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
-    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap), times);
+    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap, lmw), times);
+}
+
+/* The LM-fused search's workspace: every slot also holds lm_logp[64] | lm_h | lm_c (64 + 2 lm_layers lm_hidden floats); times != 0: the
+ * timed layout. 0 for a non-positive size. */
+size_t tsasr_beam_search_lm_workspace_bytes(int B, int T, int H, int J, int beam, int cap, int lm_layers, int lm_hidden, int times) {
+    if (lm_layers <= 0 || lm_hidden <= 0) return 0;
+    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, beam_lm_slot_floats(lm_layers, lm_hidden));
 }
 
 /* The timed searches' workspace: the untimed layout of each utterance plus one int per tree node (align16(4 (1 + (T + 1) beam + cap))). */
@@ -647,7 +780,8 @@ static int beam_launch(const char *name, const void *enc, const float *emb, cons
                        const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
                        size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores,
                        int *status, int B, int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
-                       double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
+                       double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream,
+                       const tsasr_lm_desc *lm = nullptr, double lm_weight = 0.0) {
     TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status && (frames || !times),
                     "%s: null pointer", name);
     TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
@@ -656,18 +790,43 @@ static int beam_launch(const char *name, const void *enc, const float *emb, cons
     TSASR_CHECK_ARG(beam >= 2 && beam <= V && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
                     "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
     TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
-    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times);
+    BeamLmArgs m{};
+    size_t lm_lds = 0;
+    if (lm) {
+        const int Ll = lm->layers, Hl = lm->hidden, El = lm->emb_dim, nb = lm->dnn_blocks, D = lm->dnn_neurons;
+        TSASR_CHECK_ARG(Ll >= 1 && Ll <= 4 && Hl > 0 && Hl % 4 == 0 && Hl <= 1024 && El > 0 && El % 4 == 0 && El <= 1024 && nb >= 0 && nb <= 2 &&
+                        D > 0 && D % 4 == 0 && D <= 1024 && (nb > 0 || D == Hl),
+                        "%s: bad LM shape (layers=%d hidden=%d emb_dim=%d dnn_blocks=%d dnn_neurons=%d)", name, Ll, Hl, El, nb, D);
+        bool ptrs = lm->emb && lm->w_out;
+        for (int l = 0; l < Ll; ++l) ptrs = ptrs && lm->w_ih[l] && lm->w_hh[l];
+        for (int k = 0; k < nb; ++k) ptrs = ptrs && lm->w_dnn[k];
+        TSASR_CHECK_ARG(ptrs, "%s: null LM pointer", name);
+        m.emb = lm->emb;
+        for (int l = 0; l < 4; ++l) { m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l]; m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l]; }
+        for (int k = 0; k < 2; ++k) {
+            m.w_dnn[k] = lm->w_dnn[k]; m.b_dnn[k] = lm->b_dnn[k]; m.ln_g[k] = lm->ln_g[k]; m.ln_b[k] = lm->ln_b[k]; m.ln_eps[k] = lm->ln_eps[k];
+        }
+        m.w_out = lm->w_out; m.b_out = lm->b_out;
+        m.L = Ll; m.Hl = Hl; m.E = El; m.nb = nb; m.D = D; m.slope = lm->slope; m.weight = lm_weight;
+        lm_lds = (size_t)(std::max(std::max(El, Hl), D) + 2 * Hl + std::max(4 * Hl, D) + 64 + 64 + 2) * sizeof(float);
+    }
+    const int lmw = lm ? beam_lm_slot_floats(lm->layers, lm->hidden) : 0;
+    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw);
     TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
-    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int));
+    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
     TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
     BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
                status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope, frames};
     hipStream_t st = (hipStream_t)stream;
 #define BEAM(TT, WW)                                                                                                            \
-    {                                                                                                                           \
-        auto kern = times ? beam_search_kernel<TT, WW, true> : beam_search_kernel<TT, WW, false>;                               \
+    if (lm) {                                                                                                                   \
+        auto kern = times ? beam_search_kernel<TT, WW, true, true> : beam_search_kernel<TT, WW, false, true>;                   \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, BEAM_THREADS, lds, st>>>(a);                                                                                  \
+        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<true>{a, m});                                                           \
+    } else {                                                                                                                    \
+        auto kern = times ? beam_search_kernel<TT, WW, true, false> : beam_search_kernel<TT, WW, false, false>;                 \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<false>{a});                                                             \
     }
     if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) BEAM(float, float) else BEAM(float, bf16_t) }
     else { if (wdtype == TSASR_F32) BEAM(bf16_t, float) else BEAM(bf16_t, bf16_t) }
@@ -730,6 +889,21 @@ int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void
     return beam_launch("tsasr_beam_search_stream_timed", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
                        workspace_bytes, n_valid, hyps, frames, true, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
                        cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
+}
+
+/* The LM-fused search (see BeamLmArgs): tsasr_beam_search_stream_timed's arguments, then the LM and its weight. n_valid NULL: the offline
+ * search (the workspace is started afresh; max_frames sizes it, T for one call); frames NULL: untimed. The LM's matrices are in wdtype
+ * like the predictor's, its biases, LayerNorm vectors and embedding table fp32. workspace >= tsasr_beam_search_lm_workspace_bytes. */
+int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                         size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                         int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                         double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                         double lm_weight) {
+    TSASR_CHECK_ARG(lm, "tsasr_beam_search_lm: null lm");
+    return beam_launch("tsasr_beam_search_lm", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+                       n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
+                       Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
 }
 
 }  // extern "C"

@@ -3,11 +3,18 @@
 beam_size = 1 -> greedy (transducer.py:138-218): at most one symbol per encoder frame; the predictor state of an utterance
 advances only when it emitted a non-blank. The per-frame decision stays on the device (argmax + masked state update, no
 per-item Python loop as in transducer.py:187-194); only the final token table is read back.
-beam_size > 1 -> the reference's per-utterance beam search with state_beam / expand_beam pruning (transducer.py:220-373,
-no LM fusion). For the recipes' networks one launch of csrc/search.hip decodes the batch (tsasr_beam_search: fp64 scores, the
+beam_size > 1 -> the reference's per-utterance beam search with state_beam / expand_beam pruning (transducer.py:220-373).
+For the recipes' networks one launch of csrc/search.hip decodes the batch (tsasr_beam_search: fp64 scores, the
 reference's list order, one predictor step per hypothesis node); utterances that need more than ``cap`` hypotheses in a frame, and
 every other network shape, run the host loop: host-side hypothesis bookkeeping exactly as specified there (SURVEY.md section 8f
 row f1), device-side predictor / joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
+
+LM fusion (lm_module, lm_weight > 0; transducer.py:95-110, 264-266, 311-351, 386-409): a hypothesis also carries the LM's state; each
+expansion of a runs the LM on a's last token (blank doubles as its BOS) from a's LM state; a non-blank extension by sym takes the new
+state and scores (logp(a) + logp_joint[sym]) + lm_weight * logp_lm[sym]; the top-k, the expand_beam test and the blank copies read
+the joint alone. An nnet.RNNLM of the shapes _device_lm_ok lists is fused into the device search (tsasr_beam_search_lm: one LM step
+per node, beside its predictor step); any other module with the reference's call form runs in the host loop. Greedy search never uses
+the LM. Pinned to the reference's hypotheses by tests/golden/c1_beam_lm.npz.
 
 Timestamps (forward_timed, greedy_stream / beam_stream with return_frames=True): frames[i] = index of the encoder frame whose joint
 emitted token i, absolute from the start of the utterance or stream. Greedy emits at most one symbol per frame, so the frame is the
@@ -34,8 +41,9 @@ class TransducerBeamSearcher(torch.nn.Module):
         self.blank_id, self.beam_size, self.nbest = blank_id, beam_size, nbest
         self.state_beam, self.expand_beam = state_beam, expand_beam
         self.cap = int(cap)
-        if lm_module is not None or lm_weight != 0.0:
-            raise NotImplementedError("LM fusion is not part of the TS-ASR recipes")
+        self.lm, self.lm_weight = lm_module, lm_weight
+        if lm_module is None and lm_weight > 0:
+            raise ValueError("Language model is not provided.")
 
     def forward(self, tn_output):
         if self.beam_size <= 1:
@@ -82,8 +90,44 @@ class TransducerBeamSearcher(torch.nn.Module):
         if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output):
             return False
         rnn, V = self.decode_network_lst[1].rnn, self.classifier_network[0].w.out_features
+        if self.lm_weight > 0 and not self._device_lm_ok(V):
+            return False
         return bool(2 <= self.beam_size <= V and 1 <= self.nbest <= 64 and self.cap >= self.beam_size and rnn.hidden_size <= 1024
                     and tn_output.shape[-1] <= 1024 and tn_output.shape[0] > 0 and tn_output.shape[1] > 0)
+
+    def _device_lm_ok(self, V):
+        """The LMs the device search fuses: an nnet.RNNLM in eval mode over the same V symbols with 1-4 LSTM layers, 0-2 dnn blocks with
+        LeakyReLU, and rnn_neurons, embedding_dim, dnn_neurons multiples of 4 up to 1024."""
+        from . import nnet
+        lm = self.lm
+        if not isinstance(lm, nnet.RNNLM) or not isinstance(lm.rnn, nnet.LSTM) or lm.training:
+            return False
+        rnn, emb, blocks = lm.rnn.rnn, lm.embedding, lm.dnn_layers()
+        size_ok = lambda n: 0 < n <= 1024 and n % 4 == 0  # noqa: E731
+        ok = (1 <= rnn.num_layers <= 4 and not rnn.bidirectional and getattr(rnn, "proj_size", 0) == 0 and size_ok(rnn.hidden_size)
+              and not emb.consider_as_one_hot and size_ok(emb.embedding_dim) and emb.num_embeddings == V and rnn.input_size == emb.embedding_dim
+              and len(blocks) <= 2 and lm.out.w.out_features == V and size_ok(lm.out.w.in_features)
+              and all(isinstance(b[0], nnet.Linear) and isinstance(b[1], nnet.LayerNorm) and isinstance(b[2], torch.nn.LeakyReLU)
+                      and b[0].w.out_features == lm.out.w.in_features and b[2].negative_slope == blocks[0][2].negative_slope for b in blocks)
+              and (blocks or lm.out.w.in_features == rnn.hidden_size))
+        return bool(ok)
+
+    def _device_lm_args(self, enc):
+        """The fused LM's tensors as ops.beam_search(lm=) takes them: matrices in the predictor's weight dtype (the bf16 shadows with
+        bf16 activations), the embedding table, biases and LayerNorm vectors fp32."""
+        from .ops import _bf16_weight
+        f = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+        w = (lambda t: _bf16_weight(t).contiguous()) if enc.dtype == torch.bfloat16 else f
+        lm = self.lm
+        rnn, blocks = lm.rnn.rnn, lm.dnn_layers()
+        layers = range(rnn.num_layers)
+        bias = lambda name: [f(getattr(rnn, f"{name}_l{l}")) if rnn.bias else None for l in layers]  # noqa: E731
+        return dict(emb=f(lm.embedding.Embedding.weight), w_ih=[w(getattr(rnn, f"weight_ih_l{l}")) for l in layers],
+                    w_hh=[w(getattr(rnn, f"weight_hh_l{l}")) for l in layers], b_ih=bias("bias_ih"), b_hh=bias("bias_hh"),
+                    w_dnn=[w(b[0].w.weight) for b in blocks], b_dnn=[f(b[0].w.bias) for b in blocks],
+                    ln_g=[f(b[1].norm.weight) for b in blocks], ln_b=[f(b[1].norm.bias) for b in blocks], ln_eps=[b[1].eps for b in blocks],
+                    w_out=w(lm.out.w.weight), b_out=f(lm.out.w.bias), slope=blocks[0][2].negative_slope if blocks else 0.01,
+                    weight=float(self.lm_weight))
 
     def _device_net_ok(self, tn_output):
         from . import nnet, rnnt
@@ -243,8 +287,9 @@ class TransducerBeamSearcher(torch.nn.Module):
     def _beam_host_loop(self, tn_output, timed=False):
         nbest_batch, nbest_scores, nbest_frames = [], [], []
         for b in range(tn_output.shape[0]):
-            # (prediction incl. the blank prefix, logp, predictor state); timed: + the emission frames of the prediction's tokens
-            beam = [([self.blank_id], 0.0, None, [])] if timed else [([self.blank_id], 0.0, None)]
+            # (prediction incl. the blank prefix, logp, predictor state); timed: + the emission frames of the prediction's tokens;
+            # LM fusion: + the LM's state, last
+            beam = [self._beam_start(timed)]
             for t in range(tn_output.shape[1]):
                 beam = self._beam_frame(beam, tn_output[b, t, :], t if timed else None)
             ranked = self._beam_rank(beam, timed)
@@ -256,10 +301,16 @@ class TransducerBeamSearcher(torch.nn.Module):
         out = best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
         return out + ([n[0] for n in nbest_frames], nbest_frames) if timed else out
 
+    def _beam_start(self, timed=False):
+        """The hypothesis a search starts from: ([blank], 0.0, no predictor state) + ([] if timed) + (no LM state if the LM is used)."""
+        return ([self.blank_id], 0.0, None) + (([],) if timed else ()) + ((None,) if self.lm_weight > 0 else ())
+
     def _beam_frame(self, A, enc_t, t=None):
-        """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it. ``t`` (not None: the hypotheses are
-        4-tuples that carry their frame lists) = absolute index of this frame, recorded for every token emitted here."""
+        """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it. ``t`` (not None: the hypotheses
+        carry their frame lists at index 3) = absolute index of this frame, recorded for every token emitted here. With the LM in use
+        the last element of a hypothesis is its LM state."""
         key = lambda hyp: hyp[1] / len(hyp[0])  # noqa: E731
+        use_lm = self.lm_weight > 0
         dev = enc_t.device
         frame = enc_t.view(1, 1, 1, -1)
         beam = []
@@ -275,12 +326,16 @@ class TransducerBeamSearcher(torch.nn.Module):
                 j = layer(j)
             logp, pos = torch.topk(F.log_softmax(j.float(), dim=-1).view(-1), k=self.beam_size)
             logp, pos = logp.tolist(), pos.tolist()      # one host read per expansion (the reference: one per symbol)
+            if use_lm:                                   # transducer.py:311-314, 386-409: the LM on a's last token from a's LM state
+                lm_logits, lm_state = self.lm(tok, hx=a[-1])
+                lm_logp = F.log_softmax(lm_logits.float(), dim=-1).view(-1).tolist()
             best_nonblank = logp[0] if pos[0] != self.blank_id else logp[1]
             for lp, sym in zip(logp, pos):
-                if sym == self.blank_id:
+                if sym == self.blank_id:                 # (a's frames and LM state travel in a[3:])
                     beam.append((a[0][:], a[1] + lp, a[2]) + a[3:])
                 elif lp >= best_nonblank - self.expand_beam:
-                    A.append((a[0] + [sym], a[1] + lp, new_state) + (() if t is None else (a[3] + [t],)))
+                    sc = (a[1] + lp) + self.lm_weight * lm_logp[sym] if use_lm else a[1] + lp
+                    A.append((a[0] + [sym], sc, new_state) + (() if t is None else (a[3] + [t],)) + ((lm_state,) if use_lm else ()))
         return beam
 
     def _beam_rank(self, beam, timed=False):
@@ -292,6 +347,8 @@ class TransducerBeamSearcher(torch.nn.Module):
 
     def _device_beam_call(self, enc, fn, *extra, **kw):
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
+        if self.lm_weight > 0:
+            kw["lm"] = self._device_lm_args(enc)
         return fn(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id, self.tjoint.nonlinearity.negative_slope, wdt, self.beam_size,
                   self.nbest, self.state_beam, self.expand_beam, self.cap, *extra, **kw)
 
@@ -345,6 +402,10 @@ class TransducerBeamSearcher(torch.nn.Module):
                 mf = int(max_frames or BEAM_STREAM_FRAMES)
                 size = ops.beam_stream_timed_workspace_bytes if timed else ops.beam_stream_workspace_bytes
                 nbytes = size(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
+                if self.lm_weight > 0:
+                    lm_rnn = self.lm.rnn.rnn
+                    nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size,
+                                                                self.cap, lm_rnn.num_layers, lm_rnn.hidden_size, timed)
                 state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf}
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")
@@ -363,7 +424,7 @@ class TransducerBeamSearcher(torch.nn.Module):
                 state["frames"] = nbest_frames
             return [n[0] for n in nbest_batch], state
         if state is None:
-            state = {"beams": [[([self.blank_id], 0.0, None) + (([],) if timed else ())] for _ in range(B)]}
+            state = {"beams": [[self._beam_start(timed)] for _ in range(B)]}
             if timed:
                 state["frames_done"] = [0] * B
         elif "beams" not in state:

@@ -28,6 +28,7 @@ ALIASES = {
     "speechbrain.nnet.linear.Linear": _PKG + ".nnet.Linear",
     "speechbrain.nnet.embedding.Embedding": _PKG + ".nnet.Embedding",
     "speechbrain.nnet.RNN.LSTM": _PKG + ".nnet.LSTM",
+    "speechbrain.lobes.models.RNNLM.RNNLM": _PKG + ".nnet.RNNLM",
     "speechbrain.nnet.transducer.transducer_joint.Transducer_joint": _PKG + ".rnnt.Transducer_joint",
     "speechbrain.nnet.losses.transducer_loss": _PKG + ".rnnt.transducer_loss",
     "speechbrain.nnet.schedulers.NoamScheduler": _PKG + ".core.NoamScheduler",

@@ -156,6 +156,80 @@ class LayerNorm(nn.Module):
         return ops.layer_norm(x, self.norm.weight, self.norm.bias, self.eps)
 
 
+class RNNLM(nn.Module):
+    """Recurrent language model (SB/lobes/models/RNNLM.py:15-122): embedding -> dropout -> ``rnn_layers`` recurrent layers -> ``dnn_blocks``
+    blocks of Linear, LayerNorm, activation, dropout -> Linear to the vocabulary. Constructor, call and state_dict keys are the
+    reference's (embedding.Embedding.weight, rnn.rnn.*, dnn.linear.w.*, dnn.norm.norm.*, out.w.*; the blocks after the first are named
+    linear_0, norm_0, ... as the reference's Sequential names repeated layers), so its LM checkpoints load with strict=True. Inference
+    and fine-tuning through the existing operators; the transducer beam search fuses it (decoders.TransducerBeamSearcher(lm_module=))."""
+
+    def __init__(self, output_neurons, embedding_dim=128, activation=nn.LeakyReLU, dropout=0.15, rnn_class=LSTM, rnn_layers=2,
+                 rnn_neurons=1024, rnn_re_init=False, return_hidden=False, dnn_blocks=1, dnn_neurons=512):
+        super().__init__()
+        self.embedding = Embedding(num_embeddings=output_neurons, embedding_dim=embedding_dim)
+        self.dropout = nn.Dropout(p=dropout)
+        self.rnn = rnn_class(input_size=embedding_dim, hidden_size=rnn_neurons, num_layers=rnn_layers, dropout=dropout, re_init=rnn_re_init)
+        self.return_hidden = return_hidden
+        self.reshape = False
+        self.dnn = nn.ModuleDict()
+        width = rnn_neurons
+        for _ in range(dnn_blocks):
+            for name, layer in (("linear", Linear(n_neurons=dnn_neurons, input_size=width, bias=True)), ("norm", LayerNorm(input_size=dnn_neurons)),
+                                ("act", activation()), ("dropout", nn.Dropout(p=dropout))):
+                if name in self.dnn:                     # the reference's Sequential.append: name, name_0, name_1, ...
+                    index = 0
+                    while f"{name}_{index}" in self.dnn:
+                        index += 1
+                    name = f"{name}_{index}"
+                self.dnn[name] = layer
+            width = dnn_neurons
+        self.out = Linear(input_size=dnn_neurons, n_neurons=output_neurons)
+
+    def dnn_layers(self):
+        """[(Linear, LayerNorm, activation, Dropout)] of the dnn blocks, in order."""
+        layers = list(self.dnn.values())
+        return [tuple(layers[i:i + 4]) for i in range(0, len(layers), 4)]
+
+    def _rnn(self, x, hx):
+        """The stacked LSTM through the exact-fp32 recurrence kernel, layer by layer (any depth, with or without an initial state:
+        hidden = (h, c), each [layers, B, H], as torch's); other recurrent classes are called as they are."""
+        rnn = getattr(self.rnn, "rnn", None)
+        if not (isinstance(self.rnn, LSTM) and ops.LSTM_F32_HIP and rnn.hidden_size <= 1024 and x.is_cuda):
+            return self.rnn(x, hx=hx)
+        hs, cs = [], []
+        y = x.float()
+        for l in range(rnn.num_layers):
+            w_ih, w_hh = getattr(rnn, f"weight_ih_l{l}"), getattr(rnn, f"weight_hh_l{l}")
+            b_ih, b_hh = (getattr(rnn, f"bias_ih_l{l}"), getattr(rnn, f"bias_hh_l{l}")) if rnn.bias else (None, None)
+            h0, c0 = (None, None) if hx is None else (hx[0][l], hx[1][l])
+            y, hn, cn = ops._LstmF32Fn.apply(y, w_ih, w_hh, b_ih, b_hh, h0, c0, torch.is_grad_enabled())
+            if self.training and rnn.dropout > 0 and l + 1 < rnn.num_layers:
+                y = F.dropout(y, rnn.dropout, True)
+            hs.append(hn)
+            cs.append(cn)
+        return y.to(x.dtype), (torch.stack(hs), torch.stack(cs))
+
+    def forward(self, x, hx=None):
+        x = self.dropout(self.embedding(x))
+        if x.dim() == 2:                                 # inference: add the time axis (the flag stays set, as in the reference)
+            x = x.unsqueeze(1)
+            self.reshape = True
+        x, hidden = self._rnn(x, hx)
+        for linear, norm, act, drop in self.dnn_layers():
+            x = linear(x)
+            if norm.norm.weight.numel() % 8:             # (the row kernels take widths that are multiples of 8)
+                ops.lib_fallback("layer_norm", f"width {norm.norm.weight.numel()} is no multiple of 8")
+                x = drop(act(F.layer_norm(x.float(), norm.norm.normalized_shape, norm.norm.weight, norm.norm.bias, norm.eps))).to(x.dtype)
+            elif isinstance(act, nn.LeakyReLU):          # LayerNorm and the LeakyReLU behind it: one launch
+                x = drop(ops.layer_norm(x, norm.norm.weight, norm.norm.bias, norm.eps, act_slope=act.negative_slope))
+            else:
+                x = drop(act(norm(x)))
+        out = self.out(x)
+        if self.reshape:
+            out = out.squeeze(1)
+        return (out, hidden) if self.return_hidden else out
+
+
 # ------------------------------------------------------------------------------------------------------
 # A1 / A2 features
 # ------------------------------------------------------------------------------------------------------

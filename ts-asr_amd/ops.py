@@ -36,6 +36,8 @@ STATUS = {
                                                   "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
     "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search / beam_search_stream, one launch per batch or chunk; "
                                                          "the host loop only for other predictor shapes and utterances past cap)",
+    "beam search with LM fusion (lm_module, lm_weight > 0)": "HIP (search.hip: beam_search_lm, an nnet.RNNLM with an LSTM fused into the same launch); "
+                                                             "the host loop for every other LM",
     "WER / CER statistics (VALID / TEST stages)": "HIP (editdist.hip: edit_distance, one launch per searched batch; metrics.ErrorRateStats)",
 }
 
@@ -2345,6 +2347,67 @@ def beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap):
     return beam_stream_workspace_bytes(B, T, H, J, beam, cap) + B * a16(4 * (1 + (T + 1) * beam + cap))
 
 
+def beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, lm_layers, lm_hidden, times=False):
+    """Bytes of the LM-fused searches' workspace (``lm=``): every predictor slot also holds the node's LM step, 64 + 2 * lm_layers *
+    lm_hidden floats (lm_logp | lm_h | lm_c); ``times``: the timed layout."""
+    B, T, H, J, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, beam, cap, lm_layers, lm_hidden))
+    if min(B, T, H, J, beam, cap, Ll, Hl) <= 0:
+        return 0
+    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
+    return base + B * 4 * (cap + beam) * (64 + 2 * Ll * Hl)
+
+
+_LM_KEYS = ("emb", "w_ih", "w_hh", "b_ih", "b_hh", "w_dnn", "b_dnn", "ln_g", "ln_b", "ln_eps", "w_out", "b_out", "slope", "weight")
+
+
+def _beam_lm_desc(lm, V, wdtype):
+    """(C.LmDesc, lm_weight, layers, hidden) of an ``lm=`` dict: emb fp32 [V, E]; per LSTM layer w_ih / w_hh (weight dtype) and b_ih /
+    b_hh (fp32 or None); per dnn block w_dnn, b_dnn, ln_g, ln_b, ln_eps; w_out [V, D], b_out; slope (LeakyReLU); weight (lm_weight).
+    Dtypes, the vocabulary and the shapes' consistency are checked here (ValueError); which sizes the kernel takes, the launcher says."""
+    if not isinstance(lm, dict) or any(k not in lm for k in _LM_KEYS):
+        raise ValueError(f"beam_search: lm must be a dict with the keys {_LM_KEYS}")
+    want_w = torch.float32 if wdtype == C.F32 else torch.bfloat16
+    nl, nb = len(lm["w_ih"]), len(lm["w_dnn"])
+    if nl < 1 or any(len(lm[k]) != nl for k in ("w_hh", "b_ih", "b_hh")) or any(len(lm[k]) != nb for k in ("b_dnn", "ln_g", "ln_b", "ln_eps")):
+        raise ValueError("beam_search: lm lists of unequal length")
+    emb, w_out = lm["emb"], lm["w_out"]
+    mats = list(lm["w_ih"]) + list(lm["w_hh"]) + list(lm["w_dnn"]) + [w_out]
+    if any(m.dtype != want_w or m.dim() != 2 or not m.is_contiguous() for m in mats):
+        raise ValueError(f"beam_search: the LM's matrices must be contiguous 2-D {want_w}")
+    vecs = [v for k in ("b_ih", "b_hh", "b_dnn", "ln_g", "ln_b") for v in lm[k]] + [lm["b_out"]]
+    if emb.dtype != torch.float32 or emb.dim() != 2 or not emb.is_contiguous() or any(
+            v is not None and (v.dtype != torch.float32 or not v.is_contiguous()) for v in vecs):
+        raise ValueError("beam_search: the LM's embedding table, biases and LayerNorm vectors must be contiguous fp32")
+    Hl, E = lm["w_hh"][0].shape[1], emb.shape[1]
+    D = lm["w_dnn"][0].shape[0] if nb else Hl
+    ok = emb.shape[0] == V and tuple(w_out.shape) == (V, D) and (lm["b_out"] is None or lm["b_out"].numel() == V)
+    for l in range(nl):
+        ok = ok and tuple(lm["w_ih"][l].shape) == (4 * Hl, E if l == 0 else Hl) and tuple(lm["w_hh"][l].shape) == (4 * Hl, Hl)
+        ok = ok and all(b is None or b.numel() == 4 * Hl for b in (lm["b_ih"][l], lm["b_hh"][l]))
+    for k in range(nb):
+        ok = ok and tuple(lm["w_dnn"][k].shape) == (D, Hl if k == 0 else D)
+        ok = ok and all(v is None or v.numel() == D for v in (lm["b_dnn"][k], lm["ln_g"][k], lm["ln_b"][k]))
+    if not ok:
+        raise ValueError(f"beam_search: the LM's shapes do not fit V={V} E={E} hidden={Hl} dnn={D}")
+    d = C.LmDesc()
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d.emb, d.w_out, d.b_out = p(emb), p(w_out), p(lm["b_out"])
+    for l in range(min(nl, 4)):
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = p(lm["w_ih"][l]), p(lm["w_hh"][l]), p(lm["b_ih"][l]), p(lm["b_hh"][l])
+    for k in range(min(nb, 2)):
+        d.w_dnn[k], d.b_dnn[k], d.ln_g[k], d.ln_b[k], d.ln_eps[k] = p(lm["w_dnn"][k]), p(lm["b_dnn"][k]), p(lm["ln_g"][k]), p(lm["ln_b"][k]), float(lm["ln_eps"][k])
+    d.layers, d.hidden, d.emb_dim, d.dnn_blocks, d.dnn_neurons, d.slope = nl, Hl, E, nb, D, float(lm["slope"])
+    return d, float(lm["weight"]), nl, Hl
+
+
+def _beam_lm_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope,
+                    wdtype, fr, desc, weight):
+    """tsasr_beam_search_lm's return code (0: launched): n_valid None = the offline search, fr None = untimed."""
+    return C.lib().tsasr_beam_search_lm(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size),
+                                        int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
+                                        wdtype, C.stream_ptr(), C.ptr(fr), C.ctypes.byref(desc), float(weight))
+
+
 def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype):
     """Shapes and settings tsasr_beam_search takes (ValueError before any device call)."""
     if not isinstance(enc, torch.Tensor) or enc.dim() != 3 or enc.dtype not in (torch.float32, torch.bfloat16):
@@ -2415,15 +2478,20 @@ def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
 
 
 def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                workspace=None, frames=False):
+                workspace=None, frames=False, lm=None):
     """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
     lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
     n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap).
     ``frames=True`` (tsasr_beam_search_timed): a fourth value, the n-best lists of the encoder frame that emitted each token; the
-    workspace then has beam_stream_timed_workspace_bytes; the first three values are the bits of the untimed call."""
+    workspace then has beam_stream_timed_workspace_bytes; the first three values are the bits of the untimed call.
+    ``lm`` (tsasr_beam_search_lm): a dict of the fused LM's tensors (_beam_lm_desc) with its weight; the workspace then has
+    beam_stream_lm_workspace_bytes."""
     _no_grad_only("beam_search")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, T, H, J, beam_size, cap)
+    if lm is not None:
+        desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
+        need = beam_stream_lm_workspace_bytes(B, T, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames))
     if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
         raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
     C.require_gpu(enc, table, *mats)
@@ -2436,6 +2504,10 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
         tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
                 C.io_dtype(encc), wdtype, C.stream_ptr())
         outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
+        if lm is not None:
+            C.check(_beam_lm_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
+                                    state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight), "tsasr_beam_search_lm")
+            return
         if frames:
             tail += (C.ptr(fr),)
             stream_fn, fn, sfx = C.lib().tsasr_beam_search_stream_timed, C.lib().tsasr_beam_search_timed, "_timed"
@@ -2451,14 +2523,18 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
 
 
 def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                       workspace, n_valid, max_frames, frames=False):
+                       workspace, n_valid, max_frames, frames=False, lm=None):
     """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
     (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
     beam_search returns, for the beam after the chunk. ``frames=True`` (tsasr_beam_search_stream_timed): also the n-best frame lists,
-    absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed."""
+    absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed.
+    ``lm``: as in beam_search; the workspace has beam_stream_lm_workspace_bytes and every call of the stream carries the same LM."""
     _no_grad_only("beam_search_stream")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, max_frames, H, J, beam_size, cap)
+    if lm is not None:
+        desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
+        need = beam_stream_lm_workspace_bytes(B, max_frames, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames))
     if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
         raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
     if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
@@ -2470,6 +2546,11 @@ def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slop
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
 
     def run(hyps, lens, scores, status, Lmax, readout, fr):
+        if lm is not None:
+            C.check(_beam_lm_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,
+                                    max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr,
+                                    desc, lm_weight), "tsasr_beam_search_lm")
+            return
         fn, extra = (C.lib().tsasr_beam_search_stream_timed, (C.ptr(fr),)) if frames else (C.lib().tsasr_beam_search_stream, ())
         C.check(fn(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status), B, T,
                    int(max_frames), J, H, E, V, int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam),
