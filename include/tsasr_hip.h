@@ -68,6 +68,21 @@ int tsasr_joint_bwd(const float *dlogits, const void *enc, const void *dec, cons
                     int B, int T, int U1, int J, int V, int ldl, int io_dtype, float slope,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same joint + head for subword vocabularies, 32 < V <= 1024 (csrc/joint_wide.hip): the head matrix is streamed from the fp32 masters
+ * in 32-row vocabulary tiles inside the kernels, h and W rounded to bf16 for the matrix cores (backward: dlogits too), sums in fp32.
+ * J % 32 == 0, J <= 1024. Forward: ldl % 32 == 0, ldl >= V, columns >= V written as 0 (ldl = V rounded up to 32 is what the host passes).
+ * Backward: any ldl % 4 == 0, ldl >= V; outputs, tlen / ulen, deferral of dW / dbias and bitwise reproducibility as the narrow call. The
+ * workspace (which depends on V here) holds partial sums of denc / ddec and at most 64 slabs of dW (128 MiB of them at most). io_dtype TSASR_F32 stores fp32
+ * activations and still rounds the operands to bf16: there is no exact-fp32 wide joint. */
+int tsasr_joint_wide_fwd(const void *enc, const void *dec, const float *W, const float *bias, float *logits,
+                         int B, int T, int U1, int J, int V, int ldl, int io_dtype, float slope, void *stream);
+size_t tsasr_joint_wide_bwd_workspace_bytes(int B, int T, int U1, int J, int V);
+int tsasr_joint_wide_bwd(const float *dlogits, const void *enc, const void *dec, const float *W,
+                         void *denc, void *ddec, float *dW, float *dbias,
+                         const int32_t *tlen, const int32_t *ulen,
+                         int B, int T, int U1, int J, int V, int ldl, int io_dtype, float slope,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * RNN-T loss  (replaces SB/nnet/losses.py:29-87 `transducer_loss` -> torchaudio.functional.rnnt_loss,
  * call site train_librispeechmix_scratch.py:158-160; lattice math as SB/nnet/loss/transducer_loss.py:60-236)
@@ -538,6 +553,17 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
                                const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
                                const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
                                float slope, int io_dtype, int wdtype, void *stream);
+
+/* The two greedy searches for subword vocabularies (csrc/search.hip greedy_decode_wide_kernel): arguments, outputs and the stream state
+ * [B, 2H + J + 4] of the two calls above, with V <= 1024 and E <= 1024 (a one-hot table has E = V - 1; E % 4 == 0 runs a dense product, any
+ * other E adds the columns of w_ih that meet a non-zero entry of the embedding row). The arg max takes the lowest index among ties. */
+int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
+                             int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream);
+int tsasr_greedy_decode_stream_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                                    const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
+                                    const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
+                                    float slope, int io_dtype, int wdtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beam transducer search on the device (SB/decoders/transducer.py:220-373, transducer_beam_search_decode, no LM fusion) for the networks

@@ -38,6 +38,9 @@ _PROTOS = {
     "tsasr_joint_f32_bwd": (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_float, c_void_p, c_size_t, c_void_p]),
     "tsasr_joint_bwd_workspace_bytes": (c_size_t, [c_int] * 4),
     "tsasr_joint_bwd": (c_int, [c_void_p] * 10 + [c_int] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "tsasr_joint_wide_fwd": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float, c_void_p]),
+    "tsasr_joint_wide_bwd_workspace_bytes": (c_size_t, [c_int] * 5),
+    "tsasr_joint_wide_bwd": (c_int, [c_void_p] * 10 + [c_int] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
     "tsasr_rnnt_loss_workspace_bytes": (c_size_t, [c_int] * 3),
     "tsasr_rnnt_loss_error_word_offset": (ctypes.c_longlong, [c_int] * 3),
     "tsasr_rnnt_lattice_plan": (None, [c_int] * 3),
@@ -145,6 +148,8 @@ _PROTOS = {
     "tsasr_inject_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "tsasr_greedy_decode": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
     "tsasr_greedy_decode_stream": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
+    "tsasr_greedy_decode_wide": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
+    "tsasr_greedy_decode_stream_wide": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
     "tsasr_beam_search_workspace_bytes": (c_size_t, [c_int] * 6),
     "tsasr_beam_search": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
     "tsasr_beam_search_stream": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),

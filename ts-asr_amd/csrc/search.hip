@@ -207,6 +207,134 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
 }
 
 
+// The greedy search for subword vocabularies (64 <= V <= 1024, or an embedding wider than 64 columns): a sibling of greedy_decode_kernel, which
+// stays as it is for the character models (one-wave arg max, the embedding as a 64-column side operand). Differences: `logits` holds V floats
+// and the arg max (lowest index among ties) and the sum of its log-softmax term are reduced over the workgroup's 16 waves in wave order; the
+// embedding row x = emb[token] (E <= 1024) enters the gates as a second product: a dense one (gemv_rows_acc) when the rows of W_ih are
+// 16-byte pieces (E % 4 == 0, a learned embedding), otherwise one thread per gate row adds W_ih[r][e] * x[e] over the NON-ZERO x[e] only -
+// for the frozen one-hot table (E = V - 1) that is one column of W_ih per token. State layout and LDS prefix (h | c | pn) as the narrow kernel.
+template <typename T, typename WT, bool STREAM>
+__global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_wide_kernel(const GreedyArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float gs[];
+    const int Ep = (A.E + 3) & ~3, Vp = (A.V + 3) & ~3;
+    float *h = gs, *c = h + A.H, *pn = c + A.H, *z = pn + A.J, *gates = z + A.J, *x = gates + 4 * A.H, *logits = x + Ep, *red = logits + Vp;
+    int *redi = reinterpret_cast<int *>(red + 16);      // red[16] wave maxima | redi[16] wave candidates | reds[16] wave sums | flag
+    float *reds = red + 32, *flag = red + 48;
+    __shared__ int s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T *enc = (const T *)A.enc + (size_t)b * A.T * A.J;
+    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
+    float lsum = 0.f;
+    int tbeg = -1, tend = A.T;
+    float *st = nullptr;
+    if (STREAM) {
+        const int S = 2 * A.H + A.J + 4;
+        st = A.state + (size_t)b * S;
+        tend = min(max(A.n_valid[b], 0), A.T);
+        for (int t = tid; t < A.T; t += GREEDY_THREADS)
+            if (t >= tend) A.preds[(size_t)b * A.T + t] = -1;
+        if (tend == 0) {                            // workgroup-uniform: nothing to decode, the state stays as it is
+            if (tid == 0) A.logp_sum[b] = st[2 * A.H + A.J + 1];
+            return;
+        }
+        const bool primed = st[2 * A.H + A.J + 2] != 0.f;
+        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) gs[i] = st[i];
+        if (tid == 0) s_tok = primed ? (int)st[2 * A.H + A.J] : A.blank;
+        lsum = st[2 * A.H + A.J + 1];
+        if (primed) tbeg = 0;
+    } else {
+        for (int i = tid; i < A.H; i += GREEDY_THREADS) h[i] = c[i] = 0.f;
+        if (tid == 0) s_tok = A.blank;
+    }
+    __syncthreads();
+    for (int t = tbeg; t < tend; ++t) {
+        int tok = s_tok;
+        bool advance = (t < 0);
+        if (t >= 0) {
+            for (int k = tid; k < A.J; k += GREEDY_THREADS) {
+                const float v = ld1(enc + (size_t)t * A.J + k) + pn[k];
+                z[k] = v > 0.f ? v : v * A.slope;
+            }
+            __syncthreads();
+            gemv_rows<WT>(w_head, A.V, A.J, z, A.b_head, nullptr, nullptr, 0, nullptr, logits);
+            __syncthreads();
+            const float v = tid < A.V ? logits[tid] : -INFINITY;      // V <= GREEDY_THREADS: one vocabulary entry per thread
+            const float wm = wave_max(v);
+            if (lane == 0) red[wave] = wm;
+            __syncthreads();
+            float m = red[0];
+#pragma unroll
+            for (int w = 1; w < GREEDY_THREADS / 64; ++w) m = fmaxf(m, red[w]);
+            const unsigned long long eq = __ballot(v == m && tid < A.V);
+            const float ws = wave_sum(tid < A.V ? __expf(v - m) : 0.f);
+            if (lane == 0) {
+                redi[wave] = eq ? wave * 64 + __ffsll((long long)eq) - 1 : 0x7fffffff;
+                reds[wave] = ws;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int pos = redi[0];
+                float s = reds[0];
+#pragma unroll
+                for (int w = 1; w < GREEDY_THREADS / 64; ++w) {
+                    pos = min(pos, redi[w]);
+                    s += reds[w];
+                }
+                const bool emit = pos != A.blank && pos < A.V;
+                A.preds[(size_t)b * A.T + t] = emit ? pos : -1;
+                if (emit) { lsum += -__logf(s); s_tok = pos; }
+                *flag = emit ? 1.f : 0.f;
+            }
+            __syncthreads();
+            advance = *flag != 0.f;
+            tok = s_tok;
+        }
+        if (advance) {                          // workgroup-uniform
+            for (int e = tid; e < A.E; e += GREEDY_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
+            __syncthreads();
+            if (A.E <= 64) {
+                gemv_rows<WT>(w_hh, 4 * A.H, A.H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
+            } else {
+                gemv_rows<WT>(w_hh, 4 * A.H, A.H, h, A.b_ih, A.b_hh, nullptr, 0, nullptr, gates);
+                __syncthreads();
+                if (A.E % 4 == 0) {
+                    gemv_rows_acc<WT>(w_ih, 4 * A.H, A.E, x, gates);
+                } else {
+                    for (int r = tid; r < 4 * A.H; r += GREEDY_THREADS) {
+                        float acc = 0.f;
+                        for (int e = 0; e < A.E; ++e) {
+                            const float xe = x[e];                     // the same LDS word for every thread: a uniform branch
+                            if (xe != 0.f) acc += (float)w_ih[(size_t)r * A.E + e] * xe;
+                        }
+                        gates[r] += acc;
+                    }
+                }
+            }
+            __syncthreads();
+            for (int u = tid; u < A.H; u += GREEDY_THREADS) {
+                const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[A.H + u]), gg = tanhf(gates[2 * A.H + u]), og = sigmoid_f(gates[3 * A.H + u]);
+                const float cn = fg * c[u] + ig * gg;
+                c[u] = cn;
+                h[u] = og * tanhf(cn);
+            }
+            __syncthreads();
+            gemv_rows<WT>(w_proj, A.J, A.H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
+            __syncthreads();
+        }
+    }
+    if (tid == 0) A.logp_sum[b] = lsum;
+    if (STREAM) {
+        __syncthreads();
+        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) st[i] = gs[i];
+        if (tid == 0) {
+            st[2 * A.H + A.J] = (float)s_tok;
+            st[2 * A.H + A.J + 1] = lsum;
+            st[2 * A.H + A.J + 2] = 1.f;
+        }
+    }
+}
+
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Beam transducer search (speechbrain/decoders/transducer.py:220-373, restated in decoders.py's host loop and oracle beam_decode): one
 // persistent workgroup per utterance. Per frame, A = hypotheses to extend (the last frame's beam), beam = those that emitted blank here.
@@ -750,6 +878,61 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
 #undef GREEDY
     TSASR_CHECK_LAUNCH("tsasr_greedy_decode_stream");
     return 0;
+}
+
+/* The two greedy searches for subword vocabularies: the arguments, outputs and stream state of tsasr_greedy_decode / _stream with
+ * V <= 1024 and E <= 1024 (a frozen one-hot table has E = V - 1: any E is taken, a multiple of 4 runs the dense product). n_valid / state NULL:
+ * the one-call form. The narrow entry points and their kernels are untouched; the host sends V <= 63 with E <= 64 there. */
+static int greedy_wide_launch(const char *name, const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih,
+                              const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
+                              const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope,
+                              int io_dtype, int wdtype, void *stream) {
+    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && preds && logp_sum, "%s: null pointer", name);
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 1024 && V > 1 && V <= 1024 && blank >= 0 && blank < V,
+                    "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
+    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
+    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
+    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + ((E + 3) & ~3) + ((V + 3) & ~3) + 64) * sizeof(float);
+    TSASR_CHECK_ARG(lds <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d need %zu B of LDS", name, H, J, E, V, lds);
+    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope, state, n_valid};
+    hipStream_t st = (hipStream_t)stream;
+#define GREEDY(TT, WW)                                                                                                            \
+    {                                                                                                                             \
+        if (state) {                                                                                                              \
+            auto kern = greedy_decode_wide_kernel<TT, WW, true>;                                                                  \
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                              \
+        } else {                                                                                                                  \
+            auto kern = greedy_decode_wide_kernel<TT, WW, false>;                                                                 \
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                              \
+        }                                                                                                                         \
+    }
+    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) GREEDY(float, float) else GREEDY(float, bf16_t) }
+    else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
+#undef GREEDY
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        tsasr_set_error("%s: launch failed: %s", name, hipGetErrorString(e));
+        return TSASR_E_LAUNCH;
+    }
+    return 0;
+}
+
+int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
+                             int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream) {
+    return greedy_wide_launch("tsasr_greedy_decode_wide", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, nullptr, nullptr, preds,
+                              logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
+}
+
+int tsasr_greedy_decode_stream_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                                    const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
+                                    const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
+                                    float slope, int io_dtype, int wdtype, void *stream) {
+    TSASR_CHECK_ARG(state && n_valid, "tsasr_greedy_decode_stream_wide: null pointer");
+    return greedy_wide_launch("tsasr_greedy_decode_stream_wide", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, state, n_valid,
+                              preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
 /* Beam transducer search (speechbrain/decoders/transducer.py:220-373, no LM) for the networks tsasr_greedy_decode takes; see the kernel's

@@ -28,6 +28,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
+GREEDY_WIDE_MAX = 1024          # vocabulary and embedding columns the device greedy search takes (csrc/search.hip greedy_decode_wide_kernel)
 BEAM_CAP = 512                  # hypotheses one frame of the device beam search may hold (its A list); past it: the host loop
 BEAM_STREAM_FRAMES = 4096       # frames a beam_stream workspace is laid out for when the caller does not say
 BEAM_HOST_REDECODES = {"utterances": 0}     # utterances the device beam search handed back to the host loop (status != 0)
@@ -78,16 +79,24 @@ class TransducerBeamSearcher(torch.nn.Module):
         return proj(out), hidden
 
     def _device_greedy_ok(self, tn_output):
-        """The one-launch device decoder (csrc/search.hip) covers the recipes' networks: one-hot or learned embedding (<= 64 columns),
-        one-layer unidirectional LSTM, Linear projection, joint = LeakyReLU(sum), one Linear classifier."""
+        """The one-launch device decoder (csrc/search.hip) covers the recipes' networks: one-hot or learned embedding, one-layer
+        unidirectional LSTM, Linear projection, joint = LeakyReLU(sum), one Linear classifier. Character models (V <= 63, embedding <= 64
+        columns) run the narrow kernel, subword models up to V = 1024 and 1024 embedding columns its wide sibling."""
         if os.environ.get("TSASR_GREEDY_KERNEL", "1") == "0":
             return False
-        return self._device_net_ok(tn_output)
+        if not self._device_net_ok(tn_output, GREEDY_WIDE_MAX, GREEDY_WIDE_MAX):
+            return False
+        # the launchers' own limits (hidden size and joint dimension up to 1024; the kernel's LDS then always fits): a network past them
+        # decodes through the host loop instead of meeting the entry point's argument check
+        return bool(self.decode_network_lst[1].rnn.hidden_size <= 1024 and tn_output.shape[-1] <= 1024)
+
+    def _greedy_is_wide(self):
+        return self.decode_network_lst[0].embedding_dim > 64 or self.classifier_network[0].w.out_features > 63
 
     def _device_beam_ok(self, tn_output):
         """The one-launch device beam search (csrc/search.hip) takes the networks the greedy decoder takes, with 2 <= beam_size <= V,
         nbest <= 64 and cap >= beam_size; TSASR_BEAM_KERNEL=0 sends every call to the host loop."""
-        if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output):
+        if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output, 64, 63):
             return False
         rnn, V = self.decode_network_lst[1].rnn, self.classifier_network[0].w.out_features
         if self.lm_weight > 0 and not self._device_lm_ok(V):
@@ -129,7 +138,9 @@ class TransducerBeamSearcher(torch.nn.Module):
                     w_out=w(lm.out.w.weight), b_out=f(lm.out.w.bias), slope=blocks[0][2].negative_slope if blocks else 0.01,
                     weight=float(self.lm_weight))
 
-    def _device_net_ok(self, tn_output):
+    def _device_net_ok(self, tn_output, emb_max, vocab_max):
+        """The network shape csrc/search.hip takes, with the caller's limits on the embedding width and the vocabulary: the beam search
+        (and LM fusion) stops at 64 columns / V = 63, above which it keeps the host loop; the greedy search goes to GREEDY_WIDE_MAX."""
         from . import nnet, rnnt
         if not tn_output.is_cuda or tn_output.dtype not in (torch.float32, torch.bfloat16):
             return False
@@ -139,7 +150,7 @@ class TransducerBeamSearcher(torch.nn.Module):
         head = self.classifier_network[0]
         ok = (isinstance(emb, nnet.Embedding) and isinstance(dec, nnet.LSTM) and isinstance(proj, nnet.Linear) and isinstance(head, nnet.Linear)
               and isinstance(self.tjoint, rnnt.Transducer_joint) and isinstance(self.tjoint.nonlinearity, torch.nn.LeakyReLU)
-              and dec.rnn.num_layers == 1 and not dec.rnn.bidirectional and emb.embedding_dim <= 64 and head.w.out_features <= 63
+              and dec.rnn.num_layers == 1 and not dec.rnn.bidirectional and emb.embedding_dim <= emb_max and head.w.out_features <= vocab_max
               and dec.rnn.hidden_size % 4 == 0 and proj.w.out_features % 4 == 0 and proj.w.out_features == tn_output.shape[-1])
         return bool(ok)
 
@@ -152,10 +163,11 @@ class TransducerBeamSearcher(torch.nn.Module):
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
         preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
         logp = torch.empty(B, dtype=torch.float32, device=enc.device)
-        C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                            C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, rnn.hidden_size,
-                                            table.shape[1], mats[3].shape[0], int(self.blank_id), float(self.tjoint.nonlinearity.negative_slope),
-                                            C.io_dtype(enc), wdt, C.stream_ptr()), "tsasr_greedy_decode")
+        name = "tsasr_greedy_decode_wide" if self._greedy_is_wide() else "tsasr_greedy_decode"
+        C.check(getattr(C.lib(), name)(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                       C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, rnn.hidden_size,
+                                       table.shape[1], mats[3].shape[0], int(self.blank_id), float(self.tjoint.nonlinearity.negative_slope),
+                                       C.io_dtype(enc), wdt, C.stream_ptr()), name)
         if timed:
             hyps, frames = self._unpack_preds(preds)
             return hyps, logp.exp().mean(), None, None, frames, None

@@ -22,6 +22,10 @@ STATUS = {
     "frontend block 2 (bf16, C_out = 128)": "HIP implicit GEMMs (conv_s2_fwd / conv_s2_wgrad / conv_s2_dgrad)",
     "matmul(bf16)": "HIP (gemm_bf16: fwd, dgrad, wgrad-into-arena)", "matmul(fp32 parity mode)": "HIP (gemm_f32: fp32 matrix cores; fwd, dgrad, wgrad)", "lstm(bf16 training)": "HIP persistent whole-sequence kernels (per-step kernels for other H)", "lstm(decoding / fp32 parity)": "HIP (lstm_f32: exact fp32, optional initial state)",
     "attention(fp32 parity, cross_attention injection)": "HIP (attention_f32: exact fp32)", "joint(fp32 parity)": "HIP (joint_f32)",
+    "joint(32 < V <= 1024: subword vocabularies)": "HIP (joint_wide.hip: vocabulary tiles inside the kernels; bf16-rounded h / W / dlogits with bf16 OR fp32 activations - "
+                                                   "an exact-fp32 wide joint is not built: compute_dtype fp32 with V > 32 runs these kernels with fp32 storage)",
+    "greedy search (V <= 1024, embedding <= 1024 columns)": "HIP (search.hip: greedy_decode_kernel for V <= 63 / E <= 64, greedy_decode_wide_kernel above)",
+    "beam search / LM fusion with V > 63": "host loop over device-side predictor / joint steps (the device search stops at V = 63)",
     "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP", "fbank_frames": "HIP", "running_norm": "HIP (features_stream.hip)",
     "relpos_attention": "HIP (forward: everything-in-LDS kernel for T <= 256 and, per chunk of 256 keys, for long sequences in small batches, streaming kernel otherwise; backward = query-major, key-major, d(pk) and partial-sum kernels)",
     # What is NOT hand-written: shapes / modes none of the three recipes reaches. Each of these routes goes through lib_fallback(): counted in
@@ -2315,10 +2319,12 @@ def greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_
     preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
     logp = torch.empty(B, dtype=torch.float32, device=enc.device)
     nv = n_valid.to(torch.int32).contiguous()
-    C.check(C.lib().tsasr_greedy_decode_stream(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                               C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(state), C.ptr(nv), C.ptr(preds), C.ptr(logp),
-                                               B, T, J, H, table.shape[1], mats[3].shape[0], int(blank), float(slope), C.io_dtype(enc), wdtype,
-                                               C.stream_ptr()), "tsasr_greedy_decode_stream")
+    # character models keep the narrow kernel; subword vocabularies (V > 63) or embeddings past 64 columns run its wide sibling (same state)
+    name = "tsasr_greedy_decode_stream_wide" if table.shape[1] > 64 or mats[3].shape[0] > 63 else "tsasr_greedy_decode_stream"
+    C.check(getattr(C.lib(), name)(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                   C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(state), C.ptr(nv), C.ptr(preds), C.ptr(logp),
+                                   B, T, J, H, table.shape[1], mats[3].shape[0], int(blank), float(slope), C.io_dtype(enc), wdtype,
+                                   C.stream_ptr()), name)
     return preds, logp
 
 

@@ -12,6 +12,7 @@ from . import _capi as C
 from . import prof
 
 _LDL = 32  # logits rows are padded to 32 floats (128 B) so that every row access is a 16-byte multiple
+WIDE_VMAX, WIDE_JMAX = 1024, 1024   # csrc/joint_wide.hip: 32 < V <= 1024 (rows padded to the next multiple of 32 floats), J % 32 == 0, J <= 1024
 JOINT_F32_EXACT = True   # fp32 activations: joint + head in exact fp32 arithmetic (csrc/joint_f32.hip). False: the MFMA kernels with fp32
                          # storage and bf16-rounded operands (tests that cover that instantiation switch it off)
 
@@ -35,10 +36,18 @@ class _JointLogitsFn(torch.autograd.Function):
         B, T, J = enc.shape
         U1 = dec.shape[1]
         V = w32.shape[0]
-        buf = torch.empty(B, T, U1, _LDL, dtype=torch.float32, device=enc.device)
+        ctx.wide = V > _LDL
+        if ctx.wide and (V > WIDE_VMAX or J % 32 or J > WIDE_JMAX):
+            raise ValueError(f"fused joint: vocabulary {V} / joint dimension {J} outside the wide kernels' range "
+                             f"(V <= {WIDE_VMAX}, J a multiple of 32 <= {WIDE_JMAX})")
+        ldl = (V + 31) // 32 * 32 if ctx.wide else _LDL
+        buf = torch.empty(B, T, U1, ldl, dtype=torch.float32, device=enc.device)
         ctx.exact = _exact(enc, J, V)
         with prof.region("joint_fwd"):
-            if ctx.exact:
+            if ctx.wide:     # subword vocabularies: vocabulary tiles inside the kernel; fp32 activations keep fp32 storage, operands rounded to bf16
+                C.check(C.lib().tsasr_joint_wide_fwd(C.ptr(enc), C.ptr(dec), C.ptr(w32), C.ptr(b32), C.ptr(buf), B, T, U1, J, V, ldl,
+                                                     C.io_dtype(enc), float(slope), C.stream_ptr()), "tsasr_joint_wide_fwd")
+            elif ctx.exact:
                 C.check(C.lib().tsasr_joint_f32_fwd(C.ptr(enc), C.ptr(dec), C.ptr(w32), C.ptr(b32), C.ptr(buf), B, T, U1, J, V, _LDL,
                                                     float(slope), C.stream_ptr()), "tsasr_joint_f32_fwd")
             else:
@@ -58,10 +67,17 @@ class _JointLogitsFn(torch.autograd.Function):
         denc, ddec = torch.empty_like(enc), torch.empty_like(dec)
         dW = torch.empty(V, J, dtype=torch.float32, device=enc.device)
         db = torch.empty(V, dtype=torch.float32, device=enc.device)
-        nws = C.lib().tsasr_joint_f32_bwd_workspace_bytes(B, U1, J) if ctx.exact else C.lib().tsasr_joint_bwd_workspace_bytes(B, T, U1, J)
+        if ctx.wide:
+            nws = C.lib().tsasr_joint_wide_bwd_workspace_bytes(B, T, U1, J, V)
+        else:
+            nws = C.lib().tsasr_joint_f32_bwd_workspace_bytes(B, U1, J) if ctx.exact else C.lib().tsasr_joint_bwd_workspace_bytes(B, T, U1, J)
         ws = _ws(nws, enc.device)
         with prof.region("joint_bwd"):
-            if ctx.exact:
+            if ctx.wide:
+                C.check(C.lib().tsasr_joint_wide_bwd(C.ptr(dl), C.ptr(enc), C.ptr(dec), C.ptr(w32), C.ptr(denc), C.ptr(ddec), C.ptr(dW), C.ptr(db),
+                                                     C.ptr(tlen), C.ptr(ulen), B, T, U1, J, V, dl.stride(-2), C.io_dtype(enc), ctx.slope,
+                                                     C.ptr(ws), ws.numel(), C.stream_ptr()), "tsasr_joint_wide_bwd")
+            elif ctx.exact:
                 C.check(C.lib().tsasr_joint_f32_bwd(C.ptr(dl), C.ptr(enc), C.ptr(dec), C.ptr(w32), C.ptr(denc), C.ptr(ddec), C.ptr(dW), C.ptr(db),
                                                     C.ptr(tlen), C.ptr(ulen), B, T, U1, J, V, dl.stride(-2), ctx.slope,
                                                     C.ptr(ws), ws.numel(), C.stream_ptr()), "tsasr_joint_f32_bwd")
@@ -88,7 +104,8 @@ def _as_padded_rows(x, V):
 
 
 def fused_joint_logits(enc_proj, dec_proj, head_weight, head_bias, slope=0.01, enc_abs_lens=None, tok_abs_lens=None):
-    """logits[b,t,u,:] = head(LeakyReLU(enc_proj[b,t] + dec_proj[b,u]))  as a [B,T,U1,V] view of 128-byte rows."""
+    """logits[b,t,u,:] = head(LeakyReLU(enc_proj[b,t] + dec_proj[b,u]))  as a [B,T,U1,V] view of rows padded to 32 floats (V <= 32: 128-byte
+    rows, csrc/rnnt.hip or the exact-fp32 csrc/joint_f32.hip; 32 < V <= 1024: csrc/joint_wide.hip, bf16-rounded operands in either dtype)."""
     return _JointLogitsFn.apply(enc_proj, dec_proj, head_weight, head_bias, slope, enc_abs_lens, tok_abs_lens)
 
 
