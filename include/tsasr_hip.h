@@ -643,6 +643,25 @@ int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, co
                          double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
                          double lm_weight);
 
+/* The beam search for subword vocabularies (csrc/search.hip beam_search_wide_kernel): the search, outputs, status words and stream
+ * resume of the entry points above for 2 <= V <= 1024 and an embedding of E <= 1024 columns (E <= 64: a side operand of the recurrent
+ * product; E % 4 == 0: a dense second product; any other E, the frozen one-hot table's V - 1: one gate row per thread over the non-zero
+ * columns), 2 <= beam <= min(V, 64). One entry point: tsasr_beam_search_lm's arguments with n_valid NULL = the offline search (the
+ * workspace is started afresh, max_frames = T), frames NULL = untimed, lm NULL = no LM fusion. The log-softmax and the top-k are taken
+ * over the workgroup in a fixed order: two calls give the same bits. The workspace has the narrow layout with a slot's LM part
+ * lm_logp[Vp] | lm_h | lm_c, Vp = round_up(V, 4): tsasr_beam_search_wide_workspace_bytes = B * (align16(64 + 24 beam) + align16(8 nodes)
+ * + 4 (cap + beam)(J + 2H + (lm_layers > 0 ? Vp + 2 lm_layers lm_hidden : 0)) + (times ? align16(4 nodes) : 0)), nodes = 1 + (T + 1) beam
+ * + cap; 0 for a non-positive size. LDS: 4 (6H + 2J + round_up(E, 4) + Vp + 96) + cap (16 + 4 (times ? 7 : 6)) bytes, with an LM
+ * 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden, dnn_neurons) + 2 Vp + 2) more, together <= 156 KB: a shape past it
+ * is TSASR_E_INVALID. The narrow entry points are untouched; the host sends V <= 63 with E <= 64 there. */
+size_t tsasr_beam_search_wide_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times);
+int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                           double lm_weight);
+
 /* ------------------------------------------------------------------------------------------
  * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:
  * 124-334, Kaldi's compute-wer order: the substitution / match only if strictly cheaper than both others, else the deletion if strictly

@@ -19,6 +19,14 @@ alternate, median of --reps after warm-up (the method of profiles/align_notes.md
 --lm: the LM-fused launch (tsasr_beam_search_lm, the reference-default RNNLM: 2 x 1024 LSTM, embedding 128, one 512 block; seeded initial
 weights) beside the unfused launch in the same loop, by the method of --times; then the host loop with the same LM (TSASR_BEAM_KERNEL=0)
 over --host-utts utterances, wall clock per utterance. LM steps per frame = hypothesis nodes expanded (one LM step each, as predictor steps).
+
+    python tools/beam_bench.py --vocab 256 [--lm] [--times] [--blank-bias 3.0] [--reps 5] [--host-utts 1]
+
+--vocab V: a subword model (beam_search_wide_kernel): predictor 512 / joint 640 / V symbols with the frozen one-hot table, weights seeded
+like tests/helpers/joint_wide_ref.greedy_net (head scale 1.5, blank bias +3 and --blank-bias more, so that the search ends), enc_proj
+[32, --frames, 640] seeded. The device search through the searcher's own call (launch and read-back of the n-best, median of --reps) beside
+the host loop (TSASR_BEAM_KERNEL=0, --host-utts utterances, per utterance), beams --beams; --lm fuses the reference-default RNNLM over V
+symbols into both, --times asks both for the emission frames.
 """
 import argparse
 import ctypes
@@ -231,6 +239,70 @@ def lm_bench(args):
     return results
 
 
+def wide_bench(args):
+    """--vocab V: device search per batch beside the host loop per utterance; prints one JSON line per dtype and beam."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import joint_wide_ref as JW
+    dec = importlib.import_module("ts-asr_amd.decoders")
+    ops = importlib.import_module("ts-asr_amd.ops")
+    nnet = importlib.import_module("ts-asr_amd.nnet")
+    rnnt = importlib.import_module("ts-asr_amd.rnnt")
+    V, H, J, B, T = args.vocab, 512, 640, 32, args.frames
+    net = {k: torch.from_numpy(v) for k, v in JW.greedy_net(f"beam_bench.v{V}", spec=(V, None, H, J, 1.5)).items()}
+    net["b_head"][0] += args.blank_bias
+    emb = nnet.Embedding(V, consider_as_one_hot=True, blank_id=0)
+    lstm = nnet.LSTM(H, input_size=emb.embedding_dim)
+    lstm.rnn.load_state_dict({"weight_ih_l0": net["w_ih"], "weight_hh_l0": net["w_hh"], "bias_ih_l0": net["b_ih"], "bias_hh_l0": net["b_hh"]})
+    proj, head = nnet.Linear(J, input_size=H), nnet.Linear(V, input_size=J)
+    proj.load_state_dict({"w.weight": net["w_proj"], "w.bias": net["b_proj"]})
+    head.load_state_dict({"w.weight": net["w_head"], "w.bias": net["b_head"]})
+    mods = [m.to("cuda:0").eval() for m in (emb, lstm, proj, head)]
+    lm = None
+    if args.lm:
+        torch.manual_seed(0)
+        lm = nnet.RNNLM(V, return_hidden=True).to("cuda:0").eval()
+    results = []
+    for dtype in args.dtypes.split(","):
+        nnet.set_compute_dtype(torch.float32 if dtype == "fp32" else torch.bfloat16)       # the host loop's products
+        enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (B, T, J), 1.0)).to("cuda:0", torch.float32 if dtype == "fp32" else torch.bfloat16)
+        for beam in (int(b) for b in args.beams.split(",")):
+            s = dec.TransducerBeamSearcher(mods[:3], rnnt.Transducer_joint(), [mods[3]], blank_id=0, beam_size=beam, nbest=5, lm_module=lm,
+                                           lm_weight=args.lm_weight if lm is not None else 0.0, state_beam=2.3, expand_beam=2.3)
+            kw = {"frames": True} if args.times else {}
+            with torch.no_grad():
+                assert s._device_beam_ok(enc) and s._beam_is_wide()
+                status = s._device_beam_call(enc, ops.beam_search, **kw)[2]      # warm-up (no host re-decode: timed alone)
+                ms = []
+                for _ in range(args.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    s._device_beam_call(enc, ops.beam_search, **kw)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms.append(e0.elapsed_time(e1))
+                host_ms, exp, steps, frames = float("nan"), 0, 0, 1
+                ok = [b for b in range(B) if int(status[b]) == 0][: args.host_utts]
+                if ok:
+                    os.environ["TSASR_BEAM_KERNEL"] = "0"
+                    try:
+                        t0 = time.perf_counter()
+                        s.forward_timed(enc[ok]) if args.times else s(enc[ok])
+                        torch.cuda.synchronize()
+                        host_ms = (time.perf_counter() - t0) * 1e3 / len(ok)
+                        if lm is None:
+                            exp, steps, frames = counts(s, enc[ok[:1]])
+                    finally:
+                        del os.environ["TSASR_BEAM_KERNEL"]
+            dev_ms = float(np.median(ms))
+            r = dict(vocab=V, lm=bool(args.lm), times=bool(args.times), dtype=dtype, beam=beam, B=B, T=T, device_ms_per_batch=round(dev_ms, 2),
+                     host_ms_per_utt=round(host_ms, 1), speedup_batch=round(host_ms * B / dev_ms, 1), device_stopped_utts=int((status != 0).sum()))
+            if lm is None:
+                r.update(expansions_per_frame=round(exp / frames, 2), predictor_steps_per_frame=round(steps / frames, 2))
+            print(json.dumps(r), flush=True)
+            results.append(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -242,7 +314,11 @@ def main():
     ap.add_argument("--ab-lib", default=None, help="--times: also time tsasr_beam_search of this other build of the library")
     ap.add_argument("--lm", action="store_true", help="time the LM-fused launch beside the unfused one, and the host loop with the same LM")
     ap.add_argument("--lm-weight", type=float, default=0.3)
+    ap.add_argument("--vocab", type=int, default=0, help="a subword model of this many symbols (the wide search), with --lm / --times")
+    ap.add_argument("--blank-bias", type=float, default=3.0, help="--vocab: added to the head's blank bias beside the seeded net's +3")
     args = ap.parse_args()
+    if args.vocab:
+        return wide_bench(args)
     if args.times:
         return times_bench(args)
     if args.lm:

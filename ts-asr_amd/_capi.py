@@ -159,6 +159,9 @@ _PROTOS = {
     "tsasr_beam_search_lm_workspace_bytes": (c_size_t, [c_int] * 9),
     "tsasr_beam_search_lm": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_double]),
+    "tsasr_beam_search_wide_workspace_bytes": (c_size_t, [c_int] * 10),
+    "tsasr_beam_search_wide": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_double]),
     "tsasr_edit_distance_workspace_bytes": (c_size_t, [c_int, c_ll]),
     "tsasr_edit_distance": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_ll] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),

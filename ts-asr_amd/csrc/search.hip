@@ -432,20 +432,42 @@ template <> struct BeamKernArgs<true> : BeamArgs { BeamLmArgs lm; };
 
 template <typename P> __device__ __forceinline__ P beam_pick4(const P (&a)[4], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
 
+// log_softmax over the workgroup, one entry per thread (v = -INFINITY for a thread past the vocabulary): the maximum and the sum of
+// exp(v - max) are reduced per wave, then over the 16 waves in wave order by every thread alike, so the bits do not depend on which wave
+// arrives first. expf / logf, not the fast intrinsics: the values enter fp64 score sums. red: 32 floats of LDS; two barriers.
+__device__ __forceinline__ float beam_wide_log_softmax(float v, float *red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float wm = wave_max(v);
+    if (lane == 0) red[wave] = wm;
+    __syncthreads();
+    float m = red[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) m = fmaxf(m, red[w]);
+    const float ws = wave_sum(v == -INFINITY ? 0.f : expf(v - m));
+    if (lane == 0) red[16 + wave] = ws;
+    __syncthreads();
+    float s = red[16];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) s += red[16 + w];
+    return (v - m) - logf(s);
+}
+
 // One LM step of a node, by the whole workgroup: token, the parent's LM state plm (a slot's LM part, or null: zeros) -> this node's LM part
 // slm = lm_logp[64] | lm_h[L Hl] | lm_c[L Hl] and s_lmlp[64]. LDS: lx[max(E, Hl, D)], lh[2 Hl] (h | c of the layer), lgt[max(4 Hl, D)],
-// llg[64], s_stat[2]. Ends behind a barrier.
-template <typename WT>
+// llg[64], s_stat[2]. Ends behind a barrier. WIDE (beam_search_wide_kernel): lm_logp, llg and s_lmlp hold round_up(V, 4) floats, the
+// head's log-softmax is taken over the workgroup (red: beam_wide_log_softmax's 32 floats).
+template <typename WT, bool WIDE = false>
 __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok, const float *plm, float *slm, float *lx, float *lh,
-                                             float *lgt, float *llg, float *s_lmlp, float *s_stat) {
+                                             float *lgt, float *llg, float *s_lmlp, float *s_stat, float *red = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int Hl = M.Hl, L = M.L, D = M.D;
+    const int lmo = WIDE ? (V + 3) & ~3 : 64;                // floats of lm_logp in a slot's LM part
     for (int e = tid; e < M.E; e += BEAM_THREADS) lx[e] = M.emb[(size_t)tok * M.E + e];
     for (int l = 0; l < L; ++l) {
         const WT *w_ih = (const WT *)beam_pick4(M.w_ih, l), *w_hh = (const WT *)beam_pick4(M.w_hh, l);
         const float *b_ih = beam_pick4(M.b_ih, l), *b_hh = beam_pick4(M.b_hh, l);
         for (int i = tid; i < 2 * Hl; i += BEAM_THREADS)
-            lh[i] = plm ? plm[64 + (i < Hl ? l * Hl + i : (L + l) * Hl + (i - Hl))] : 0.f;
+            lh[i] = plm ? plm[lmo + (i < Hl ? l * Hl + i : (L + l) * Hl + (i - Hl))] : 0.f;
         __syncthreads();
         gemv_rows<WT>(w_ih, 4 * Hl, l == 0 ? M.E : Hl, lx, b_ih, b_hh, nullptr, 0, nullptr, lgt);
         __syncthreads();
@@ -456,8 +478,8 @@ __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok
             const float cn = fg * lh[Hl + u] + ig * gg;
             const float hn = og * tanhf(cn);
             lx[u] = hn;                                      // the next layer's input
-            slm[64 + l * Hl + u] = hn;
-            slm[64 + (L + l) * Hl + u] = cn;
+            slm[lmo + l * Hl + u] = hn;
+            slm[lmo + (L + l) * Hl + u] = cn;
         }
         __syncthreads();
     }
@@ -487,7 +509,13 @@ __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok
     }
     gemv_rows<WT>((const WT *)M.w_out, V, K, lx, M.b_out, nullptr, nullptr, 0, nullptr, llg);
     __syncthreads();
-    if (wave == 0) {
+    if constexpr (WIDE) {
+        const float lp = beam_wide_log_softmax(tid < V ? llg[tid] : -INFINITY, red);
+        if (tid < V) {
+            s_lmlp[tid] = lp;
+            slm[tid] = lp;
+        }
+    } else if (wave == 0) {
         const float v = lane < V ? llg[lane] : -INFINITY;
         const float m = wave_max(v);
         const float s = wave_sum(lane < V ? expf(v - m) : 0.f);
@@ -715,6 +743,360 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamKer
                     s_ctl[0] = nA;
                     s_ctl[1] = nb;
                 }
+            }
+            __syncthreads();
+            if (s_ctl[11] != 0) break;
+        }
+        __syncthreads();
+        if (s_ctl[4] != 0) break;
+        // End of the frame: promote the new nodes on the beam's paths into the tree, in creation (index) order.
+        if (tid == 0) {
+            int cnt = 0;
+            for (int j = 0; j < s_ctl[1]; ++j)
+                for (int e = s_bidx[j]; e >= 0 && Anode[e] < 0 && !(Aflag[e] & 2); e = Apar[e]) { Aflag[e] |= 2; ++cnt; }
+            if (s_ctl[7] + cnt > L.nn) s_ctl[12] = 1;
+        }
+        __syncthreads();
+        if (s_ctl[12] != 0) break;
+        if (wave == 0) {
+            int base = s_ctl[7];
+            const int nA = s_ctl[0];
+            for (int i0 = 0; i0 < nA; i0 += 64) {
+                const int i = i0 + lane;
+                const bool mk = i < nA && (Aflag[i] & 2);
+                const unsigned long long bal = __ballot(mk);
+                if (mk) Anode[i] = base + __popcll(bal & ((1ull << lane) - 1));
+                base += __popcll(bal);
+            }
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            for (int i = lane; i < nA; i += 64)
+                if (Aflag[i] & 2) {
+                    tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
+                    if (TIMES) nfrm[Anode[i]] = Afrm[i];
+                }
+            if (lane == 0) s_ctl[7] = base;
+        }
+        __syncthreads();
+        BeamEnt ne{};
+        const int nb = s_ctl[1];
+        if (tid < nb) {
+            const int e = s_bidx[tid];
+            ne = BeamEnt{s_blp[tid], Anode[e], Alen[e], Aslot[e], Atok[e]};
+        }
+        __syncthreads();
+        if (tid < nb) {
+            Alp[tid] = ne.logp;
+            Akey[tid] = s_bkey[tid];
+            Apar[tid] = -1;
+            Atok[tid] = ne.tok;
+            Alen[tid] = ne.len;
+            Aslot[tid] = ne.slot;
+            Anode[tid] = ne.node;
+            Aflag[tid] = 1;
+        }
+        if (tid == 0) s_ctl[5] = nb;
+        __syncthreads();
+    }
+    __syncthreads();
+    const int st = s_ctl[4] != 0 ? s_ctl[4] : (s_ctl[12] != 0 ? 2 : 0), nbeam = s_ctl[5];
+    if (tid == 0) {
+        if (run) {                                           // the state this call leaves (a zero count leaves it untouched)
+            hdr[1] = st;
+            if (st == 0) {
+                hdr[0] = 1;
+                hdr[2] = nbeam;
+                hdr[3] = s_ctl[7];
+                hdr[4] = (fresh ? 0 : hdr[4]) + tend;
+            }
+        }
+        A.status[b] = st;
+        // n-best: sorted(beam, key=logp/len, reverse=True)[:nbest], stable -> repeated first-maximum selection
+        for (int r = 0; r < A.nbest; ++r) {
+            int best = -1;
+            if (st == 0)
+                for (int j = 0; j < nbeam; ++j)
+                    if (Aflag[j] & 1 && (best < 0 || Akey[j] > Akey[best])) best = j;
+            if (best >= 0) Aflag[best] &= ~1;
+            s_order[r] = best;
+            A.lens[(size_t)b * A.nbest + r] = best >= 0 ? Alen[best] - 1 : -1;
+            A.scores[(size_t)b * A.nbest + r] = best >= 0 ? Akey[best] : -INFINITY;
+        }
+    }
+    if (tid < nbeam && st == 0 && run) bent[tid] = BeamEnt{Alp[tid], Anode[tid], Alen[tid], Aslot[tid], Atok[tid]};
+    __syncthreads();
+    for (int r = wave; r < A.nbest; r += BEAM_THREADS / 64) {  // one wave's lane 0 walks a hypothesis up the tree
+        const int e = s_order[r];
+        if (lane == 0 && e >= 0) {
+            int node = Anode[e];
+            int *out = A.hyps + ((size_t)b * A.nbest + r) * A.Lmax;
+            int *fout = TIMES ? A.frames + ((size_t)b * A.nbest + r) * A.Lmax : nullptr;
+            for (int d = Alen[e] - 2; d >= 0 && node > 0; --d) {
+                const int2 nd = tree[node];
+                if (d < A.Lmax) {
+                    out[d] = nd.x;
+                    if (TIMES) fout[d] = nfrm[node];
+                }
+                node = nd.y;
+            }
+        }
+    }
+}
+
+// (key, index) of the better top-k candidate: the larger value, equal values: the lower index; index INT_MAX = no candidate
+__device__ __forceinline__ void beam_topk_pick(float &k, int &i, float k2, int i2) {
+    if (i2 != INT_MAX && (i == INT_MAX || k2 > k || (k2 == k && i2 < i))) { k = k2; i = i2; }
+}
+
+__host__ __device__ inline int beam_round4(int v) { return (v + 3) & ~3; }
+// WIDE: floats a slot holds after pn | h | c with LM fusion: lm_logp[round_up(V, 4)] | lm_h[L * Hl] | lm_c[L * Hl]
+__host__ __device__ inline int beam_wide_lm_slot_floats(int V, int layers, int hidden) { return beam_round4(V) + 2 * layers * hidden; }
+
+// The beam search for subword vocabularies (64 <= V <= 1024, or an embedding wider than 64 columns): a sibling of beam_search_kernel as
+// greedy_decode_wide_kernel is of the narrow greedy kernel. The search itself - A in LDS, fp64 scores and keys, memoised predictor (and
+// LM) steps in slots, promotion into the token tree, status words, stream resume, TIMES - is the narrow kernel's, statement for statement;
+// the workspace has its layout with the slot's LM part widened to lm_logp[round_up(V, 4)]. What differs:
+//   - log-softmax: one vocabulary entry per thread, maximum and sum reduced over the 16 waves in wave order (beam_wide_log_softmax);
+//   - top-k: beam rounds of a workgroup arg max over the entries not taken yet, ordered by (value descending, index ascending) - the
+//     order the narrow kernel's rank counting gives. A round: the wave's best by shuffles, the 16 wave candidates through LDS (two
+//     buffers in turn: one barrier per round), every thread reduces them alike, the winner's thread records itself. No atomics, no
+//     dependence on which wave arrives first;
+//   - embedding x = emb[token] of E <= 1024 columns: greedy_decode_wide_kernel's three routes (side operand for E <= 64, dense second
+//     product for E % 4 == 0, one thread per gate row over the non-zero x[e] otherwise: the frozen one-hot table);
+//   - LM: beam_lm_step<WT, true>, s_lmlp of round_up(V, 4) floats.
+// Dynamic LDS: h | c | pn | z | gates | x[Ep] | lg[Vp] | red[96] | A arrays (cap) | LM: lx | lh | lgt | llg[Vp] | s_lmlp[Vp] | s_stat[2];
+// red = wave maxima[16] | wave sums[16] | top-k wave values[2][16] | top-k wave indices[2][16].
+template <typename T, typename WT, bool TIMES, bool LM>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const BeamKernArgs<LM> A) {
+    extern __shared__ __attribute__((aligned(16))) float bsm[];
+    const int H = A.H, J = A.J, cap = A.cap;
+    const int Ep = beam_round4(A.E), Vp = beam_round4(A.V);
+    float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + Ep, *red = lg + Vp;
+    double *Alp = reinterpret_cast<double *>(red + 96), *Akey = Alp + cap;
+    int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
+        *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
+    int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
+    float *lx = nullptr, *lh = nullptr, *lgt = nullptr, *llg = nullptr, *s_lmlp = nullptr, *s_stat = nullptr;
+    int lmw = 0;
+    if constexpr (LM) {
+        lx = reinterpret_cast<float *>(Aflag + cap + (TIMES ? cap : 0));
+        lh = lx + max(max(A.lm.E, A.lm.Hl), A.lm.D);
+        lgt = lh + 2 * A.lm.Hl;
+        llg = lgt + max(4 * A.lm.Hl, A.lm.D);
+        s_lmlp = llg + Vp;
+        s_stat = s_lmlp + Vp;
+        lmw = beam_wide_lm_slot_floats(A.V, A.lm.L, A.lm.Hl);
+    }
+    __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
+    __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
+    __shared__ int s_ctl[16];                                // the narrow kernel's control words
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap, lmw);
+    unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES);
+    int *hdr = reinterpret_cast<int *>(wsu);
+    BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
+    int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
+    float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
+    int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
+    const int SWP = J + 2 * H;                               // floats per slot: pn | h | c
+    const int SW = SWP + lmw;                                // LM: | lm_logp[Vp] | lm_h | lm_c
+    const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
+    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
+    const bool fresh = A.n_valid == nullptr;
+    const int tend = fresh ? A.T : min(max(A.n_valid[b], 0), A.T);
+    const int fbase = (TIMES && !fresh) ? hdr[4] : 0;        // frames of this stream decoded before this call (written after the last frame)
+
+    if (tid == 0) {
+        const bool primed = !fresh && hdr[0] != 0;
+        s_ctl[4] = fresh ? 0 : hdr[1];
+        s_ctl[11] = s_ctl[12] = 0;
+        if (primed) {
+            const int nb = min(max(hdr[2], 1), A.beam);
+            s_ctl[5] = nb;
+            s_ctl[7] = hdr[3];
+        } else {
+            s_ctl[5] = 1;
+            s_ctl[7] = 1;
+        }
+    }
+    __syncthreads();
+    const bool primed = !fresh && hdr[0] != 0;
+    if (tid < s_ctl[5]) {                                    // the beam entering this call = the first frame's A
+        BeamEnt e = primed ? bent[tid] : BeamEnt{0.0, 0, 1, -1, A.blank};
+        Alp[tid] = e.logp;
+        Akey[tid] = e.logp / (double)e.len;
+        Apar[tid] = -1;
+        Atok[tid] = e.tok;
+        Alen[tid] = e.len;
+        Aslot[tid] = e.slot;
+        Anode[tid] = e.node;
+        Aflag[tid] = 1;
+    }
+    __syncthreads();
+    const bool run = s_ctl[4] == 0 && tend > 0;              // workgroup-uniform
+    if (run && !primed && tid == 0) tree[0] = make_int2(A.blank, -1);
+
+    for (int t = 0; run && t < tend; ++t) {
+        if (tid == 0) { s_ctl[0] = s_ctl[5]; s_ctl[1] = 0; s_ctl[6] = 0; s_ctl[3] = 0; }
+        __syncthreads();
+        while (true) {
+            if (wave == 0) {
+                const int nA = s_ctl[0], nb = s_ctl[1];
+                double bk = -INFINITY;
+                int bi = INT_MAX;
+                if (nb < A.beam) {
+                    for (int i = lane; i < nA; i += 64)
+                        if ((Aflag[i] & 1) && (Akey[i] > bk || bi == INT_MAX)) { bk = Akey[i]; bi = i; }
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) beam_argmax_step(bk, bi, m);
+                }
+                if (lane == 0) {
+                    int stop = 0;
+                    if (nb >= A.beam) stop = 1;
+                    else if (bi == INT_MAX) { s_ctl[4] = 3; stop = 2; }          // A ran empty (the reference's max() raises)
+                    else if (nb > 0) {
+                        int bm = 0;
+                        for (int j = 1; j < nb; ++j)
+                            if (s_bkey[j] > s_bkey[bm]) bm = j;
+                        if (s_blp[bm] >= A.state_beam + Alp[bi]) stop = 1;
+                    }
+                    if (!stop) {
+                        Aflag[bi] &= ~1;
+                        s_ctl[2] = bi;
+                        s_ctl[8] = Aslot[bi] < 0;
+                        if (Aslot[bi] < 0) {                         // first expansion of this node: a slot for its predictor step
+                            int p = s_ctl[6];
+                            const int ni = s_ctl[5];
+                            for (bool used = true; used && p < L.ns;) {
+                                used = false;
+                                for (int j = 0; j < ni; ++j) used |= Aslot[j] == p;
+                                if (used) ++p;
+                            }
+                            if (p >= L.ns) { s_ctl[4] = 1; stop = 2; }
+                            else {
+                                Aslot[bi] = p;
+                                s_ctl[6] = p + 1;
+                                s_ctl[9] = Apar[bi] >= 0 ? Aslot[Apar[bi]] : -1;
+                                s_ctl[10] = Atok[bi];
+                            }
+                        }
+                    }
+                    s_ctl[3] = stop;
+                }
+            }
+            __syncthreads();
+            if (s_ctl[3] != 0) break;
+            const int a = s_ctl[2];
+            float *sl = slots + (size_t)Aslot[a] * SW;
+            if (s_ctl[8]) {                                  // predictor step of node a: pn(token, parent's state), once per node
+                const int ps = s_ctl[9], tok = s_ctl[10];
+                const float *pst = ps >= 0 ? slots + (size_t)ps * SW : nullptr;
+                for (int i = tid; i < 2 * H; i += BEAM_THREADS) h[i] = pst ? pst[J + i] : 0.f;   // h | c contiguous in LDS and in a slot
+                for (int e = tid; e < A.E; e += BEAM_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
+                __syncthreads();
+                if (A.E <= 64) {
+                    gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
+                } else {
+                    gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, nullptr, 0, nullptr, gates);
+                    __syncthreads();
+                    if (A.E % 4 == 0) {
+                        gemv_rows_acc<WT>(w_ih, 4 * H, A.E, x, gates);
+                    } else {
+                        for (int r = tid; r < 4 * H; r += BEAM_THREADS) {
+                            float acc = 0.f;
+                            for (int e = 0; e < A.E; ++e) {
+                                const float xe = x[e];                 // the same LDS word for every thread: a uniform branch
+                                if (xe != 0.f) acc += (float)w_ih[(size_t)r * A.E + e] * xe;
+                            }
+                            gates[r] += acc;
+                        }
+                    }
+                }
+                __syncthreads();
+                for (int u = tid; u < H; u += BEAM_THREADS) {
+                    const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[H + u]), gg = tanhf(gates[2 * H + u]), og = sigmoid_f(gates[3 * H + u]);
+                    const float cn = fg * c[u] + ig * gg;
+                    c[u] = cn;
+                    h[u] = og * tanhf(cn);
+                }
+                __syncthreads();
+                gemv_rows<WT>(w_proj, J, H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
+                __syncthreads();
+                for (int i = tid; i < SWP; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];    // slot = pn | h | c (h, c adjacent in LDS)
+                if constexpr (LM)                            // the LM step of the same token from the parent slot's LM state
+                    beam_lm_step<WT, true>(A.lm, A.V, tok, pst ? pst + SWP : nullptr, sl + SWP, lx, lh, lgt, llg, s_lmlp, s_stat, red);
+            } else {
+                for (int k = tid; k < J; k += BEAM_THREADS) pn[k] = sl[k];
+                if constexpr (LM)
+                    for (int i = tid; i < A.V; i += BEAM_THREADS) s_lmlp[i] = sl[SWP + i];
+                __syncthreads();
+            }
+            for (int k = tid; k < J; k += BEAM_THREADS) {
+                const float v = ld1(enc + (size_t)t * J + k) + pn[k];
+                z[k] = v > 0.f ? v : v * A.slope;
+            }
+            __syncthreads();
+            gemv_rows<WT>(w_head, A.V, J, z, A.b_head, nullptr, nullptr, 0, nullptr, lg);
+            __syncthreads();
+            {                                                // log_softmax and top-k over the workgroup (V <= BEAM_THREADS: one entry per thread)
+                const float lp = beam_wide_log_softmax(tid < A.V ? lg[tid] : -INFINITY, red);
+                bool taken = tid >= A.V;
+                for (int r = 0; r < A.beam; ++r) {
+                    float k = lp;
+                    int i = taken ? INT_MAX : tid;
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) {
+                        const float k2 = __shfl_xor(k, m);
+                        const int i2 = __shfl_xor(i, m);
+                        beam_topk_pick(k, i, k2, i2);
+                    }
+                    float *rk = red + 32 + (r & 1) * 16;
+                    int *ri = reinterpret_cast<int *>(red + 64) + (r & 1) * 16;
+                    if (lane == 0) { rk[wave] = k; ri[wave] = i; }
+                    __syncthreads();
+                    float bk = rk[0];
+                    int bi = ri[0];
+#pragma unroll
+                    for (int w = 1; w < BEAM_THREADS / 64; ++w) beam_topk_pick(bk, bi, rk[w], ri[w]);
+                    if (tid == bi) {
+                        taken = true;
+                        s_tlp[r] = (double)lp;
+                        s_tpos[r] = tid;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {                                  // the appends, in top-k order
+                const double alp = Alp[a];
+                const int alen = Alen[a];
+                const double bnb = s_tpos[0] != A.blank ? s_tlp[0] : s_tlp[1];
+                int nA = s_ctl[0], nb = s_ctl[1];
+                for (int j = 0; j < A.beam; ++j) {
+                    const double sc = alp + s_tlp[j];
+                    const int sym = s_tpos[j];
+                    if (sym == A.blank) {
+                        s_blp[nb] = sc;
+                        s_bkey[nb] = sc / (double)alen;
+                        s_bidx[nb] = a;
+                        ++nb;
+                    } else if (s_tlp[j] >= bnb - A.expand_beam) {
+                        if (nA >= cap) { s_ctl[4] = 1; s_ctl[11] = 1; break; }
+                        double sx = sc;                      // LM: (alp + joint) + weight * lm, a product and a sum (no fused multiply-add)
+                        if constexpr (LM) sx = __dadd_rn(sc, __dmul_rn(A.lm.weight, (double)s_lmlp[sym]));
+                        Alp[nA] = sx;
+                        Akey[nA] = sx / (double)(alen + 1);
+                        Apar[nA] = a;
+                        Atok[nA] = sym;
+                        Alen[nA] = alen + 1;
+                        Aslot[nA] = -1;
+                        Anode[nA] = -1;
+                        Aflag[nA] = 1;
+                        if (TIMES) Afrm[nA] = fbase + t;
+                        ++nA;
+                    }
+                }
+                s_ctl[0] = nA;
+                s_ctl[1] = nb;
             }
             __syncthreads();
             if (s_ctl[11] != 0) break;
@@ -1087,6 +1469,79 @@ int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, co
     return beam_launch("tsasr_beam_search_lm", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
                        n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
                        Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
+}
+
+/* The wide search's workspace (beam_search_wide_kernel), a function of the shape alone: the narrow layout with the slot's LM part
+ * widened to round_up(V, 4) + 2 lm_layers lm_hidden floats; lm_layers == 0: no LM (lm_hidden is not read). 0 for a shape no call takes. */
+size_t tsasr_beam_search_wide_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times) {
+    if (V <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
+    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_wide_lm_slot_floats(V, lm_layers, lm_hidden) : 0);
+}
+
+/* The beam search for subword vocabularies: tsasr_beam_search_lm's arguments with V <= 1024, E <= 1024 (any E; a multiple of 4 runs the
+ * dense product), beam <= 64, and lm NULL = no LM fusion (lm_weight is then not read). n_valid NULL: the offline search; frames NULL:
+ * untimed. The LDS the shape needs is checked here: a shape past it is an argument error. */
+int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                           double lm_weight) {
+    const char *name = "tsasr_beam_search_wide";
+    const bool times = frames != nullptr;
+    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status, "%s: null pointer", name);
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 1024 && V > 1 && V <= BEAM_THREADS && blank >= 0 &&
+                    blank < V, "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
+    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
+    TSASR_CHECK_ARG(beam >= 2 && beam <= V && beam <= BEAM_MAXK && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
+                    "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
+    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
+    const int Vp = beam_round4(V);
+    BeamLmArgs m{};
+    size_t lm_lds = 0;
+    if (lm) {
+        const int Ll = lm->layers, Hl = lm->hidden, El = lm->emb_dim, nb = lm->dnn_blocks, D = lm->dnn_neurons;
+        TSASR_CHECK_ARG(Ll >= 1 && Ll <= 4 && Hl > 0 && Hl % 4 == 0 && Hl <= 1024 && El > 0 && El % 4 == 0 && El <= 1024 && nb >= 0 && nb <= 2 &&
+                        D > 0 && D % 4 == 0 && D <= 1024 && (nb > 0 || D == Hl),
+                        "%s: bad LM shape (layers=%d hidden=%d emb_dim=%d dnn_blocks=%d dnn_neurons=%d)", name, Ll, Hl, El, nb, D);
+        bool ptrs = lm->emb && lm->w_out;
+        for (int l = 0; l < Ll; ++l) ptrs = ptrs && lm->w_ih[l] && lm->w_hh[l];
+        for (int k = 0; k < nb; ++k) ptrs = ptrs && lm->w_dnn[k];
+        TSASR_CHECK_ARG(ptrs, "%s: null LM pointer", name);
+        m.emb = lm->emb;
+        for (int l = 0; l < 4; ++l) { m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l]; m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l]; }
+        for (int k = 0; k < 2; ++k) {
+            m.w_dnn[k] = lm->w_dnn[k]; m.b_dnn[k] = lm->b_dnn[k]; m.ln_g[k] = lm->ln_g[k]; m.ln_b[k] = lm->ln_b[k]; m.ln_eps[k] = lm->ln_eps[k];
+        }
+        m.w_out = lm->w_out; m.b_out = lm->b_out;
+        m.L = Ll; m.Hl = Hl; m.E = El; m.nb = nb; m.D = D; m.slope = lm->slope; m.weight = lm_weight;
+        lm_lds = (size_t)(std::max(std::max(El, Hl), D) + 2 * Hl + std::max(4 * Hl, D) + 2 * Vp + 2) * sizeof(float);
+    }
+    const int lmw = lm ? beam_wide_lm_slot_floats(V, lm->layers, lm->hidden) : 0;
+    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw);
+    TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
+    // dynamic LDS (the kernel's comment) + 4 KB for its static arrays (the beam's and the top-k's, 2.4 KB) within the CU's 160 KB
+    const size_t lds = (size_t)(6 * H + 2 * J + beam_round4(E) + Vp + 96) * sizeof(float) +
+                       (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
+    TSASR_CHECK_ARG(lds + 4096 <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d cap=%d need %zu B of LDS", name, H, J, E, V, cap, lds);
+    BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
+               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope, frames};
+    hipStream_t st = (hipStream_t)stream;
+#define BEAM(TT, WW)                                                                                                            \
+    if (lm) {                                                                                                                   \
+        auto kern = times ? beam_search_wide_kernel<TT, WW, true, true> : beam_search_wide_kernel<TT, WW, false, true>;         \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<true>{a, m});                                                           \
+    } else {                                                                                                                    \
+        auto kern = times ? beam_search_wide_kernel<TT, WW, true, false> : beam_search_wide_kernel<TT, WW, false, false>;       \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<false>{a});                                                             \
+    }
+    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) BEAM(float, float) else BEAM(float, bf16_t) }
+    else { if (wdtype == TSASR_F32) BEAM(bf16_t, float) else BEAM(bf16_t, bf16_t) }
+#undef BEAM
+    TSASR_CHECK_LAUNCH(name);
+    return 0;
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ For the recipes' networks one launch of csrc/search.hip decodes the batch (tsasr
 reference's list order, one predictor step per hypothesis node); utterances that need more than ``cap`` hypotheses in a frame, and
 every other network shape, run the host loop: host-side hypothesis bookkeeping exactly as specified there (SURVEY.md section 8f
 row f1), device-side predictor / joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
+Subword models (64 <= V <= 1024, or an embedding of up to 1024 columns; beam_size <= 64) run the same search in
+beam_search_wide_kernel (tsasr_beam_search_wide: offline, streams, timestamps and LM fusion through one entry point).
 
 LM fusion (lm_module, lm_weight > 0; transducer.py:95-110, 264-266, 311-351, 386-409): a hypothesis also carries the LM's state; each
 expansion of a runs the LM on a's last token (blank doubles as its BOS) from a's LM state; a non-blank extension by sym takes the new
@@ -95,14 +97,26 @@ class TransducerBeamSearcher(torch.nn.Module):
 
     def _device_beam_ok(self, tn_output):
         """The one-launch device beam search (csrc/search.hip) takes the networks the greedy decoder takes, with 2 <= beam_size <= V,
-        nbest <= 64 and cap >= beam_size; TSASR_BEAM_KERNEL=0 sends every call to the host loop."""
-        if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output, 64, 63):
+        nbest <= 64 and cap >= beam_size; subword models (_beam_is_wide) also need beam_size <= 64 and a shape whose search fits the
+        kernel's LDS. TSASR_BEAM_KERNEL=0 sends every call to the host loop."""
+        if os.environ.get("TSASR_BEAM_KERNEL", "1") == "0" or not self._device_net_ok(tn_output, GREEDY_WIDE_MAX, GREEDY_WIDE_MAX):
             return False
         rnn, V = self.decode_network_lst[1].rnn, self.classifier_network[0].w.out_features
         if self.lm_weight > 0 and not self._device_lm_ok(V):
             return False
-        return bool(2 <= self.beam_size <= V and 1 <= self.nbest <= 64 and self.cap >= self.beam_size and rnn.hidden_size <= 1024
-                    and tn_output.shape[-1] <= 1024 and tn_output.shape[0] > 0 and tn_output.shape[1] > 0)
+        ok = bool(2 <= self.beam_size <= V and 1 <= self.nbest <= 64 and self.cap >= self.beam_size and rnn.hidden_size <= 1024
+                  and tn_output.shape[-1] <= 1024 and tn_output.shape[0] > 0 and tn_output.shape[1] > 0)
+        if ok and self._beam_is_wide():
+            from . import ops
+            lm_rnn = self.lm.rnn.rnn if self.lm_weight > 0 else None
+            lm_dims = (self.lm.embedding.embedding_dim, lm_rnn.hidden_size, self.lm.out.w.in_features) if lm_rnn is not None else None
+            ok = self.beam_size <= 64 and ops.beam_wide_lds_bytes(rnn.hidden_size, tn_output.shape[-1], self.decode_network_lst[0].embedding_dim,
+                                                                  V, self.cap, lm_dims) <= ops.BEAM_WIDE_LDS_MAX
+        return ok
+
+    def _beam_is_wide(self):
+        """Subword models (V > 63 or an embedding wider than 64 columns) run beam_search_wide_kernel, character models the narrow one."""
+        return self._greedy_is_wide()
 
     def _device_lm_ok(self, V):
         """The LMs the device search fuses: an nnet.RNNLM in eval mode over the same V symbols with 1-4 LSTM layers, 0-2 dnn blocks with
@@ -139,8 +153,8 @@ class TransducerBeamSearcher(torch.nn.Module):
                     weight=float(self.lm_weight))
 
     def _device_net_ok(self, tn_output, emb_max, vocab_max):
-        """The network shape csrc/search.hip takes, with the caller's limits on the embedding width and the vocabulary: the beam search
-        (and LM fusion) stops at 64 columns / V = 63, above which it keeps the host loop; the greedy search goes to GREEDY_WIDE_MAX."""
+        """The network shape csrc/search.hip takes, with the caller's limits on the embedding width and the vocabulary: the greedy and
+        the beam search (with LM fusion) both go to GREEDY_WIDE_MAX, in the wide kernels past 64 columns / V = 63."""
         from . import nnet, rnnt
         if not tn_output.is_cuda or tn_output.dtype not in (torch.float32, torch.bfloat16):
             return False
@@ -361,6 +375,8 @@ class TransducerBeamSearcher(torch.nn.Module):
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
         if self.lm_weight > 0:
             kw["lm"] = self._device_lm_args(enc)
+        if self._beam_is_wide():
+            kw["wide"] = True
         return fn(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id, self.tjoint.nonlinearity.negative_slope, wdt, self.beam_size,
                   self.nbest, self.state_beam, self.expand_beam, self.cap, *extra, **kw)
 
@@ -416,8 +432,13 @@ class TransducerBeamSearcher(torch.nn.Module):
                 nbytes = size(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
                 if self.lm_weight > 0:
                     lm_rnn = self.lm.rnn.rnn
-                    nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size,
-                                                                self.cap, lm_rnn.num_layers, lm_rnn.hidden_size, timed)
+                    hid, V = self.decode_network_lst[1].rnn.hidden_size, self.classifier_network[0].w.out_features
+                    if self._beam_is_wide():
+                        nbytes = ops.beam_wide_workspace_bytes(B, mf, hid, enc.shape[-1], V, self.beam_size, self.cap, lm_rnn.num_layers,
+                                                               lm_rnn.hidden_size, timed)
+                    else:
+                        nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, hid, enc.shape[-1], self.beam_size, self.cap, lm_rnn.num_layers,
+                                                                    lm_rnn.hidden_size, timed)
                 state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf}
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")

@@ -25,7 +25,8 @@ STATUS = {
     "joint(32 < V <= 1024: subword vocabularies)": "HIP (joint_wide.hip: vocabulary tiles inside the kernels; bf16-rounded h / W / dlogits with bf16 OR fp32 activations - "
                                                    "an exact-fp32 wide joint is not built: compute_dtype fp32 with V > 32 runs these kernels with fp32 storage)",
     "greedy search (V <= 1024, embedding <= 1024 columns)": "HIP (search.hip: greedy_decode_kernel for V <= 63 / E <= 64, greedy_decode_wide_kernel above)",
-    "beam search / LM fusion with V > 63": "host loop over device-side predictor / joint steps (the device search stops at V = 63)",
+    "beam search / LM fusion with V > 63 or an embedding past 64 columns (V, E <= 1024, beam_size <= 64)":
+        "HIP (search.hip: beam_search_wide_kernel, workgroup-wide log-softmax and top-k; offline, streams, timestamps and LM fusion)",
     "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP", "fbank_frames": "HIP", "running_norm": "HIP (features_stream.hip)",
     "relpos_attention": "HIP (forward: everything-in-LDS kernel for T <= 256 and, per chunk of 256 keys, for long sequences in small batches, streaming kernel otherwise; backward = query-major, key-major, d(pk) and partial-sum kernels)",
     # What is NOT hand-written: shapes / modes none of the three recipes reaches. Each of these routes goes through lib_fallback(): counted in
@@ -2363,6 +2364,29 @@ def beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, lm_layers, lm_hidden, 
     return base + B * 4 * (cap + beam) * (64 + 2 * Ll * Hl)
 
 
+BEAM_WIDE_LDS_MAX = 156 * 1024      # dynamic LDS tsasr_beam_search_wide takes (160 KB less 4 KB for the kernel's static arrays)
+
+
+def beam_wide_workspace_bytes(B, T, H, J, V, beam, cap, lm_layers=0, lm_hidden=0, times=False):
+    """Bytes of the wide search's workspace (tsasr_beam_search_wide_workspace_bytes): the narrow layout, a slot's LM part holding
+    round_up(V, 4) + 2 * lm_layers * lm_hidden floats (lm_layers 0: no LM); ``times``: the timed layout."""
+    B, T, H, J, V, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, V, beam, cap, lm_layers, lm_hidden))
+    if min(B, T, H, J, V, beam, cap) <= 0 or Ll < 0 or (Ll > 0 and Hl <= 0):
+        return 0
+    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
+    return base + (B * 4 * (cap + beam) * ((V + 3) // 4 * 4 + 2 * Ll * Hl) if Ll > 0 else 0)
+
+
+def beam_wide_lds_bytes(H, J, E, V, cap, lm_dims=None, times=True):
+    """Dynamic LDS of beam_search_wide_kernel (include/tsasr_hip.h); lm_dims = (emb_dim, hidden, dnn_neurons) of a fused LM."""
+    r4 = lambda v: (int(v) + 3) // 4 * 4  # noqa: E731
+    n = 4 * (6 * H + 2 * J + r4(E) + r4(V) + 96) + int(cap) * (16 + 4 * (7 if times else 6))
+    if lm_dims is not None:
+        El, Hl, D = (int(v) for v in lm_dims)
+        n += 4 * (max(El, Hl, D) + 2 * Hl + max(4 * Hl, D) + 2 * r4(V) + 2)
+    return n
+
+
 _LM_KEYS = ("emb", "w_ih", "w_hh", "b_ih", "b_hh", "w_dnn", "b_dnn", "ln_g", "ln_b", "ln_eps", "w_out", "b_out", "slope", "weight")
 
 
@@ -2407,15 +2431,17 @@ def _beam_lm_desc(lm, V, wdtype):
 
 
 def _beam_lm_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope,
-                    wdtype, fr, desc, weight):
-    """tsasr_beam_search_lm's return code (0: launched): n_valid None = the offline search, fr None = untimed."""
-    return C.lib().tsasr_beam_search_lm(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size),
-                                        int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
-                                        wdtype, C.stream_ptr(), C.ptr(fr), C.ctypes.byref(desc), float(weight))
+                    wdtype, fr, desc, weight, name="tsasr_beam_search_lm"):
+    """tsasr_beam_search_lm's (or, by ``name``, tsasr_beam_search_wide's: desc None = no LM) return code (0: launched): n_valid None = the
+    offline search, fr None = untimed."""
+    return getattr(C.lib(), name)(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size),
+                                  int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
+                                  wdtype, C.stream_ptr(), C.ptr(fr), None if desc is None else C.ctypes.byref(desc), float(weight))
 
 
-def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype):
-    """Shapes and settings tsasr_beam_search takes (ValueError before any device call)."""
+def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide=False):
+    """Shapes and settings tsasr_beam_search takes, with ``wide`` those of tsasr_beam_search_wide (ValueError before any device call)."""
+    emax, vmax = (1024, 1024) if wide else (64, 63)
     if not isinstance(enc, torch.Tensor) or enc.dim() != 3 or enc.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("beam_search: enc must be a float32 / bfloat16 [B, T, J] tensor")
     B, T, J = enc.shape
@@ -2428,12 +2454,12 @@ def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, 
     want_w = torch.float32 if wdtype == C.F32 else torch.bfloat16
     if wdtype not in (C.F32, C.BF16) or any(m.dtype != want_w or not m.is_contiguous() for m in mats):
         raise ValueError(f"beam_search: weight matrices must be contiguous {want_w}")
-    if table.dtype != torch.float32 or table.dim() != 2 or E > 64:
-        raise ValueError("beam_search: the embedding table must be fp32 [n_emb, E <= 64]")
+    if table.dtype != torch.float32 or table.dim() != 2 or E > emax:
+        raise ValueError(f"beam_search: the embedding table must be fp32 [n_emb, E <= {emax}]")
     if tuple(w_ih.shape) != (4 * H, E) or tuple(w_hh.shape) != (4 * H, H) or tuple(w_proj.shape) != (J, H) or tuple(w_head.shape) != (V, J):
         raise ValueError(f"beam_search: weight shapes {[tuple(m.shape) for m in mats]} do not fit E={E} H={H} J={J}")
-    if H % 4 or J % 4 or H > 1024 or J > 1024 or V < 2 or V > 63:
-        raise ValueError(f"beam_search: H={H} and J={J} must be multiples of 4 <= 1024 and 2 <= V={V} <= 63")
+    if H % 4 or J % 4 or H > 1024 or J > 1024 or V < 2 or V > vmax:
+        raise ValueError(f"beam_search: H={H} and J={J} must be multiples of 4 <= 1024 and 2 <= V={V} <= {vmax}")
     for name, bvec, n in (("b_ih", b_ih, 4 * H), ("b_hh", b_hh, 4 * H), ("b_proj", b_proj, J), ("b_head", b_head, V)):
         if bvec is not None and (bvec.dtype != torch.float32 or bvec.numel() != n):
             raise ValueError(f"beam_search: {name} must be fp32 [{n}] or None")
@@ -2441,6 +2467,8 @@ def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, 
         raise ValueError(f"beam_search: blank {blank} outside the vocabulary of {V}")
     if not 2 <= int(beam_size) <= V:
         raise ValueError(f"beam_search: beam_size {beam_size} must be in [2, V={V}]")
+    if wide and int(beam_size) > 64:
+        raise ValueError(f"beam_search: beam_size {beam_size} above 64 (the wide search)")
     if not 1 <= int(nbest) <= 64:
         raise ValueError(f"beam_search: nbest {nbest} must be in [1, 64]")
     if int(cap) < int(beam_size):
@@ -2484,20 +2512,25 @@ def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
 
 
 def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                workspace=None, frames=False, lm=None):
+                workspace=None, frames=False, lm=None, wide=False):
     """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
     lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
     n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap).
     ``frames=True`` (tsasr_beam_search_timed): a fourth value, the n-best lists of the encoder frame that emitted each token; the
     workspace then has beam_stream_timed_workspace_bytes; the first three values are the bits of the untimed call.
     ``lm`` (tsasr_beam_search_lm): a dict of the fused LM's tensors (_beam_lm_desc) with its weight; the workspace then has
-    beam_stream_lm_workspace_bytes."""
+    beam_stream_lm_workspace_bytes.
+    ``wide=True`` (tsasr_beam_search_wide, subword models): V and the embedding's columns up to 1024, beam_size <= 64; every form above
+    through the one entry point; with an LM the workspace has beam_wide_workspace_bytes. Without it the narrow limits hold (V <= 63, 64
+    embedding columns)."""
     _no_grad_only("beam_search")
-    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
+    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, T, H, J, beam_size, cap)
+    desc, lm_weight = None, 0.0
     if lm is not None:
         desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
-        need = beam_stream_lm_workspace_bytes(B, T, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames))
+        need = (beam_wide_workspace_bytes(B, T, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
+                beam_stream_lm_workspace_bytes(B, T, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
     if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
         raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
     C.require_gpu(enc, table, *mats)
@@ -2510,9 +2543,10 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
         tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
                 C.io_dtype(encc), wdtype, C.stream_ptr())
         outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
-        if lm is not None:
+        if lm is not None or wide:
+            name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
             C.check(_beam_lm_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
-                                    state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight), "tsasr_beam_search_lm")
+                                    state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight, name), name)
             return
         if frames:
             tail += (C.ptr(fr),)
@@ -2529,18 +2563,21 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
 
 
 def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                       workspace, n_valid, max_frames, frames=False, lm=None):
+                       workspace, n_valid, max_frames, frames=False, lm=None, wide=False):
     """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
     (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
     beam_search returns, for the beam after the chunk. ``frames=True`` (tsasr_beam_search_stream_timed): also the n-best frame lists,
     absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed.
-    ``lm``: as in beam_search; the workspace has beam_stream_lm_workspace_bytes and every call of the stream carries the same LM."""
+    ``lm``: as in beam_search; the workspace has beam_stream_lm_workspace_bytes and every call of the stream carries the same LM.
+    ``wide``: as in beam_search, the same for every call of the stream."""
     _no_grad_only("beam_search_stream")
-    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype)
+    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, max_frames, H, J, beam_size, cap)
+    desc, lm_weight = None, 0.0
     if lm is not None:
         desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
-        need = beam_stream_lm_workspace_bytes(B, max_frames, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames))
+        need = (beam_wide_workspace_bytes(B, max_frames, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
+                beam_stream_lm_workspace_bytes(B, max_frames, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
     if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
         raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
     if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
@@ -2552,10 +2589,11 @@ def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slop
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
 
     def run(hyps, lens, scores, status, Lmax, readout, fr):
-        if lm is not None:
+        if lm is not None or wide:
+            name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
             C.check(_beam_lm_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,
                                     max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr,
-                                    desc, lm_weight), "tsasr_beam_search_lm")
+                                    desc, lm_weight, name), name)
             return
         fn, extra = (C.lib().tsasr_beam_search_stream_timed, (C.ptr(fr),)) if frames else (C.lib().tsasr_beam_search_stream, ())
         C.check(fn(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status), B, T,
