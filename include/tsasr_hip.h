@@ -554,7 +554,7 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
                                const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
                                float slope, int io_dtype, int wdtype, void *stream);
 
-/* The two greedy searches for subword vocabularies (csrc/search.hip greedy_decode_wide_kernel): arguments, outputs and the stream state
+/* The two greedy searches for subword vocabularies (csrc/search.hip greedy_decode_kernel's WIDE instantiations): arguments, outputs and the stream state
  * [B, 2H + J + 4] of the two calls above, with V <= 1024 and E <= 1024 (a one-hot table has E = V - 1; E % 4 == 0 runs a dense product, any
  * other E adds the columns of w_ih that meet a non-zero entry of the embedding row). The arg max takes the lowest index among ties. */
 int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
@@ -643,7 +643,7 @@ int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, co
                          double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
                          double lm_weight);
 
-/* The beam search for subword vocabularies (csrc/search.hip beam_search_wide_kernel): the search, outputs, status words and stream
+/* The beam search for subword vocabularies (csrc/search.hip beam_search_kernel's WIDE instantiations): the search, outputs, status words and stream
  * resume of the entry points above for 2 <= V <= 1024 and an embedding of E <= 1024 columns (E <= 64: a side operand of the recurrent
  * product; E % 4 == 0: a dense second product; any other E, the frozen one-hot table's V - 1: one gate row per thread over the non-zero
  * columns), 2 <= beam <= min(V, 64). One entry point: tsasr_beam_search_lm's arguments with n_valid NULL = the offline search (the

@@ -57,7 +57,7 @@ def backward(enc, dec, W, dlogits, slope=SLOPE, rounded=True):
     return dh.sum(2), dh.sum(1), dW, dlogits.to(torch.float64).sum((0, 1, 2))
 
 
-# ---- greedy transducer search in float64 (speechbrain/decoders/transducer.py:138-218; csrc/search.hip greedy_decode_wide_kernel) ----
+# ---- greedy transducer search in float64 (speechbrain/decoders/transducer.py:138-218; csrc/search.hip greedy_decode_kernel's WIDE instantiations) ----
 GREEDY_BLANK_BIAS = 3.0          # added to the head's blank bias, as oracle/gen_golden_beam.py does (random heads rarely choose blank)
 GREEDY_B, GREEDY_T = 3, 40
 GREEDY_CASES = {                 # name -> V, learned embedding width (None: the frozen one-hot table, E = V - 1), H, J, head scale

@@ -1,4 +1,4 @@
-"""Device beam search for subword vocabularies (csrc/search.hip beam_search_wide_kernel through decoders.TransducerBeamSearcher) against
+"""Device beam search for subword vocabularies (csrc/search.hip beam_search_kernel's WIDE instantiations through decoders.TransducerBeamSearcher) against
 the float64 search of tests/helpers/beam_wide_ref.py and the reference searcher's hypotheses in tests/golden/c1_beam_wide.npz.
 
 Every case meets the helper's beam_case_ok (tests/test_beam_wide_ref_cpu.py: every comparison of the float64 search, in fp32 and on the
@@ -311,3 +311,53 @@ def test_workspace_bytes_and_guard_region():
     assert bool((buf[need:] == 0xA5).all()), "the search wrote past its workspace"
     want = BW.run_case("v1024_big", 4)
     assert nb == [r["nbest"] for r in want] and fr == [r["frames"] for r in want]
+
+
+# ---- 10: a character model through the wide entry point ----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _narrow_searcher(with_lm):
+    """JW.NARROW_CASE (V = 29, one-hot E = 28, H = J = 64) at B = 3, T = 24, beam 4, nbest 3; blank bias +2 (the float64 search then ends
+    every frame below 32 hypotheses and emits 16 to 30 tokens per utterance, with and without the LM); ``with_lm``: BL's l1b0 over V = 29."""
+    name, spec = JW.NARROW_CASE
+    V, _, H, J, _ = spec
+    net = {k: torch.from_numpy(v.copy()) for k, v in JW.greedy_net(name, spec=spec).items()}
+    net["b_head"][0] += 2.0
+    emb = nnet.Embedding(V, consider_as_one_hot=True, blank_id=0)
+    lstm = nnet.LSTM(H, input_size=emb.embedding_dim)
+    lstm.rnn.load_state_dict({"weight_ih_l0": net["w_ih"], "weight_hh_l0": net["w_hh"], "bias_ih_l0": net["b_ih"], "bias_hh_l0": net["b_hh"]})
+    proj, head = nnet.Linear(J, input_size=H), nnet.Linear(V, input_size=J)
+    proj.load_state_dict({"w.weight": net["w_proj"], "w.bias": net["b_proj"]})
+    head.load_state_dict({"w.weight": net["w_head"], "w.bias": net["b_head"]})
+    mods = [m.to(DEV).eval() for m in (emb, lstm, proj, head)]
+    lm = None
+    if with_lm:
+        cfg = BW.BL.LM_CONFIGS["l1b0"]
+        lm = nnet.RNNLM(V, embedding_dim=cfg["emb"], dropout=0.0, rnn_layers=cfg["layers"], rnn_neurons=cfg["hidden"], return_hidden=True,
+                        dnn_blocks=cfg["blocks"], dnn_neurons=cfg["dnn"])
+        lm.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in BW.BL.lm_weights("l1b0", V=V).items()}, strict=True)
+        lm = lm.to(DEV).eval()
+    s = dec.TransducerBeamSearcher(mods[:3], rnnt.Transducer_joint(), [mods[3]], blank_id=0, beam_size=4, nbest=3, lm_module=lm,
+                                   lm_weight=cfg["weight"] if with_lm else 0.0, state_beam=2.3, expand_beam=2.3)
+    return s, net["enc"][:3, :24].contiguous()
+
+
+@pytest.mark.parametrize("with_lm", [False, True], ids=["nolm", "l1b0"])
+@pytest.mark.parametrize("timed", [False, True], ids=["untimed", "timed"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_character_model_same_bits_through_the_wide_entry_point(dtype, timed, with_lm):
+    """WIDE switches widths, the embedding's route, the log-softmax / top-k and who appends; at V = 29, E = 28 none of them changes a
+    bit: wave 0 holds the whole vocabulary (the other waves add a maximum of -inf and a sum of +0), both top-k orders are (value
+    descending, index ascending), and E <= 64 takes the side operand. So tsasr_beam_search_wide gives the narrow entry points' hypotheses,
+    lengths, status, fp64 scores and frames."""
+    s, enc = _narrow_searcher(with_lm)
+    enc = enc.to(DEV, dtype)
+    assert s._device_beam_ok(enc) and not s._beam_is_wide()
+    with torch.no_grad():
+        narrow = s._device_beam_call(enc, ops.beam_search, frames=timed)
+        wide = s._device_beam_call(enc, ops.beam_search, frames=timed, wide=True)
+    assert [int(x) for x in narrow[2]] == [0] * enc.shape[0] == [int(x) for x in wide[2]]
+    assert all(1 <= len(h) <= 3 and len(h[0]) > 0 for h in narrow[0])
+    assert wide[0] == narrow[0]                                              # token lists: hyps and lens
+    assert bits(wide[1]) == bits(narrow[1])
+    if timed:
+        assert wide[3] == narrow[3]

@@ -1,4 +1,4 @@
-"""Device greedy search for subword vocabularies (csrc/search.hip greedy_decode_wide_kernel through decoders.TransducerBeamSearcher) against
+"""Device greedy search for subword vocabularies (csrc/search.hip greedy_decode_kernel's WIDE instantiations through decoders.TransducerBeamSearcher) against
 the float64 search of tests/helpers/joint_wide_ref.py and the reference searcher's hypotheses in tests/golden/c1_wide_vocab.npz.
 
 Every case meets the helper's conditions (tests/test_joint_wide_ref_cpu.py: float64 top-2 logit margin >= 1e-4 at every decision, in fp32

@@ -22,7 +22,7 @@ over --host-utts utterances, wall clock per utterance. LM steps per frame = hypo
 
     python tools/beam_bench.py --vocab 256 [--lm] [--times] [--blank-bias 3.0] [--reps 5] [--host-utts 1]
 
---vocab V: a subword model (beam_search_wide_kernel): predictor 512 / joint 640 / V symbols with the frozen one-hot table, weights seeded
+--vocab V: a subword model (beam_search_kernel's WIDE instantiations): predictor 512 / joint 640 / V symbols with the frozen one-hot table, weights seeded
 like tests/helpers/joint_wide_ref.greedy_net (head scale 1.5, blank bias +3 and --blank-bias more, so that the search ends), enc_proj
 [32, --frames, 640] seeded. The device search through the searcher's own call (launch and read-back of the n-best, median of --reps) beside
 the host loop (TSASR_BEAM_KERNEL=0, --host-utts utterances, per utterance), beams --beams; --lm fuses the reference-default RNNLM over V

@@ -18,10 +18,12 @@
 
 namespace {
 
-constexpr int GREEDY_THREADS = 1024;   // 16 waves: the matrix-vector products are latency chains per wave
+constexpr int SEARCH_THREADS = 1024;   // 16 waves: the matrix-vector products are latency chains per wave
 
-struct GreedyArgs {
-    const void *enc;            // [B, T, J] io dtype
+__host__ __device__ inline int round4(int v) { return (v + 3) & ~3; }
+
+// The weights of the predictor and of the joint's head
+struct NetArgs {
     const float *emb;           // [V_emb, E] fp32 (one-hot table or learned)
     const void *w_ih, *w_hh;    // [4H, E], [4H, H]  (wdtype)
     const float *b_ih, *b_hh;   // [4H] fp32 (may be NULL)
@@ -29,6 +31,11 @@ struct GreedyArgs {
     const float *b_proj;        // [J] or NULL
     const void *w_head;         // [V, J] (wdtype)
     const float *b_head;        // [V] or NULL
+};
+
+struct GreedyArgs {
+    const void *enc;            // [B, T, J] io dtype
+    NetArgs net;
     int *preds;                 // [B, T]: symbol emitted at frame t, -1 = blank
     float *logp_sum;            // [B]: sum of the emitted symbols' log-probabilities
     int B, T, J, H, E, V, blank;
@@ -114,17 +121,68 @@ __device__ __forceinline__ void gemv_rows_acc(const WT *__restrict__ W, int rows
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
+// One predictor step by the whole workgroup, all in LDS: x = emb[tok] (E floats), gates = W_ih x + b_ih + W_hh h + b_hh, the LSTM cell on
+// h | c in place, pn = W_proj h + b_proj. h | c are the caller's; ends behind a barrier. The embedding row enters the gates as the
+// 64-column side operand of the recurrent product; WIDE (E <= 1024) keeps that route for E <= 64 and otherwise adds a second product: a
+// dense one (gemv_rows_acc) when the rows of W_ih are 16-byte pieces (E % 4 == 0, a learned embedding), else one thread per gate row adds
+// W_ih[r][e] * x[e] over the NON-ZERO x[e] only - for the frozen one-hot table (E = V - 1) that is one column of W_ih per token.
+template <typename WT, bool WIDE>
+__device__ __forceinline__ void predictor_step(const NetArgs &N, int E, int H, int J, int tok, float *x, float *h, float *c, float *gates,
+                                               float *pn) {
+    const int tid = threadIdx.x;
+    const WT *w_ih = (const WT *)N.w_ih, *w_hh = (const WT *)N.w_hh;
+    for (int e = tid; e < E; e += SEARCH_THREADS) x[e] = N.emb[(size_t)tok * E + e];
+    __syncthreads();
+    if (!WIDE || E <= 64) {
+        gemv_rows<WT>(w_hh, 4 * H, H, h, N.b_ih, N.b_hh, w_ih, E, x, gates);
+    } else {
+        gemv_rows<WT>(w_hh, 4 * H, H, h, N.b_ih, N.b_hh, nullptr, 0, nullptr, gates);
+        __syncthreads();
+        if (E % 4 == 0) {
+            gemv_rows_acc<WT>(w_ih, 4 * H, E, x, gates);
+        } else {
+            for (int r = tid; r < 4 * H; r += SEARCH_THREADS) {
+                float acc = 0.f;
+                for (int e = 0; e < E; ++e) {
+                    const float xe = x[e];                     // the same LDS word for every thread: a uniform branch
+                    if (xe != 0.f) acc += (float)w_ih[(size_t)r * E + e] * xe;
+                }
+                gates[r] += acc;
+            }
+        }
+    }
+    __syncthreads();
+    for (int u = tid; u < H; u += SEARCH_THREADS) {
+        const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[H + u]), gg = tanhf(gates[2 * H + u]), og = sigmoid_f(gates[3 * H + u]);
+        const float cn = fg * c[u] + ig * gg;
+        c[u] = cn;
+        h[u] = og * tanhf(cn);
+    }
+    __syncthreads();
+    gemv_rows<WT>((const WT *)N.w_proj, J, H, h, N.b_proj, nullptr, nullptr, 0, nullptr, pn);
+    __syncthreads();
+}
+
 // STREAM: the predictor state of utterance b is loaded from / stored to A.state[b] = [h (H) | c (H) | pn (J) | last symbol | logp sum |
 // primed flag | 0]; a state with primed flag 0 (all zeros) is primed with the blank symbol first, as the one-call decoder does. Only the
 // first n_valid[b] frames are decoded (preds of the rest: -1); with n_valid[b] == 0 the state is neither read for priming nor written.
-template <typename T, typename WT, bool STREAM>
-__global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const GreedyArgs A) {
+//
+// WIDE (tsasr_greedy_decode_wide / _stream_wide: V <= 1024, E <= 1024) switches three things, the rest is one body:
+//   - x and logits hold round_up(E, 4) and round_up(V, 4) floats instead of 64 each, and 64 floats of reduction space follow them:
+//     red[16] wave maxima | redi[16] wave candidates | reds[16] wave sums | the emit flag;
+//   - the arg max (lowest index among ties) and the sum of its log-softmax term: one vocabulary entry per thread, reduced per wave and
+//     then over the workgroup's 16 waves in wave order, instead of in wave 0 alone;
+//   - the emit flag reaches the workgroup through red[48] instead of logits[63].
+// and predictor_step<WT, true> takes the embedding row by its three routes.
+template <typename T, typename WT, bool STREAM, bool WIDE>
+__global__ __launch_bounds__(SEARCH_THREADS) void greedy_decode_kernel(const GreedyArgs A) {
     extern __shared__ __attribute__((aligned(16))) float gs[];
-    float *h = gs, *c = h + A.H, *pn = c + A.H, *z = pn + A.J, *gates = z + A.J, *x = gates + 4 * A.H, *logits = x + 64;
+    const int Ep = WIDE ? round4(A.E) : 64, Vp = WIDE ? round4(A.V) : 64;
+    float *h = gs, *c = h + A.H, *pn = c + A.H, *z = pn + A.J, *gates = z + A.J, *x = gates + 4 * A.H, *logits = x + Ep, *red = logits + Vp;
+    float *flag = WIDE ? red + 48 : logits + 63;
     __shared__ int s_tok;
     const int b = blockIdx.x, tid = threadIdx.x;
     const T *enc = (const T *)A.enc + (size_t)b * A.T * A.J;
-    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
     float lsum = 0.f;
     int tbeg = -1, tend = A.T;
     float *st = nullptr;
@@ -132,19 +190,19 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
         const int S = 2 * A.H + A.J + 4;
         st = A.state + (size_t)b * S;
         tend = min(max(A.n_valid[b], 0), A.T);
-        for (int t = tid; t < A.T; t += GREEDY_THREADS)
+        for (int t = tid; t < A.T; t += SEARCH_THREADS)
             if (t >= tend) A.preds[(size_t)b * A.T + t] = -1;
         if (tend == 0) {                            // workgroup-uniform: nothing to decode, the state stays as it is
             if (tid == 0) A.logp_sum[b] = st[2 * A.H + A.J + 1];
             return;
         }
         const bool primed = st[2 * A.H + A.J + 2] != 0.f;
-        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) gs[i] = st[i];   // h | c | pn are contiguous in LDS and in the state
+        for (int i = tid; i < 2 * A.H + A.J; i += SEARCH_THREADS) gs[i] = st[i];   // h | c | pn are contiguous in LDS and in the state
         if (tid == 0) s_tok = primed ? (int)st[2 * A.H + A.J] : A.blank;
         lsum = st[2 * A.H + A.J + 1];
         if (primed) tbeg = 0;
     } else {
-        for (int i = tid; i < A.H; i += GREEDY_THREADS) h[i] = c[i] = 0.f;
+        for (int i = tid; i < A.H; i += SEARCH_THREADS) h[i] = c[i] = 0.f;
         if (tid == 0) s_tok = A.blank;
     }
     __syncthreads();
@@ -153,179 +211,67 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_kernel(const Gre
         int tok = s_tok;                        // symbol to feed the predictor with (every thread reads the same LDS word)
         bool advance = (t < 0);
         if (t >= 0) {
-            for (int k = tid; k < A.J; k += GREEDY_THREADS) {
+            for (int k = tid; k < A.J; k += SEARCH_THREADS) {
                 const float v = ld1(enc + (size_t)t * A.J + k) + pn[k];
                 z[k] = v > 0.f ? v : v * A.slope;
             }
             __syncthreads();
-            gemv_rows<WT>(w_head, A.V, A.J, z, A.b_head, nullptr, nullptr, 0, nullptr, logits);
+            gemv_rows<WT>((const WT *)A.net.w_head, A.V, A.J, z, A.net.b_head, nullptr, nullptr, 0, nullptr, logits);
             __syncthreads();
-            if (tid < 64) {                     // arg max (lowest index among ties) and its log-probability, one wave
+            // arg max (lowest index among ties) and the sum of its log-softmax term; thread 0 gets both
+            int pos = 0;
+            float s = 0.f;
+            if constexpr (WIDE) {
+                const int lane = tid & 63, wave = tid >> 6;
+                int *redi = reinterpret_cast<int *>(red + 16);
+                float *reds = red + 32;
+                const float v = tid < A.V ? logits[tid] : -INFINITY;      // V <= SEARCH_THREADS: one vocabulary entry per thread
+                const float wm = wave_max(v);
+                if (lane == 0) red[wave] = wm;
+                __syncthreads();
+                float m = red[0];
+#pragma unroll
+                for (int w = 1; w < SEARCH_THREADS / 64; ++w) m = fmaxf(m, red[w]);
+                const unsigned long long eq = __ballot(v == m && tid < A.V);
+                const float ws = wave_sum(tid < A.V ? __expf(v - m) : 0.f);
+                if (lane == 0) {
+                    redi[wave] = eq ? wave * 64 + __ffsll((long long)eq) - 1 : 0x7fffffff;
+                    reds[wave] = ws;
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    pos = redi[0];
+                    s = reds[0];
+#pragma unroll
+                    for (int w = 1; w < SEARCH_THREADS / 64; ++w) {
+                        pos = min(pos, redi[w]);
+                        s += reds[w];
+                    }
+                }
+            } else if (tid < 64) {              // one wave holds the vocabulary
                 const float v = tid < A.V ? logits[tid] : -INFINITY;
                 float m = v;
                 m = wave_max(m);
                 const unsigned long long eq = __ballot(v == m && tid < A.V);
-                const int pos = __ffsll((long long)eq) - 1;
-                const float s = wave_sum(tid < A.V ? __expf(v - m) : 0.f);
-                if (tid == 0) {
-                    const bool emit = pos != A.blank;
-                    A.preds[(size_t)b * A.T + t] = emit ? pos : -1;
-                    if (emit) { lsum += -__logf(s); s_tok = pos; }     // log-softmax at the maximum = -log(sum exp(v - m))
-                    logits[63] = emit ? 1.f : 0.f;
-                }
+                pos = __ffsll((long long)eq) - 1;
+                s = wave_sum(tid < A.V ? __expf(v - m) : 0.f);
             }
-            __syncthreads();
-            advance = logits[63] != 0.f;
-            tok = s_tok;
-        }
-        if (advance) {                          // workgroup-uniform
-            for (int e = tid; e < A.E; e += GREEDY_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
-            __syncthreads();
-            gemv_rows<WT>(w_hh, 4 * A.H, A.H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
-            __syncthreads();
-            for (int u = tid; u < A.H; u += GREEDY_THREADS) {
-                const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[A.H + u]), gg = tanhf(gates[2 * A.H + u]), og = sigmoid_f(gates[3 * A.H + u]);
-                const float cn = fg * c[u] + ig * gg;
-                c[u] = cn;
-                h[u] = og * tanhf(cn);
-            }
-            __syncthreads();
-            gemv_rows<WT>(w_proj, A.J, A.H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
-            __syncthreads();
-        }
-    }
-    if (tid == 0) A.logp_sum[b] = lsum;
-    if (STREAM) {
-        __syncthreads();
-        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) st[i] = gs[i];
-        if (tid == 0) {
-            st[2 * A.H + A.J] = (float)s_tok;
-            st[2 * A.H + A.J + 1] = lsum;
-            st[2 * A.H + A.J + 2] = 1.f;
-        }
-    }
-}
-
-
-// The greedy search for subword vocabularies (64 <= V <= 1024, or an embedding wider than 64 columns): a sibling of greedy_decode_kernel, which
-// stays as it is for the character models (one-wave arg max, the embedding as a 64-column side operand). Differences: `logits` holds V floats
-// and the arg max (lowest index among ties) and the sum of its log-softmax term are reduced over the workgroup's 16 waves in wave order; the
-// embedding row x = emb[token] (E <= 1024) enters the gates as a second product: a dense one (gemv_rows_acc) when the rows of W_ih are
-// 16-byte pieces (E % 4 == 0, a learned embedding), otherwise one thread per gate row adds W_ih[r][e] * x[e] over the NON-ZERO x[e] only -
-// for the frozen one-hot table (E = V - 1) that is one column of W_ih per token. State layout and LDS prefix (h | c | pn) as the narrow kernel.
-template <typename T, typename WT, bool STREAM>
-__global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_wide_kernel(const GreedyArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float gs[];
-    const int Ep = (A.E + 3) & ~3, Vp = (A.V + 3) & ~3;
-    float *h = gs, *c = h + A.H, *pn = c + A.H, *z = pn + A.J, *gates = z + A.J, *x = gates + 4 * A.H, *logits = x + Ep, *red = logits + Vp;
-    int *redi = reinterpret_cast<int *>(red + 16);      // red[16] wave maxima | redi[16] wave candidates | reds[16] wave sums | flag
-    float *reds = red + 32, *flag = red + 48;
-    __shared__ int s_tok;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const T *enc = (const T *)A.enc + (size_t)b * A.T * A.J;
-    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
-    float lsum = 0.f;
-    int tbeg = -1, tend = A.T;
-    float *st = nullptr;
-    if (STREAM) {
-        const int S = 2 * A.H + A.J + 4;
-        st = A.state + (size_t)b * S;
-        tend = min(max(A.n_valid[b], 0), A.T);
-        for (int t = tid; t < A.T; t += GREEDY_THREADS)
-            if (t >= tend) A.preds[(size_t)b * A.T + t] = -1;
-        if (tend == 0) {                            // workgroup-uniform: nothing to decode, the state stays as it is
-            if (tid == 0) A.logp_sum[b] = st[2 * A.H + A.J + 1];
-            return;
-        }
-        const bool primed = st[2 * A.H + A.J + 2] != 0.f;
-        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) gs[i] = st[i];
-        if (tid == 0) s_tok = primed ? (int)st[2 * A.H + A.J] : A.blank;
-        lsum = st[2 * A.H + A.J + 1];
-        if (primed) tbeg = 0;
-    } else {
-        for (int i = tid; i < A.H; i += GREEDY_THREADS) h[i] = c[i] = 0.f;
-        if (tid == 0) s_tok = A.blank;
-    }
-    __syncthreads();
-    for (int t = tbeg; t < tend; ++t) {
-        int tok = s_tok;
-        bool advance = (t < 0);
-        if (t >= 0) {
-            for (int k = tid; k < A.J; k += GREEDY_THREADS) {
-                const float v = ld1(enc + (size_t)t * A.J + k) + pn[k];
-                z[k] = v > 0.f ? v : v * A.slope;
-            }
-            __syncthreads();
-            gemv_rows<WT>(w_head, A.V, A.J, z, A.b_head, nullptr, nullptr, 0, nullptr, logits);
-            __syncthreads();
-            const float v = tid < A.V ? logits[tid] : -INFINITY;      // V <= GREEDY_THREADS: one vocabulary entry per thread
-            const float wm = wave_max(v);
-            if (lane == 0) red[wave] = wm;
-            __syncthreads();
-            float m = red[0];
-#pragma unroll
-            for (int w = 1; w < GREEDY_THREADS / 64; ++w) m = fmaxf(m, red[w]);
-            const unsigned long long eq = __ballot(v == m && tid < A.V);
-            const float ws = wave_sum(tid < A.V ? __expf(v - m) : 0.f);
-            if (lane == 0) {
-                redi[wave] = eq ? wave * 64 + __ffsll((long long)eq) - 1 : 0x7fffffff;
-                reds[wave] = ws;
-            }
-            __syncthreads();
             if (tid == 0) {
-                int pos = redi[0];
-                float s = reds[0];
-#pragma unroll
-                for (int w = 1; w < GREEDY_THREADS / 64; ++w) {
-                    pos = min(pos, redi[w]);
-                    s += reds[w];
-                }
-                const bool emit = pos != A.blank && pos < A.V;
+                const bool emit = pos != A.blank && pos < A.V;             // (pos >= V: no entry equals the maximum, a NaN among the logits)
                 A.preds[(size_t)b * A.T + t] = emit ? pos : -1;
-                if (emit) { lsum += -__logf(s); s_tok = pos; }
+                if (emit) { lsum += -__logf(s); s_tok = pos; }     // log-softmax at the maximum = -log(sum exp(v - m))
                 *flag = emit ? 1.f : 0.f;
             }
             __syncthreads();
             advance = *flag != 0.f;
             tok = s_tok;
         }
-        if (advance) {                          // workgroup-uniform
-            for (int e = tid; e < A.E; e += GREEDY_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
-            __syncthreads();
-            if (A.E <= 64) {
-                gemv_rows<WT>(w_hh, 4 * A.H, A.H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
-            } else {
-                gemv_rows<WT>(w_hh, 4 * A.H, A.H, h, A.b_ih, A.b_hh, nullptr, 0, nullptr, gates);
-                __syncthreads();
-                if (A.E % 4 == 0) {
-                    gemv_rows_acc<WT>(w_ih, 4 * A.H, A.E, x, gates);
-                } else {
-                    for (int r = tid; r < 4 * A.H; r += GREEDY_THREADS) {
-                        float acc = 0.f;
-                        for (int e = 0; e < A.E; ++e) {
-                            const float xe = x[e];                     // the same LDS word for every thread: a uniform branch
-                            if (xe != 0.f) acc += (float)w_ih[(size_t)r * A.E + e] * xe;
-                        }
-                        gates[r] += acc;
-                    }
-                }
-            }
-            __syncthreads();
-            for (int u = tid; u < A.H; u += GREEDY_THREADS) {
-                const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[A.H + u]), gg = tanhf(gates[2 * A.H + u]), og = sigmoid_f(gates[3 * A.H + u]);
-                const float cn = fg * c[u] + ig * gg;
-                c[u] = cn;
-                h[u] = og * tanhf(cn);
-            }
-            __syncthreads();
-            gemv_rows<WT>(w_proj, A.J, A.H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
-            __syncthreads();
-        }
+        if (advance) predictor_step<WT, WIDE>(A.net, A.E, A.H, A.J, tok, x, h, c, gates, pn);   // workgroup-uniform
     }
     if (tid == 0) A.logp_sum[b] = lsum;
     if (STREAM) {
         __syncthreads();
-        for (int i = tid; i < 2 * A.H + A.J; i += GREEDY_THREADS) st[i] = gs[i];
+        for (int i = tid; i < 2 * A.H + A.J; i += SEARCH_THREADS) st[i] = gs[i];
         if (tid == 0) {
             st[2 * A.H + A.J] = (float)s_tok;
             st[2 * A.H + A.J + 1] = lsum;
@@ -358,8 +304,7 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_decode_wide_kernel(cons
 // scores are those of the untimed form, bit for bit. The frames of a stream are absolute only if its header was zeroed as a whole at the
 // start: the stream form takes "frames decoded so far" from hdr[4] whether or not the stream is primed, so hdr[0] == 0 over a stale
 // hdr[4] would shift every frame of the stream by that stale count (the untimed form only ever adds to the word).
-constexpr int BEAM_THREADS = 1024;
-constexpr int BEAM_MAXK = 64;            // beam_size <= V <= 63
+constexpr int BEAM_MAXK = 64;            // beam_size <= min(V, 64), nbest <= 64
 
 struct BeamEnt {
     double logp;
@@ -372,7 +317,7 @@ struct BeamLayout {
 };
 
 __host__ __device__ inline size_t beam_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-// lmw (LM fusion): floats a slot holds after pn | h | c, the LM step of the node: lm_logp[64] | lm_h[L * Hl] | lm_c[L * Hl]
+// lmw (LM fusion): floats a slot holds after pn | h | c, the LM step of the node: lm_logp[64, WIDE: round_up(V, 4)] | lm_h[L * Hl] | lm_c[L * Hl]
 __host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam, int cap, int lmw = 0) {
     BeamLayout L;
     L.nn = 1 + (T + 1) * beam + cap;                          // tree nodes: root + (typically <= beam promoted per frame) + slack
@@ -382,7 +327,9 @@ __host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam,
     L.per_utt = L.hdr + L.tree + (size_t)L.ns * (size_t)(J + 2 * H + lmw) * sizeof(float);
     return L;
 }
-__host__ __device__ inline int beam_lm_slot_floats(int layers, int hidden) { return 64 + 2 * layers * hidden; }
+__host__ __device__ inline int beam_lm_slot_floats(bool wide, int V, int layers, int hidden) {
+    return (wide ? round4(V) : 64) + 2 * layers * hidden;
+}
 // TIMES: the node-frame array (one int per tree node) follows the untimed layout of each utterance
 __host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times) {
     return L.per_utt + (times ? beam_align16(sizeof(int) * (size_t)L.nn) : 0);
@@ -390,13 +337,7 @@ __host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times) 
 
 struct BeamArgs {
     const void *enc;            // [B, T, J] io dtype (T = frames of this call)
-    const float *emb;
-    const void *w_ih, *w_hh;
-    const float *b_ih, *b_hh;
-    const void *w_proj;
-    const float *b_proj;
-    const void *w_head;
-    const float *b_head;
+    NetArgs net;
     unsigned char *ws;          // [B, layout.per_utt]
     const int *n_valid;         // [B] or NULL (= T, and the workspace is started afresh)
     int *hyps;                  // [B, nbest, Lmax]
@@ -454,7 +395,7 @@ __device__ __forceinline__ float beam_wide_log_softmax(float v, float *red) {
 
 // One LM step of a node, by the whole workgroup: token, the parent's LM state plm (a slot's LM part, or null: zeros) -> this node's LM part
 // slm = lm_logp[64] | lm_h[L Hl] | lm_c[L Hl] and s_lmlp[64]. LDS: lx[max(E, Hl, D)], lh[2 Hl] (h | c of the layer), lgt[max(4 Hl, D)],
-// llg[64], s_stat[2]. Ends behind a barrier. WIDE (beam_search_wide_kernel): lm_logp, llg and s_lmlp hold round_up(V, 4) floats, the
+// llg[64], s_stat[2]. Ends behind a barrier. WIDE (beam_search_kernel's): lm_logp, llg and s_lmlp hold round_up(V, 4) floats, the
 // head's log-softmax is taken over the workgroup (red: beam_wide_log_softmax's 32 floats).
 template <typename WT, bool WIDE = false>
 __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok, const float *plm, float *slm, float *lx, float *lh,
@@ -462,18 +403,18 @@ __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int Hl = M.Hl, L = M.L, D = M.D;
     const int lmo = WIDE ? (V + 3) & ~3 : 64;                // floats of lm_logp in a slot's LM part
-    for (int e = tid; e < M.E; e += BEAM_THREADS) lx[e] = M.emb[(size_t)tok * M.E + e];
+    for (int e = tid; e < M.E; e += SEARCH_THREADS) lx[e] = M.emb[(size_t)tok * M.E + e];
     for (int l = 0; l < L; ++l) {
         const WT *w_ih = (const WT *)beam_pick4(M.w_ih, l), *w_hh = (const WT *)beam_pick4(M.w_hh, l);
         const float *b_ih = beam_pick4(M.b_ih, l), *b_hh = beam_pick4(M.b_hh, l);
-        for (int i = tid; i < 2 * Hl; i += BEAM_THREADS)
+        for (int i = tid; i < 2 * Hl; i += SEARCH_THREADS)
             lh[i] = plm ? plm[lmo + (i < Hl ? l * Hl + i : (L + l) * Hl + (i - Hl))] : 0.f;
         __syncthreads();
         gemv_rows<WT>(w_ih, 4 * Hl, l == 0 ? M.E : Hl, lx, b_ih, b_hh, nullptr, 0, nullptr, lgt);
         __syncthreads();
         gemv_rows_acc<WT>(w_hh, 4 * Hl, Hl, lh, lgt);
         __syncthreads();
-        for (int u = tid; u < Hl; u += BEAM_THREADS) {
+        for (int u = tid; u < Hl; u += SEARCH_THREADS) {
             const float ig = sigmoid_f(lgt[u]), fg = sigmoid_f(lgt[Hl + u]), gg = tanhf(lgt[2 * Hl + u]), og = sigmoid_f(lgt[3 * Hl + u]);
             const float cn = fg * lh[Hl + u] + ig * gg;
             const float hn = og * tanhf(cn);
@@ -500,7 +441,7 @@ __device__ __forceinline__ void beam_lm_step(const BeamLmArgs &M, int V, int tok
             if (lane == 0) { s_stat[0] = mean; s_stat[1] = 1.f / sqrtf(var + eps); }
         }
         __syncthreads();
-        for (int i = tid; i < D; i += BEAM_THREADS) {
+        for (int i = tid; i < D; i += SEARCH_THREADS) {
             const float v = (lgt[i] - s_stat[0]) * s_stat[1] * (g ? g[i] : 1.f) + (be ? be[i] : 0.f);
             lx[i] = v > 0.f ? v : v * M.slope;
         }
@@ -533,17 +474,37 @@ __device__ __forceinline__ void beam_argmax_step(double &k, int &i, int mask) {
     if (k2 > k || (k2 == k && i2 < i)) { k = k2; i = i2; }
 }
 
-template <typename T, typename WT, bool TIMES, bool LM>
-__global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamKernArgs<LM> A) {
+// (key, index) of the better top-k candidate: the larger value, equal values: the lower index; index INT_MAX = no candidate
+__device__ __forceinline__ void beam_topk_pick(float &k, int &i, float k2, int i2) {
+    if (i2 != INT_MAX && (i == INT_MAX || k2 > k || (k2 == k && i2 < i))) { k = k2; i = i2; }
+}
+
+// WIDE (tsasr_beam_search_wide: subword vocabularies, V <= 1024 and E <= 1024) switches four things; the search itself - A in LDS, fp64
+// scores and keys, memoised predictor (and LM) steps in slots, promotion into the token tree, status words, stream resume, TIMES - is
+// one body:
+//   - widths: x, lg, s_lmlp, llg and the lm_logp part of a slot hold round_up(E, 4) / round_up(V, 4) floats instead of 64;
+//   - embedding x = emb[token]: predictor_step<WT, true>'s three routes instead of the one side operand;
+//   - log-softmax: one vocabulary entry per thread, maximum and sum reduced over the 16 waves in wave order (beam_wide_log_softmax)
+//     instead of in wave 0; top-k: beam rounds of a workgroup arg max over the entries not taken yet, ordered by (value descending,
+//     index ascending) - the order the one-wave rank counting gives. A round: the wave's best by shuffles, the 16 wave candidates
+//     through LDS (two buffers in turn: one barrier per round), every thread reduces them alike, the winner's thread records itself.
+//     No atomics, no dependence on which wave arrives first;
+//   - the appends: by thread 0 behind a barrier instead of by lane 0 of wave 0 behind a wave fence.
+// Dynamic LDS: h | c | pn | z | gates | x[Ep] | lg[Vp] | WIDE: red[96] | A arrays (cap) | LM: lx | lh | lgt | llg[Vp] | s_lmlp[Vp] |
+// s_stat[2], Ep = Vp = 64 unless WIDE; red = wave maxima[16] | wave sums[16] | top-k wave values[2][16] | top-k wave indices[2][16].
+template <typename T, typename WT, bool TIMES, bool LM, bool WIDE>
+__global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamKernArgs<LM> A) {
     extern __shared__ __attribute__((aligned(16))) float bsm[];
     const int H = A.H, J = A.J, cap = A.cap;
-    float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + 64;
-    double *Alp = reinterpret_cast<double *>(lg + 64), *Akey = Alp + cap;
+    const int Ep = WIDE ? round4(A.E) : 64, Vp = WIDE ? round4(A.V) : 64;
+    float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + Ep;
+    float *red = WIDE ? lg + Vp : nullptr;
+    double *Alp = reinterpret_cast<double *>(lg + Vp + (WIDE ? 96 : 0)), *Akey = Alp + cap;
     int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
         *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
     int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
-    // LM: the LM step's own LDS after the A arrays: lx[max(E, Hl, D)] | lh[2 Hl] | lgt[max(4 Hl, D)] | llg[64] (beam_lm_step) |
-    // s_lmlp[64] (lm_logp of the node being expanded) | s_stat[2] (LayerNorm mean, rstd)
+    // LM: the LM step's own LDS after the A arrays: lx[max(E, Hl, D)] | lh[2 Hl] | lgt[max(4 Hl, D)] | llg[Vp] (beam_lm_step) |
+    // s_lmlp[Vp] (lm_logp of the node being expanded) | s_stat[2] (LayerNorm mean, rstd)
     float *lx = nullptr, *lh = nullptr, *lgt = nullptr, *llg = nullptr, *s_lmlp = nullptr, *s_stat = nullptr;
     int lmw = 0;
     if constexpr (LM) {
@@ -551,13 +512,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamKer
         lh = lx + max(max(A.lm.E, A.lm.Hl), A.lm.D);
         lgt = lh + 2 * A.lm.Hl;
         llg = lgt + max(4 * A.lm.Hl, A.lm.D);
-        s_lmlp = llg + 64;
-        s_stat = s_lmlp + 64;
-        lmw = beam_lm_slot_floats(A.lm.L, A.lm.Hl);
+        s_lmlp = llg + Vp;
+        s_stat = s_lmlp + Vp;
+        lmw = beam_lm_slot_floats(WIDE, A.V, A.lm.L, A.lm.Hl);
     }
     __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
     __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
-    __shared__ float s_lp[64];
     // s_ctl: 0 nA, 1 nbeam (this frame), 2 chosen a, 3 stop (1 frame done, 2 status set), 4 status, 5 n_init, 6 next slot, 7 tree size,
     //        8 compute the predictor step, 9 parent slot, 10 token, 11 A full (appends), 12 tree full (promotion). Each flag is written in
     //        one phase and read right after that phase's barrier, so that no wave reads a word another wave is writing.
@@ -571,337 +531,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(const BeamKer
     float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
     int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
     const int SWP = J + 2 * H;                               // floats per slot: pn | h | c
-    const int SW = SWP + lmw;                                // LM: | lm_logp[64] | lm_h | lm_c
-    const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
-    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
-    const bool fresh = A.n_valid == nullptr;
-    const int tend = fresh ? A.T : min(max(A.n_valid[b], 0), A.T);
-    const int fbase = (TIMES && !fresh) ? hdr[4] : 0;        // frames of this stream decoded before this call (written after the last frame)
-
-    if (tid == 0) {
-        const bool primed = !fresh && hdr[0] != 0;
-        s_ctl[4] = fresh ? 0 : hdr[1];
-        s_ctl[11] = s_ctl[12] = 0;
-        if (primed) {
-            const int nb = min(max(hdr[2], 1), A.beam);
-            s_ctl[5] = nb;
-            s_ctl[7] = hdr[3];
-        } else {
-            s_ctl[5] = 1;
-            s_ctl[7] = 1;
-        }
-    }
-    __syncthreads();
-    const bool primed = !fresh && hdr[0] != 0;
-    if (tid < s_ctl[5]) {                                    // the beam entering this call = the first frame's A
-        BeamEnt e = primed ? bent[tid] : BeamEnt{0.0, 0, 1, -1, A.blank};
-        Alp[tid] = e.logp;
-        Akey[tid] = e.logp / (double)e.len;
-        Apar[tid] = -1;
-        Atok[tid] = e.tok;
-        Alen[tid] = e.len;
-        Aslot[tid] = e.slot;
-        Anode[tid] = e.node;
-        Aflag[tid] = 1;
-    }
-    __syncthreads();
-    const bool run = s_ctl[4] == 0 && tend > 0;              // workgroup-uniform
-    if (run && !primed && tid == 0) tree[0] = make_int2(A.blank, -1);
-
-    for (int t = 0; run && t < tend; ++t) {
-        if (tid == 0) { s_ctl[0] = s_ctl[5]; s_ctl[1] = 0; s_ctl[6] = 0; s_ctl[3] = 0; }
-        __syncthreads();
-        while (true) {
-            if (wave == 0) {
-                const int nA = s_ctl[0], nb = s_ctl[1];
-                double bk = -INFINITY;
-                int bi = INT_MAX;
-                if (nb < A.beam) {
-                    for (int i = lane; i < nA; i += 64)
-                        if ((Aflag[i] & 1) && (Akey[i] > bk || bi == INT_MAX)) { bk = Akey[i]; bi = i; }
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) beam_argmax_step(bk, bi, m);
-                }
-                if (lane == 0) {
-                    int stop = 0;
-                    if (nb >= A.beam) stop = 1;
-                    else if (bi == INT_MAX) { s_ctl[4] = 3; stop = 2; }          // A ran empty (the reference's max() raises)
-                    else if (nb > 0) {
-                        int bm = 0;
-                        for (int j = 1; j < nb; ++j)
-                            if (s_bkey[j] > s_bkey[bm]) bm = j;
-                        if (s_blp[bm] >= A.state_beam + Alp[bi]) stop = 1;
-                    }
-                    if (!stop) {
-                        Aflag[bi] &= ~1;
-                        s_ctl[2] = bi;
-                        s_ctl[8] = Aslot[bi] < 0;
-                        if (Aslot[bi] < 0) {                         // first expansion of this node: a slot for its predictor step
-                            int p = s_ctl[6];
-                            const int ni = s_ctl[5];
-                            for (bool used = true; used && p < L.ns;) {
-                                used = false;
-                                for (int j = 0; j < ni; ++j) used |= Aslot[j] == p;
-                                if (used) ++p;
-                            }
-                            if (p >= L.ns) { s_ctl[4] = 1; stop = 2; }
-                            else {
-                                Aslot[bi] = p;
-                                s_ctl[6] = p + 1;
-                                s_ctl[9] = Apar[bi] >= 0 ? Aslot[Apar[bi]] : -1;
-                                s_ctl[10] = Atok[bi];
-                            }
-                        }
-                    }
-                    s_ctl[3] = stop;
-                }
-            }
-            __syncthreads();
-            if (s_ctl[3] != 0) break;
-            const int a = s_ctl[2];
-            float *sl = slots + (size_t)Aslot[a] * SW;
-            if (s_ctl[8]) {                                  // predictor step of node a: pn(token, parent's state), once per node
-                const int ps = s_ctl[9], tok = s_ctl[10];
-                const float *pst = ps >= 0 ? slots + (size_t)ps * SW : nullptr;
-                for (int i = tid; i < 2 * H; i += BEAM_THREADS) h[i] = pst ? pst[J + i] : 0.f;   // h | c contiguous in LDS and in a slot
-                for (int e = tid; e < A.E; e += BEAM_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
-                __syncthreads();
-                gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
-                __syncthreads();
-                for (int u = tid; u < H; u += BEAM_THREADS) {
-                    const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[H + u]), gg = tanhf(gates[2 * H + u]), og = sigmoid_f(gates[3 * H + u]);
-                    const float cn = fg * c[u] + ig * gg;
-                    c[u] = cn;
-                    h[u] = og * tanhf(cn);
-                }
-                __syncthreads();
-                gemv_rows<WT>(w_proj, J, H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
-                __syncthreads();
-                for (int i = tid; i < SWP; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];    // slot = pn | h | c (h, c adjacent in LDS)
-                if constexpr (LM)                            // the LM step of the same token from the parent slot's LM state
-                    beam_lm_step<WT>(A.lm, A.V, tok, pst ? pst + SWP : nullptr, sl + SWP, lx, lh, lgt, llg, s_lmlp, s_stat);
-            } else {
-                for (int k = tid; k < J; k += BEAM_THREADS) pn[k] = sl[k];
-                if constexpr (LM)
-                    if (tid < 64) s_lmlp[tid] = sl[SWP + tid];
-                __syncthreads();
-            }
-            for (int k = tid; k < J; k += BEAM_THREADS) {
-                const float v = ld1(enc + (size_t)t * J + k) + pn[k];
-                z[k] = v > 0.f ? v : v * A.slope;
-            }
-            __syncthreads();
-            gemv_rows<WT>(w_head, A.V, J, z, A.b_head, nullptr, nullptr, 0, nullptr, lg);
-            __syncthreads();
-            if (wave == 0) {                                 // log_softmax, top-k (equal values: lower index first), the appends
-                const float v = lane < A.V ? lg[lane] : -INFINITY;
-                const float m = wave_max(v);
-                const float s = wave_sum(lane < A.V ? expf(v - m) : 0.f);
-                const float lp = (v - m) - logf(s);
-                s_lp[lane] = lp;
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                if (lane < A.V) {
-                    int rank = 0;
-                    for (int u = 0; u < A.V; ++u) {
-                        const float o = s_lp[u];
-                        rank += (o > lp) || (o == lp && u < lane);
-                    }
-                    if (rank < A.beam) { s_tlp[rank] = (double)lp; s_tpos[rank] = lane; }
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                if (lane == 0) {
-                    const double alp = Alp[a];
-                    const int alen = Alen[a];
-                    const double bnb = s_tpos[0] != A.blank ? s_tlp[0] : s_tlp[1];
-                    int nA = s_ctl[0], nb = s_ctl[1];
-                    for (int j = 0; j < A.beam; ++j) {
-                        const double sc = alp + s_tlp[j];
-                        const int sym = s_tpos[j];
-                        if (sym == A.blank) {
-                            s_blp[nb] = sc;
-                            s_bkey[nb] = sc / (double)alen;
-                            s_bidx[nb] = a;
-                            ++nb;
-                        } else if (s_tlp[j] >= bnb - A.expand_beam) {
-                            if (nA >= cap) { s_ctl[4] = 1; s_ctl[11] = 1; break; }
-                            double sx = sc;                  // LM: (alp + joint) + weight * lm, a product and a sum (no fused multiply-add)
-                            if constexpr (LM) sx = __dadd_rn(sc, __dmul_rn(A.lm.weight, (double)s_lmlp[sym]));
-                            Alp[nA] = sx;
-                            Akey[nA] = sx / (double)(alen + 1);
-                            Apar[nA] = a;
-                            Atok[nA] = sym;
-                            Alen[nA] = alen + 1;
-                            Aslot[nA] = -1;
-                            Anode[nA] = -1;
-                            Aflag[nA] = 1;
-                            if (TIMES) Afrm[nA] = fbase + t;
-                            ++nA;
-                        }
-                    }
-                    s_ctl[0] = nA;
-                    s_ctl[1] = nb;
-                }
-            }
-            __syncthreads();
-            if (s_ctl[11] != 0) break;
-        }
-        __syncthreads();
-        if (s_ctl[4] != 0) break;
-        // End of the frame: promote the new nodes on the beam's paths into the tree, in creation (index) order.
-        if (tid == 0) {
-            int cnt = 0;
-            for (int j = 0; j < s_ctl[1]; ++j)
-                for (int e = s_bidx[j]; e >= 0 && Anode[e] < 0 && !(Aflag[e] & 2); e = Apar[e]) { Aflag[e] |= 2; ++cnt; }
-            if (s_ctl[7] + cnt > L.nn) s_ctl[12] = 1;
-        }
-        __syncthreads();
-        if (s_ctl[12] != 0) break;
-        if (wave == 0) {
-            int base = s_ctl[7];
-            const int nA = s_ctl[0];
-            for (int i0 = 0; i0 < nA; i0 += 64) {
-                const int i = i0 + lane;
-                const bool mk = i < nA && (Aflag[i] & 2);
-                const unsigned long long bal = __ballot(mk);
-                if (mk) Anode[i] = base + __popcll(bal & ((1ull << lane) - 1));
-                base += __popcll(bal);
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            for (int i = lane; i < nA; i += 64)
-                if (Aflag[i] & 2) {
-                    tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
-                    if (TIMES) nfrm[Anode[i]] = Afrm[i];
-                }
-            if (lane == 0) s_ctl[7] = base;
-        }
-        __syncthreads();
-        BeamEnt ne{};
-        const int nb = s_ctl[1];
-        if (tid < nb) {
-            const int e = s_bidx[tid];
-            ne = BeamEnt{s_blp[tid], Anode[e], Alen[e], Aslot[e], Atok[e]};
-        }
-        __syncthreads();
-        if (tid < nb) {
-            Alp[tid] = ne.logp;
-            Akey[tid] = s_bkey[tid];
-            Apar[tid] = -1;
-            Atok[tid] = ne.tok;
-            Alen[tid] = ne.len;
-            Aslot[tid] = ne.slot;
-            Anode[tid] = ne.node;
-            Aflag[tid] = 1;
-        }
-        if (tid == 0) s_ctl[5] = nb;
-        __syncthreads();
-    }
-    __syncthreads();
-    const int st = s_ctl[4] != 0 ? s_ctl[4] : (s_ctl[12] != 0 ? 2 : 0), nbeam = s_ctl[5];
-    if (tid == 0) {
-        if (run) {                                           // the state this call leaves (a zero count leaves it untouched)
-            hdr[1] = st;
-            if (st == 0) {
-                hdr[0] = 1;
-                hdr[2] = nbeam;
-                hdr[3] = s_ctl[7];
-                hdr[4] = (fresh ? 0 : hdr[4]) + tend;
-            }
-        }
-        A.status[b] = st;
-        // n-best: sorted(beam, key=logp/len, reverse=True)[:nbest], stable -> repeated first-maximum selection
-        for (int r = 0; r < A.nbest; ++r) {
-            int best = -1;
-            if (st == 0)
-                for (int j = 0; j < nbeam; ++j)
-                    if (Aflag[j] & 1 && (best < 0 || Akey[j] > Akey[best])) best = j;
-            if (best >= 0) Aflag[best] &= ~1;
-            s_order[r] = best;
-            A.lens[(size_t)b * A.nbest + r] = best >= 0 ? Alen[best] - 1 : -1;
-            A.scores[(size_t)b * A.nbest + r] = best >= 0 ? Akey[best] : -INFINITY;
-        }
-    }
-    if (tid < nbeam && st == 0 && run) bent[tid] = BeamEnt{Alp[tid], Anode[tid], Alen[tid], Aslot[tid], Atok[tid]};
-    __syncthreads();
-    for (int r = wave; r < A.nbest; r += BEAM_THREADS / 64) {  // one wave's lane 0 walks a hypothesis up the tree
-        const int e = s_order[r];
-        if (lane == 0 && e >= 0) {
-            int node = Anode[e];
-            int *out = A.hyps + ((size_t)b * A.nbest + r) * A.Lmax;
-            int *fout = TIMES ? A.frames + ((size_t)b * A.nbest + r) * A.Lmax : nullptr;
-            for (int d = Alen[e] - 2; d >= 0 && node > 0; --d) {
-                const int2 nd = tree[node];
-                if (d < A.Lmax) {
-                    out[d] = nd.x;
-                    if (TIMES) fout[d] = nfrm[node];
-                }
-                node = nd.y;
-            }
-        }
-    }
-}
-
-// (key, index) of the better top-k candidate: the larger value, equal values: the lower index; index INT_MAX = no candidate
-__device__ __forceinline__ void beam_topk_pick(float &k, int &i, float k2, int i2) {
-    if (i2 != INT_MAX && (i == INT_MAX || k2 > k || (k2 == k && i2 < i))) { k = k2; i = i2; }
-}
-
-__host__ __device__ inline int beam_round4(int v) { return (v + 3) & ~3; }
-// WIDE: floats a slot holds after pn | h | c with LM fusion: lm_logp[round_up(V, 4)] | lm_h[L * Hl] | lm_c[L * Hl]
-__host__ __device__ inline int beam_wide_lm_slot_floats(int V, int layers, int hidden) { return beam_round4(V) + 2 * layers * hidden; }
-
-// The beam search for subword vocabularies (64 <= V <= 1024, or an embedding wider than 64 columns): a sibling of beam_search_kernel as
-// greedy_decode_wide_kernel is of the narrow greedy kernel. The search itself - A in LDS, fp64 scores and keys, memoised predictor (and
-// LM) steps in slots, promotion into the token tree, status words, stream resume, TIMES - is the narrow kernel's, statement for statement;
-// the workspace has its layout with the slot's LM part widened to lm_logp[round_up(V, 4)]. What differs:
-//   - log-softmax: one vocabulary entry per thread, maximum and sum reduced over the 16 waves in wave order (beam_wide_log_softmax);
-//   - top-k: beam rounds of a workgroup arg max over the entries not taken yet, ordered by (value descending, index ascending) - the
-//     order the narrow kernel's rank counting gives. A round: the wave's best by shuffles, the 16 wave candidates through LDS (two
-//     buffers in turn: one barrier per round), every thread reduces them alike, the winner's thread records itself. No atomics, no
-//     dependence on which wave arrives first;
-//   - embedding x = emb[token] of E <= 1024 columns: greedy_decode_wide_kernel's three routes (side operand for E <= 64, dense second
-//     product for E % 4 == 0, one thread per gate row over the non-zero x[e] otherwise: the frozen one-hot table);
-//   - LM: beam_lm_step<WT, true>, s_lmlp of round_up(V, 4) floats.
-// Dynamic LDS: h | c | pn | z | gates | x[Ep] | lg[Vp] | red[96] | A arrays (cap) | LM: lx | lh | lgt | llg[Vp] | s_lmlp[Vp] | s_stat[2];
-// red = wave maxima[16] | wave sums[16] | top-k wave values[2][16] | top-k wave indices[2][16].
-template <typename T, typename WT, bool TIMES, bool LM>
-__global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const BeamKernArgs<LM> A) {
-    extern __shared__ __attribute__((aligned(16))) float bsm[];
-    const int H = A.H, J = A.J, cap = A.cap;
-    const int Ep = beam_round4(A.E), Vp = beam_round4(A.V);
-    float *h = bsm, *c = h + H, *pn = c + H, *z = pn + J, *gates = z + J, *x = gates + 4 * H, *lg = x + Ep, *red = lg + Vp;
-    double *Alp = reinterpret_cast<double *>(red + 96), *Akey = Alp + cap;
-    int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
-        *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
-    int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
-    float *lx = nullptr, *lh = nullptr, *lgt = nullptr, *llg = nullptr, *s_lmlp = nullptr, *s_stat = nullptr;
-    int lmw = 0;
-    if constexpr (LM) {
-        lx = reinterpret_cast<float *>(Aflag + cap + (TIMES ? cap : 0));
-        lh = lx + max(max(A.lm.E, A.lm.Hl), A.lm.D);
-        lgt = lh + 2 * A.lm.Hl;
-        llg = lgt + max(4 * A.lm.Hl, A.lm.D);
-        s_lmlp = llg + Vp;
-        s_stat = s_lmlp + Vp;
-        lmw = beam_wide_lm_slot_floats(A.V, A.lm.L, A.lm.Hl);
-    }
-    __shared__ double s_blp[BEAM_MAXK], s_bkey[BEAM_MAXK], s_tlp[BEAM_MAXK];
-    __shared__ int s_bidx[BEAM_MAXK], s_tpos[BEAM_MAXK], s_order[BEAM_MAXK];
-    __shared__ int s_ctl[16];                                // the narrow kernel's control words
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap, lmw);
-    unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES);
-    int *hdr = reinterpret_cast<int *>(wsu);
-    BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
-    int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
-    float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
-    int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
-    const int SWP = J + 2 * H;                               // floats per slot: pn | h | c
     const int SW = SWP + lmw;                                // LM: | lm_logp[Vp] | lm_h | lm_c
     const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
-    const WT *w_ih = (const WT *)A.w_ih, *w_hh = (const WT *)A.w_hh, *w_proj = (const WT *)A.w_proj, *w_head = (const WT *)A.w_head;
     const bool fresh = A.n_valid == nullptr;
     const int tend = fresh ? A.T : min(max(A.n_valid[b], 0), A.T);
     const int fbase = (TIMES && !fresh) ? hdr[4] : 0;        // frames of this stream decoded before this call (written after the last frame)
@@ -991,82 +622,26 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const Be
             if (s_ctl[8]) {                                  // predictor step of node a: pn(token, parent's state), once per node
                 const int ps = s_ctl[9], tok = s_ctl[10];
                 const float *pst = ps >= 0 ? slots + (size_t)ps * SW : nullptr;
-                for (int i = tid; i < 2 * H; i += BEAM_THREADS) h[i] = pst ? pst[J + i] : 0.f;   // h | c contiguous in LDS and in a slot
-                for (int e = tid; e < A.E; e += BEAM_THREADS) x[e] = A.emb[(size_t)tok * A.E + e];
-                __syncthreads();
-                if (A.E <= 64) {
-                    gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, w_ih, A.E, x, gates);
-                } else {
-                    gemv_rows<WT>(w_hh, 4 * H, H, h, A.b_ih, A.b_hh, nullptr, 0, nullptr, gates);
-                    __syncthreads();
-                    if (A.E % 4 == 0) {
-                        gemv_rows_acc<WT>(w_ih, 4 * H, A.E, x, gates);
-                    } else {
-                        for (int r = tid; r < 4 * H; r += BEAM_THREADS) {
-                            float acc = 0.f;
-                            for (int e = 0; e < A.E; ++e) {
-                                const float xe = x[e];                 // the same LDS word for every thread: a uniform branch
-                                if (xe != 0.f) acc += (float)w_ih[(size_t)r * A.E + e] * xe;
-                            }
-                            gates[r] += acc;
-                        }
-                    }
-                }
-                __syncthreads();
-                for (int u = tid; u < H; u += BEAM_THREADS) {
-                    const float ig = sigmoid_f(gates[u]), fg = sigmoid_f(gates[H + u]), gg = tanhf(gates[2 * H + u]), og = sigmoid_f(gates[3 * H + u]);
-                    const float cn = fg * c[u] + ig * gg;
-                    c[u] = cn;
-                    h[u] = og * tanhf(cn);
-                }
-                __syncthreads();
-                gemv_rows<WT>(w_proj, J, H, h, A.b_proj, nullptr, nullptr, 0, nullptr, pn);
-                __syncthreads();
-                for (int i = tid; i < SWP; i += BEAM_THREADS) sl[i] = i < J ? pn[i] : h[i - J];    // slot = pn | h | c (h, c adjacent in LDS)
+                for (int i = tid; i < 2 * H; i += SEARCH_THREADS) h[i] = pst ? pst[J + i] : 0.f;   // h | c contiguous in LDS and in a slot
+                predictor_step<WT, WIDE>(A.net, A.E, H, J, tok, x, h, c, gates, pn);
+                for (int i = tid; i < SWP; i += SEARCH_THREADS) sl[i] = i < J ? pn[i] : h[i - J];    // slot = pn | h | c (h, c adjacent in LDS)
                 if constexpr (LM)                            // the LM step of the same token from the parent slot's LM state
-                    beam_lm_step<WT, true>(A.lm, A.V, tok, pst ? pst + SWP : nullptr, sl + SWP, lx, lh, lgt, llg, s_lmlp, s_stat, red);
+                    beam_lm_step<WT, WIDE>(A.lm, A.V, tok, pst ? pst + SWP : nullptr, sl + SWP, lx, lh, lgt, llg, s_lmlp, s_stat, red);
             } else {
-                for (int k = tid; k < J; k += BEAM_THREADS) pn[k] = sl[k];
+                for (int k = tid; k < J; k += SEARCH_THREADS) pn[k] = sl[k];
                 if constexpr (LM)
-                    for (int i = tid; i < A.V; i += BEAM_THREADS) s_lmlp[i] = sl[SWP + i];
+                    for (int i = tid; i < (WIDE ? A.V : 64); i += SEARCH_THREADS) s_lmlp[i] = sl[SWP + i];
                 __syncthreads();
             }
-            for (int k = tid; k < J; k += BEAM_THREADS) {
+            for (int k = tid; k < J; k += SEARCH_THREADS) {
                 const float v = ld1(enc + (size_t)t * J + k) + pn[k];
                 z[k] = v > 0.f ? v : v * A.slope;
             }
             __syncthreads();
-            gemv_rows<WT>(w_head, A.V, J, z, A.b_head, nullptr, nullptr, 0, nullptr, lg);
+            gemv_rows<WT>((const WT *)A.net.w_head, A.V, J, z, A.net.b_head, nullptr, nullptr, 0, nullptr, lg);
             __syncthreads();
-            {                                                // log_softmax and top-k over the workgroup (V <= BEAM_THREADS: one entry per thread)
-                const float lp = beam_wide_log_softmax(tid < A.V ? lg[tid] : -INFINITY, red);
-                bool taken = tid >= A.V;
-                for (int r = 0; r < A.beam; ++r) {
-                    float k = lp;
-                    int i = taken ? INT_MAX : tid;
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) {
-                        const float k2 = __shfl_xor(k, m);
-                        const int i2 = __shfl_xor(i, m);
-                        beam_topk_pick(k, i, k2, i2);
-                    }
-                    float *rk = red + 32 + (r & 1) * 16;
-                    int *ri = reinterpret_cast<int *>(red + 64) + (r & 1) * 16;
-                    if (lane == 0) { rk[wave] = k; ri[wave] = i; }
-                    __syncthreads();
-                    float bk = rk[0];
-                    int bi = ri[0];
-#pragma unroll
-                    for (int w = 1; w < BEAM_THREADS / 64; ++w) beam_topk_pick(bk, bi, rk[w], ri[w]);
-                    if (tid == bi) {
-                        taken = true;
-                        s_tlp[r] = (double)lp;
-                        s_tpos[r] = tid;
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid == 0) {                                  // the appends, in top-k order
+            // the appends, in top-k order: run by ONE thread once s_tlp / s_tpos hold the top-k of log_softmax(lg)
+            const auto append = [&]() __attribute__((always_inline)) {
                 const double alp = Alp[a];
                 const int alen = Alen[a];
                 const double bnb = s_tpos[0] != A.blank ? s_tlp[0] : s_tlp[1];
@@ -1097,6 +672,55 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const Be
                 }
                 s_ctl[0] = nA;
                 s_ctl[1] = nb;
+            };
+            if constexpr (WIDE) {                            // log_softmax and top-k over the workgroup (V <= SEARCH_THREADS: one entry per thread)
+                const float lp = beam_wide_log_softmax(tid < A.V ? lg[tid] : -INFINITY, red);
+                bool taken = tid >= A.V;
+                for (int r = 0; r < A.beam; ++r) {
+                    float k = lp;
+                    int i = taken ? INT_MAX : tid;
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) {
+                        const float k2 = __shfl_xor(k, m);
+                        const int i2 = __shfl_xor(i, m);
+                        beam_topk_pick(k, i, k2, i2);
+                    }
+                    float *rk = red + 32 + (r & 1) * 16;
+                    int *ri = reinterpret_cast<int *>(red + 64) + (r & 1) * 16;
+                    if (lane == 0) { rk[wave] = k; ri[wave] = i; }
+                    __syncthreads();
+                    float bk = rk[0];
+                    int bi = ri[0];
+#pragma unroll
+                    for (int w = 1; w < SEARCH_THREADS / 64; ++w) beam_topk_pick(bk, bi, rk[w], ri[w]);
+                    if (tid == bi) {
+                        taken = true;
+                        s_tlp[r] = (double)lp;
+                        s_tpos[r] = tid;
+                    }
+                }
+                __syncthreads();
+                if (tid == 0) append();
+            } else if (wave == 0) {                          // log_softmax, top-k (equal values: lower index first), the appends: one wave
+                __shared__ float s_lp[64];
+                const float v = lane < A.V ? lg[lane] : -INFINITY;
+                const float m = wave_max(v);
+                const float s = wave_sum(lane < A.V ? expf(v - m) : 0.f);
+                const float lp = (v - m) - logf(s);
+                s_lp[lane] = lp;
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (lane < A.V) {
+                    int rank = 0;
+                    for (int u = 0; u < A.V; ++u) {
+                        const float o = s_lp[u];
+                        rank += (o > lp) || (o == lp && u < lane);
+                    }
+                    if (rank < A.beam) { s_tlp[rank] = (double)lp; s_tpos[rank] = lane; }
+                }
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (lane == 0) append();
             }
             __syncthreads();
             if (s_ctl[11] != 0) break;
@@ -1179,7 +803,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const Be
     }
     if (tid < nbeam && st == 0 && run) bent[tid] = BeamEnt{Alp[tid], Anode[tid], Alen[tid], Aslot[tid], Atok[tid]};
     __syncthreads();
-    for (int r = wave; r < A.nbest; r += BEAM_THREADS / 64) {  // one wave's lane 0 walks a hypothesis up the tree
+    for (int r = wave; r < A.nbest; r += SEARCH_THREADS / 64) {  // one wave's lane 0 walks a hypothesis up the tree
         const int e = s_order[r];
         if (lane == 0 && e >= 0) {
             int node = Anode[e];
@@ -1197,6 +821,42 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_wide_kernel(const Be
     }
 }
 
+// RUN(T, WT) with the io and the weight type that the two (checked) dtype codes name
+#define SEARCH_DTYPES(io_dtype, wdtype, RUN)                                                        \
+    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) RUN(float, float) else RUN(float, bf16_t) } \
+    else { if (wdtype == TSASR_F32) RUN(bf16_t, float) else RUN(bf16_t, bf16_t) }
+
+template <typename Args>
+void search_launch(void (*kern)(const Args), int B, size_t lds, void *stream, const Args &a) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kern<<<B, SEARCH_THREADS, lds, (hipStream_t)stream>>>(a);
+}
+
+// The four greedy entry points. wide: V <= 1024 and E <= 1024 instead of V <= 63 and E <= 64; streamed: state and n_valid are given.
+int greedy_launch(const char *name, bool wide, bool streamed, const void *enc, const NetArgs &net, float *state, const int32_t *n_valid,
+                  int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype,
+                  void *stream) {
+    TSASR_CHECK_ARG(enc && net.emb && net.w_ih && net.w_hh && net.w_proj && net.w_head && preds && logp_sum && (!streamed || (state && n_valid)),
+                    "%s: null pointer", name);
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= (wide ? 1024 : 64) && V > 1 &&
+                    V <= (wide ? 1024 : 63) && blank >= 0 && blank < V,
+                    "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
+    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
+    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
+    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + (wide ? round4(E) + round4(V) + 64 : 64 + 64)) * sizeof(float);
+    if (wide) TSASR_CHECK_ARG(lds <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d need %zu B of LDS", name, H, J, E, V, lds);
+    else TSASR_CHECK_ARG(lds <= 160 * 1024, "%s: H=%d J=%d need %zu B of LDS", name, H, J, lds);
+    const GreedyArgs a{enc, net, preds, logp_sum, B, T, J, H, E, V, blank, slope, state, n_valid};
+#define GREEDY(TT, WW)                                                                                                                  \
+    search_launch(wide ? (streamed ? greedy_decode_kernel<TT, WW, true, true> : greedy_decode_kernel<TT, WW, false, true>)              \
+                       : (streamed ? greedy_decode_kernel<TT, WW, true, false> : greedy_decode_kernel<TT, WW, false, false>),           \
+                  B, lds, stream, a);
+    SEARCH_DTYPES(io_dtype, wdtype, GREEDY)
+#undef GREEDY
+    TSASR_CHECK_LAUNCH(name);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1208,27 +868,8 @@ extern "C" {
 int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
                         int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream) {
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && preds && logp_sum, "tsasr_greedy_decode: null pointer");
-    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
-                    "tsasr_greedy_decode: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", B, T, J, H, E, V, blank);
-    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "tsasr_greedy_decode: J=%d H=%d above 1024", J, H);
-    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "tsasr_greedy_decode: bad dtype");
-    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + 64 + 64) * sizeof(float);
-    TSASR_CHECK_ARG(lds <= 160 * 1024, "tsasr_greedy_decode: H=%d J=%d need %zu B of LDS", H, J, lds);
-    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope,
-                 nullptr, nullptr};
-    hipStream_t st = (hipStream_t)stream;
-#define GREEDY(TT, WW)                                                                                                          \
-    {                                                                                                                           \
-        auto kern = greedy_decode_kernel<TT, WW, false>;                                                                               \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                                           \
-    }
-    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) GREEDY(float, float) else GREEDY(float, bf16_t) }
-    else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
-#undef GREEDY
-    TSASR_CHECK_LAUNCH("tsasr_greedy_decode");
-    return 0;
+    return greedy_launch("tsasr_greedy_decode", false, false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, nullptr, nullptr,
+                         preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
 /* tsasr_greedy_decode over one chunk of a stream: state fp32 [B, 2H + J + 4] (caller-owned, zeroed before the first chunk) carries the
@@ -1239,82 +880,26 @@ int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_
                                const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state, const int32_t *n_valid,
                                int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype,
                                int wdtype, void *stream) {
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && state && n_valid && preds && logp_sum, "tsasr_greedy_decode_stream: null pointer");
-    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
-                    "tsasr_greedy_decode_stream: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", B, T, J, H, E, V, blank);
-    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "tsasr_greedy_decode_stream: J=%d H=%d above 1024", J, H);
-    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "tsasr_greedy_decode_stream: bad dtype");
-    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + 64 + 64) * sizeof(float);
-    TSASR_CHECK_ARG(lds <= 160 * 1024, "tsasr_greedy_decode_stream: H=%d J=%d need %zu B of LDS", H, J, lds);
-    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope,
-                 state, n_valid};
-    hipStream_t st = (hipStream_t)stream;
-#define GREEDY(TT, WW)                                                                                                          \
-    {                                                                                                                           \
-        auto kern = greedy_decode_kernel<TT, WW, true>;                                                                         \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                                \
-    }
-    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) GREEDY(float, float) else GREEDY(float, bf16_t) }
-    else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
-#undef GREEDY
-    TSASR_CHECK_LAUNCH("tsasr_greedy_decode_stream");
-    return 0;
+    return greedy_launch("tsasr_greedy_decode_stream", false, true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, state,
+                         n_valid, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
 /* The two greedy searches for subword vocabularies: the arguments, outputs and stream state of tsasr_greedy_decode / _stream with
- * V <= 1024 and E <= 1024 (a frozen one-hot table has E = V - 1: any E is taken, a multiple of 4 runs the dense product). n_valid / state NULL:
- * the one-call form. The narrow entry points and their kernels are untouched; the host sends V <= 63 with E <= 64 there. */
-static int greedy_wide_launch(const char *name, const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih,
-                              const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
-                              const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope,
-                              int io_dtype, int wdtype, void *stream) {
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && preds && logp_sum, "%s: null pointer", name);
-    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 1024 && V > 1 && V <= 1024 && blank >= 0 && blank < V,
-                    "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
-    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
-    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
-    const size_t lds = (size_t)(2 * H + 2 * J + 4 * H + ((E + 3) & ~3) + ((V + 3) & ~3) + 64) * sizeof(float);
-    TSASR_CHECK_ARG(lds <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d need %zu B of LDS", name, H, J, E, V, lds);
-    GreedyArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, preds, logp_sum, B, T, J, H, E, V, blank, slope, state, n_valid};
-    hipStream_t st = (hipStream_t)stream;
-#define GREEDY(TT, WW)                                                                                                            \
-    {                                                                                                                             \
-        if (state) {                                                                                                              \
-            auto kern = greedy_decode_wide_kernel<TT, WW, true>;                                                                  \
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                              \
-        } else {                                                                                                                  \
-            auto kern = greedy_decode_wide_kernel<TT, WW, false>;                                                                 \
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            kern<<<B, GREEDY_THREADS, lds, st>>>(a);                                                                              \
-        }                                                                                                                         \
-    }
-    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) GREEDY(float, float) else GREEDY(float, bf16_t) }
-    else { if (wdtype == TSASR_F32) GREEDY(bf16_t, float) else GREEDY(bf16_t, bf16_t) }
-#undef GREEDY
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        tsasr_set_error("%s: launch failed: %s", name, hipGetErrorString(e));
-        return TSASR_E_LAUNCH;
-    }
-    return 0;
-}
-
+ * V <= 1024 and E <= 1024 (a frozen one-hot table has E = V - 1: any E is taken, a multiple of 4 runs the dense product). The host sends
+ * V <= 63 with E <= 64 to the narrow entry points. */
 int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
                              const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
                              int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream) {
-    return greedy_wide_launch("tsasr_greedy_decode_wide", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, nullptr, nullptr, preds,
-                              logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
+    return greedy_launch("tsasr_greedy_decode_wide", true, false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, nullptr,
+                         nullptr, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
 int tsasr_greedy_decode_stream_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
                                     const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
                                     const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
                                     float slope, int io_dtype, int wdtype, void *stream) {
-    TSASR_CHECK_ARG(state && n_valid, "tsasr_greedy_decode_stream_wide: null pointer");
-    return greedy_wide_launch("tsasr_greedy_decode_stream_wide", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, state, n_valid,
-                              preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
+    return greedy_launch("tsasr_greedy_decode_stream_wide", true, true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, state,
+                         n_valid, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
 /* Beam transducer search (speechbrain/decoders/transducer.py:220-373, no LM) for the networks tsasr_greedy_decode takes; see the kernel's
@@ -1333,7 +918,7 @@ static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap
  * timed layout. 0 for a non-positive size. */
 size_t tsasr_beam_search_lm_workspace_bytes(int B, int T, int H, int J, int beam, int cap, int lm_layers, int lm_hidden, int times) {
     if (lm_layers <= 0 || lm_hidden <= 0) return 0;
-    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, beam_lm_slot_floats(lm_layers, lm_hidden));
+    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, beam_lm_slot_floats(false, 0, lm_layers, lm_hidden));
 }
 
 /* The timed searches' workspace: the untimed layout of each utterance plus one int per tree node (align16(4 (1 + (T + 1) beam + cap))). */
@@ -1341,61 +926,68 @@ size_t tsasr_beam_search_timed_workspace_bytes(int B, int T, int H, int J, int b
     return beam_workspace_bytes(B, T, H, J, beam, cap, true);
 }
 
-static int beam_launch(const char *name, const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih,
-                       const float *b_hh, const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                       size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores,
-                       int *status, int B, int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
-                       double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream,
-                       const tsasr_lm_desc *lm = nullptr, double lm_weight = 0.0) {
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status && (frames || !times),
-                    "%s: null pointer", name);
-    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 64 && V > 1 && V <= 63 && blank >= 0 && blank < V,
+// Checks an LM descriptor and restates it, with the fusion weight, as the kernel's arguments
+static int beam_lm_args(const char *name, const tsasr_lm_desc *lm, double lm_weight, BeamLmArgs &m) {
+    const int Ll = lm->layers, Hl = lm->hidden, El = lm->emb_dim, nb = lm->dnn_blocks, D = lm->dnn_neurons;
+    TSASR_CHECK_ARG(Ll >= 1 && Ll <= 4 && Hl > 0 && Hl % 4 == 0 && Hl <= 1024 && El > 0 && El % 4 == 0 && El <= 1024 && nb >= 0 && nb <= 2 &&
+                    D > 0 && D % 4 == 0 && D <= 1024 && (nb > 0 || D == Hl),
+                    "%s: bad LM shape (layers=%d hidden=%d emb_dim=%d dnn_blocks=%d dnn_neurons=%d)", name, Ll, Hl, El, nb, D);
+    bool ptrs = lm->emb && lm->w_out;
+    for (int l = 0; l < Ll; ++l) ptrs = ptrs && lm->w_ih[l] && lm->w_hh[l];
+    for (int k = 0; k < nb; ++k) ptrs = ptrs && lm->w_dnn[k];
+    TSASR_CHECK_ARG(ptrs, "%s: null LM pointer", name);
+    m.emb = lm->emb;
+    for (int l = 0; l < 4; ++l) { m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l]; m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l]; }
+    for (int k = 0; k < 2; ++k) {
+        m.w_dnn[k] = lm->w_dnn[k]; m.b_dnn[k] = lm->b_dnn[k]; m.ln_g[k] = lm->ln_g[k]; m.ln_b[k] = lm->ln_b[k]; m.ln_eps[k] = lm->ln_eps[k];
+    }
+    m.w_out = lm->w_out; m.b_out = lm->b_out;
+    m.L = Ll; m.Hl = Hl; m.E = El; m.nb = nb; m.D = D; m.slope = lm->slope; m.weight = lm_weight;
+    return 0;
+}
+
+// Every beam entry point. wide: V <= 1024, E <= 1024 and the LDS budget of the wide instantiations; times: frames are reported.
+static int beam_launch(const char *name, bool wide, const void *enc, const NetArgs &net, void *workspace, size_t workspace_bytes,
+                       const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores, int *status, int B, int T,
+                       int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                       double expand_beam, float slope, int io_dtype, int wdtype, void *stream, const tsasr_lm_desc *lm = nullptr,
+                       double lm_weight = 0.0) {
+    TSASR_CHECK_ARG(enc && net.emb && net.w_ih && net.w_hh && net.w_proj && net.w_head && workspace && hyps && lens && scores && status &&
+                    (frames || !times), "%s: null pointer", name);
+    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= (wide ? 1024 : 64) && V > 1 &&
+                    V <= (wide ? SEARCH_THREADS : 63) && blank >= 0 && blank < V,
                     "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
     TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
-    TSASR_CHECK_ARG(beam >= 2 && beam <= V && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
+    TSASR_CHECK_ARG(beam >= 2 && beam <= V && beam <= BEAM_MAXK && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
                     "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
     TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
+    const int Ep = wide ? round4(E) : 64, Vp = wide ? round4(V) : 64;
     BeamLmArgs m{};
     size_t lm_lds = 0;
     if (lm) {
-        const int Ll = lm->layers, Hl = lm->hidden, El = lm->emb_dim, nb = lm->dnn_blocks, D = lm->dnn_neurons;
-        TSASR_CHECK_ARG(Ll >= 1 && Ll <= 4 && Hl > 0 && Hl % 4 == 0 && Hl <= 1024 && El > 0 && El % 4 == 0 && El <= 1024 && nb >= 0 && nb <= 2 &&
-                        D > 0 && D % 4 == 0 && D <= 1024 && (nb > 0 || D == Hl),
-                        "%s: bad LM shape (layers=%d hidden=%d emb_dim=%d dnn_blocks=%d dnn_neurons=%d)", name, Ll, Hl, El, nb, D);
-        bool ptrs = lm->emb && lm->w_out;
-        for (int l = 0; l < Ll; ++l) ptrs = ptrs && lm->w_ih[l] && lm->w_hh[l];
-        for (int k = 0; k < nb; ++k) ptrs = ptrs && lm->w_dnn[k];
-        TSASR_CHECK_ARG(ptrs, "%s: null LM pointer", name);
-        m.emb = lm->emb;
-        for (int l = 0; l < 4; ++l) { m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l]; m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l]; }
-        for (int k = 0; k < 2; ++k) {
-            m.w_dnn[k] = lm->w_dnn[k]; m.b_dnn[k] = lm->b_dnn[k]; m.ln_g[k] = lm->ln_g[k]; m.ln_b[k] = lm->ln_b[k]; m.ln_eps[k] = lm->ln_eps[k];
-        }
-        m.w_out = lm->w_out; m.b_out = lm->b_out;
-        m.L = Ll; m.Hl = Hl; m.E = El; m.nb = nb; m.D = D; m.slope = lm->slope; m.weight = lm_weight;
-        lm_lds = (size_t)(std::max(std::max(El, Hl), D) + 2 * Hl + std::max(4 * Hl, D) + 64 + 64 + 2) * sizeof(float);
+        if (const int err = beam_lm_args(name, lm, lm_weight, m)) return err;
+        lm_lds = (size_t)(std::max(std::max(m.E, m.Hl), m.D) + 2 * m.Hl + std::max(4 * m.Hl, m.D) + 2 * Vp + 2) * sizeof(float);
     }
-    const int lmw = lm ? beam_lm_slot_floats(lm->layers, lm->hidden) : 0;
+    const int lmw = lm ? beam_lm_slot_floats(wide, V, lm->layers, lm->hidden) : 0;
     const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw);
     TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
-    const size_t lds = (size_t)(6 * H + 2 * J + 128) * sizeof(float) + (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
-    TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
-    BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
-               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope, frames};
-    hipStream_t st = (hipStream_t)stream;
-#define BEAM(TT, WW)                                                                                                            \
-    if (lm) {                                                                                                                   \
-        auto kern = times ? beam_search_kernel<TT, WW, true, true> : beam_search_kernel<TT, WW, false, true>;                   \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<true>{a, m});                                                           \
-    } else {                                                                                                                    \
-        auto kern = times ? beam_search_kernel<TT, WW, true, false> : beam_search_kernel<TT, WW, false, false>;                 \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<false>{a});                                                             \
+    // dynamic LDS (the kernel's comment); wide: + 4 KB for its static arrays (the beam's and the top-k's, 2.4 KB) within the CU's 160 KB
+    const size_t lds = (size_t)(6 * H + 2 * J + Ep + Vp + (wide ? 96 : 0)) * sizeof(float) +
+                       (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
+    if (wide) TSASR_CHECK_ARG(lds + 4096 <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d cap=%d need %zu B of LDS", name, H, J, E, V, cap, lds);
+    else TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
+    const BeamArgs a{enc, net, (unsigned char *)workspace, n_valid, hyps, lens, scores, status, B, T, J, H, E, V, blank, beam, nbest, cap,
+                     Lmax, max_frames, state_beam, expand_beam, slope, frames};
+#define BEAM_KERN(TT, WW, LM) (wide ? (times ? beam_search_kernel<TT, WW, true, LM, true> : beam_search_kernel<TT, WW, false, LM, true>) \
+                                    : (times ? beam_search_kernel<TT, WW, true, LM, false> : beam_search_kernel<TT, WW, false, LM, false>))
+#define BEAM(TT, WW)                                                                              \
+    {                                                                                             \
+        if (lm) search_launch(BEAM_KERN(TT, WW, true), B, lds, stream, BeamKernArgs<true>{a, m}); \
+        else search_launch(BEAM_KERN(TT, WW, false), B, lds, stream, BeamKernArgs<false>{a});     \
     }
-    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) BEAM(float, float) else BEAM(float, bf16_t) }
-    else { if (wdtype == TSASR_F32) BEAM(bf16_t, float) else BEAM(bf16_t, bf16_t) }
+    SEARCH_DTYPES(io_dtype, wdtype, BEAM)
 #undef BEAM
+#undef BEAM_KERN
     TSASR_CHECK_LAUNCH(name);
     return 0;
 }
@@ -1409,7 +1001,7 @@ int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const
                       const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
                       int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
                       int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
-    return beam_launch("tsasr_beam_search", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+    return beam_launch("tsasr_beam_search", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
                        nullptr, hyps, nullptr, false, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
                        expand_beam, slope, io_dtype, wdtype, stream);
 }
@@ -1423,7 +1015,7 @@ int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih
                              int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
                              double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
     TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream: null n_valid");
-    return beam_launch("tsasr_beam_search_stream", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
+    return beam_launch("tsasr_beam_search_stream", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
                        workspace_bytes, n_valid, hyps, nullptr, false, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
                        cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
 }
@@ -1437,7 +1029,7 @@ int tsasr_beam_search_timed(const void *enc, const float *emb, const void *w_ih,
                             size_t workspace_bytes, int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V,
                             int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype,
                             int wdtype, void *stream, int *frames) {
-    return beam_launch("tsasr_beam_search_timed", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+    return beam_launch("tsasr_beam_search_timed", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
                        nullptr, hyps, frames, true, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
                        expand_beam, slope, io_dtype, wdtype, stream);
 }
@@ -1451,7 +1043,7 @@ int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void
                                    int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
                                    double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames) {
     TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream_timed: null n_valid");
-    return beam_launch("tsasr_beam_search_stream_timed", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace,
+    return beam_launch("tsasr_beam_search_stream_timed", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
                        workspace_bytes, n_valid, hyps, frames, true, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
                        cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
 }
@@ -1466,16 +1058,16 @@ int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, co
                          double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
                          double lm_weight) {
     TSASR_CHECK_ARG(lm, "tsasr_beam_search_lm: null lm");
-    return beam_launch("tsasr_beam_search_lm", enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, workspace, workspace_bytes,
+    return beam_launch("tsasr_beam_search_lm", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
                        n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
                        Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
 }
 
-/* The wide search's workspace (beam_search_wide_kernel), a function of the shape alone: the narrow layout with the slot's LM part
+/* The wide search's workspace (beam_search_kernel's WIDE), a function of the shape alone: the narrow layout with the slot's LM part
  * widened to round_up(V, 4) + 2 lm_layers lm_hidden floats; lm_layers == 0: no LM (lm_hidden is not read). 0 for a shape no call takes. */
 size_t tsasr_beam_search_wide_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times) {
     if (V <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
-    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_wide_lm_slot_floats(V, lm_layers, lm_hidden) : 0);
+    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_lm_slot_floats(true, V, lm_layers, lm_hidden) : 0);
 }
 
 /* The beam search for subword vocabularies: tsasr_beam_search_lm's arguments with V <= 1024, E <= 1024 (any E; a multiple of 4 runs the
@@ -1487,61 +1079,9 @@ int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, 
                            int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
                            double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
                            double lm_weight) {
-    const char *name = "tsasr_beam_search_wide";
-    const bool times = frames != nullptr;
-    TSASR_CHECK_ARG(enc && emb && w_ih && w_hh && w_proj && w_head && workspace && hyps && lens && scores && status, "%s: null pointer", name);
-    TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= 1024 && V > 1 && V <= BEAM_THREADS && blank >= 0 &&
-                    blank < V, "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
-    TSASR_CHECK_ARG(J <= 1024 && H <= 1024, "%s: J=%d H=%d above 1024", name, J, H);
-    TSASR_CHECK_ARG(beam >= 2 && beam <= V && beam <= BEAM_MAXK && nbest >= 1 && nbest <= BEAM_MAXK && cap >= beam && Lmax >= 1 && max_frames >= 1,
-                    "%s: bad search settings (beam=%d V=%d nbest=%d cap=%d Lmax=%d max_frames=%d)", name, beam, V, nbest, cap, Lmax, max_frames);
-    TSASR_CHECK_ARG((io_dtype == TSASR_F32 || io_dtype == TSASR_BF16) && (wdtype == TSASR_F32 || wdtype == TSASR_BF16), "%s: bad dtype", name);
-    const int Vp = beam_round4(V);
-    BeamLmArgs m{};
-    size_t lm_lds = 0;
-    if (lm) {
-        const int Ll = lm->layers, Hl = lm->hidden, El = lm->emb_dim, nb = lm->dnn_blocks, D = lm->dnn_neurons;
-        TSASR_CHECK_ARG(Ll >= 1 && Ll <= 4 && Hl > 0 && Hl % 4 == 0 && Hl <= 1024 && El > 0 && El % 4 == 0 && El <= 1024 && nb >= 0 && nb <= 2 &&
-                        D > 0 && D % 4 == 0 && D <= 1024 && (nb > 0 || D == Hl),
-                        "%s: bad LM shape (layers=%d hidden=%d emb_dim=%d dnn_blocks=%d dnn_neurons=%d)", name, Ll, Hl, El, nb, D);
-        bool ptrs = lm->emb && lm->w_out;
-        for (int l = 0; l < Ll; ++l) ptrs = ptrs && lm->w_ih[l] && lm->w_hh[l];
-        for (int k = 0; k < nb; ++k) ptrs = ptrs && lm->w_dnn[k];
-        TSASR_CHECK_ARG(ptrs, "%s: null LM pointer", name);
-        m.emb = lm->emb;
-        for (int l = 0; l < 4; ++l) { m.w_ih[l] = lm->w_ih[l]; m.w_hh[l] = lm->w_hh[l]; m.b_ih[l] = lm->b_ih[l]; m.b_hh[l] = lm->b_hh[l]; }
-        for (int k = 0; k < 2; ++k) {
-            m.w_dnn[k] = lm->w_dnn[k]; m.b_dnn[k] = lm->b_dnn[k]; m.ln_g[k] = lm->ln_g[k]; m.ln_b[k] = lm->ln_b[k]; m.ln_eps[k] = lm->ln_eps[k];
-        }
-        m.w_out = lm->w_out; m.b_out = lm->b_out;
-        m.L = Ll; m.Hl = Hl; m.E = El; m.nb = nb; m.D = D; m.slope = lm->slope; m.weight = lm_weight;
-        lm_lds = (size_t)(std::max(std::max(El, Hl), D) + 2 * Hl + std::max(4 * Hl, D) + 2 * Vp + 2) * sizeof(float);
-    }
-    const int lmw = lm ? beam_wide_lm_slot_floats(V, lm->layers, lm->hidden) : 0;
-    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw);
-    TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
-    // dynamic LDS (the kernel's comment) + 4 KB for its static arrays (the beam's and the top-k's, 2.4 KB) within the CU's 160 KB
-    const size_t lds = (size_t)(6 * H + 2 * J + beam_round4(E) + Vp + 96) * sizeof(float) +
-                       (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
-    TSASR_CHECK_ARG(lds + 4096 <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d cap=%d need %zu B of LDS", name, H, J, E, V, cap, lds);
-    BeamArgs a{enc, emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head, (unsigned char *)workspace, n_valid, hyps, lens, scores,
-               status, B, T, J, H, E, V, blank, beam, nbest, cap, Lmax, max_frames, state_beam, expand_beam, slope, frames};
-    hipStream_t st = (hipStream_t)stream;
-#define BEAM(TT, WW)                                                                                                            \
-    if (lm) {                                                                                                                   \
-        auto kern = times ? beam_search_wide_kernel<TT, WW, true, true> : beam_search_wide_kernel<TT, WW, false, true>;         \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<true>{a, m});                                                           \
-    } else {                                                                                                                    \
-        auto kern = times ? beam_search_wide_kernel<TT, WW, true, false> : beam_search_wide_kernel<TT, WW, false, false>;       \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        kern<<<B, BEAM_THREADS, lds, st>>>(BeamKernArgs<false>{a});                                                             \
-    }
-    if (io_dtype == TSASR_F32) { if (wdtype == TSASR_F32) BEAM(float, float) else BEAM(float, bf16_t) }
-    else { if (wdtype == TSASR_F32) BEAM(bf16_t, float) else BEAM(bf16_t, bf16_t) }
-#undef BEAM
-    TSASR_CHECK_LAUNCH(name);
-    return 0;
+    return beam_launch("tsasr_beam_search_wide", true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
+                       n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
+                       Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
 }
 
 }  // extern "C"
