@@ -161,7 +161,10 @@ __global__ __launch_bounds__(SN_NT) void sentence_norm_kernel(const TI *__restri
     if (threadIdx.x < Fq) {
         float a = 0.f;
         for (int q = 0; q < rows; ++q) a += sm[q * Fq + threadIdx.x];
-        inv[threadIdx.x] = 1.f / fmaxf(sqrtf(a / (n - 1)), eps);  // unbiased; n == 1 gives NaN exactly as torch.std does
+        // unbiased; n == 1 is 0 / 0 = NaN as torch.std gives it, and the reference's max(std, eps) hands that NaN on. fmaxf would not
+        // (fmaxf(NaN, eps) = eps, which wrote (x - x[0]) / eps into the row): eps is selected only where the deviation compares below it
+        const float sd = sqrtf(a / (n - 1));
+        inv[threadIdx.x] = 1.f / (sd < eps ? eps : sd);
     }
     __syncthreads();
     TO *yb = y + (long long)b * Tn * Fq;
@@ -208,7 +211,8 @@ int tsasr_fbank_fwd(const float *wav, const float *window, const float *melmat, 
     return 0;
 }
 
-/* y = (x - mean_b) / max(std_b, eps), statistics per utterance and feature bin over the first lens[b] frames (unbiased std). */
+/* y = (x - mean_b) / max(std_b, eps), statistics per utterance and feature bin over the first lens[b] frames (unbiased std;
+ * lens[b] <= 1: the deviation of one frame is NaN, and so is the whole row, as in the reference). */
 int tsasr_sentence_norm_fwd(const void *x, const int32_t *lens, void *y, int B, int T, int F, float eps, int in_dtype, int out_dtype,
                             void *stream) {
     TSASR_CHECK_ARG(x && lens && y, "tsasr_sentence_norm_fwd: null pointer");
