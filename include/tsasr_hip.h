@@ -122,6 +122,40 @@ int tsasr_rnnt_align(const float *logits, const int32_t *targets, int ldt, const
                      int32_t *frames /* [B, ldf] */, int ldf, float *scores /* [B] */,
                      int B, int T, int U1, int V, int ldl, int blank, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused joint + RNN-T loss for subword vocabularies, 32 < V <= 1024 (csrc/joint_wide.hip): the loss and the forced alignment of
+ * tsasr_joint_wide_fwd's logits WITHOUT the [B,T,U1,V] logits / dlogits tensors (3.97 GB each at the benchmark batch and V = 1024).
+ *   fwd  : the vocabulary tiles of a lattice cell are folded into its log-sum-exp as they leave the matrix cores (online, in tile order);
+ *          lse / lp(blank) / lp(label) go straight into the lattice planes, then the lattice of tsasr_rnnt_loss_fwd runs. costs[b] as there.
+ *   bwd  : denc / ddec (io dtype) and dW [V,J] / dbias [V] (fp32) of sum_b gscale[b] * costs[b]. Both backward products recompute their
+ *          dlogits operand tile by tile from W, h and three scalars per lattice cell; rounding as tsasr_joint_wide_bwd (dlogits, W, h to
+ *          bf16, sums in fp32). dW / dbias are deferred like every parameter gradient while tsasr_reduce_defer(1) is in force.
+ *   align: tsasr_rnnt_align's best path (same tie rule, same outputs) on planes filled the same way.
+ * Ranges as tsasr_joint_wide_fwd (J % 32 == 0, J <= 1024), U1 <= 2048, targets [B, ldt] with ldt >= max(U1 - 1, 1); tlen / ulen are required
+ * and clamped as tsasr_rnnt_loss_fwd clamps them. tsasr_rnnt_lattice_plan governs these calls as it governs tsasr_rnnt_loss_*.
+ * Workspace = tsasr_rnnt_loss_workspace_bytes (first, so the split lattice's time-out word keeps its offset) + 3 floats per lattice cell
+ * + the denc shares of the cdiv(U1, 32) u tiles + the ddec shares of at most 8 frame ranges + at most 64 slabs of dW [V,J] and dbias
+ * (128 MiB of dW slabs at most): a function of the shape alone, nothing in it grows with B*T*U1*V. bwd takes the forward's workspace.
+ * No float atomics, no waiting between workgroups in the new kernels: two runs give the same bits. No allocation, no host read: capturable.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_joint_wide_loss_workspace_bytes(int B, int T, int U1, int J, int V);
+long long tsasr_joint_wide_loss_error_word_offset(int B, int T, int U1, int J, int V);   /* as tsasr_rnnt_loss_error_word_offset, in this workspace */
+int tsasr_joint_wide_loss_fwd(const void *enc, const void *dec, const float *W, const float *bias,
+                              const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen, float *costs,
+                              int B, int T, int U1, int J, int V, int blank, int io_dtype, float slope,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int tsasr_joint_wide_loss_bwd(const void *enc, const void *dec, const float *W, const float *bias,
+                              const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen, const float *gscale /* [B] */,
+                              void *denc, void *ddec, float *dW, float *dbias,
+                              int B, int T, int U1, int J, int V, int blank, int io_dtype, float slope,
+                              void *workspace /* the forward's */, size_t workspace_bytes, void *stream);
+size_t tsasr_joint_wide_align_workspace_bytes(int B, int T, int U1, int J, int V);
+int tsasr_joint_wide_align(const void *enc, const void *dec, const float *W, const float *bias,
+                           const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen,
+                           int32_t *frames /* [B, ldf] */, int ldf, float *scores /* [B] */,
+                           int B, int T, int U1, int J, int V, int blank, int io_dtype, float slope,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Row kernels of the Conformer block (HBM-bound, one pass each, fp32 math, deterministic column reductions).

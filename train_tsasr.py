@@ -22,6 +22,8 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
   --lm_ckpt FILE --lm_weight W : the TEST stage's beam search fuses a recurrent LM (decoders.py: LM fusion): FILE is a local state_dict
         of an RNNLM (the reference's keys; torch.save), its shape is read from the tensors; W > 0 is the LM's weight in the score. YAMLs
         that name lm_model / lm_weight themselves need neither option.
+  --joint_logits lazy : subword vocabularies (32 < V <= 1024): loss and alignment run the fused joint + loss kernels, the [B,T',U+1,V]
+        logits / dlogits tensors are never written (hparams key joint_logits: materialized | lazy; default materialized).
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
 import importlib
 import os

@@ -183,4 +183,10 @@ def load_hyperpyyaml(yaml_stream, overrides=None):
         out[k] = res.key(k)
     for k, v in res.overrides.items():
         out.setdefault(k, v)
+    if "joint_logits" in out and out["joint_logits"] not in JOINT_LOGITS_ROUTES:
+        raise ValueError(f"joint_logits: {out['joint_logits']!r} is not one of {' | '.join(JOINT_LOGITS_ROUTES)} "
+                         "(materialized: the [B,T,U+1,V] logits tensor, the default; lazy: the fused joint + loss, no logits tensor)")
     return out
+
+
+JOINT_LOGITS_ROUTES = ("materialized", "lazy")

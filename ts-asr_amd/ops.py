@@ -24,6 +24,7 @@ STATUS = {
     "attention(fp32 parity, cross_attention injection)": "HIP (attention_f32: exact fp32)", "joint(fp32 parity)": "HIP (joint_f32)",
     "joint(32 < V <= 1024: subword vocabularies)": "HIP (joint_wide.hip: vocabulary tiles inside the kernels; bf16-rounded h / W / dlogits with bf16 OR fp32 activations - "
                                                    "an exact-fp32 wide joint is not built: compute_dtype fp32 with V > 32 runs these kernels with fp32 storage)",
+    "joint + loss without logits (joint_logits: lazy, 32 < V <= 1024)": "HIP (joint_wide.hip: joint_wide_lp / joint_wide_lazy_x / joint_wide_lazy_w; V <= 32 materialises)",
     "greedy search (V <= 1024, embedding <= 1024 columns)": "HIP (search.hip: greedy_decode_kernel for V <= 63 / E <= 64, greedy_decode_wide_kernel above)",
     "beam search / LM fusion with V > 63 or an embedding past 64 columns (V, E <= 1024, beam_size <= 64)":
         "HIP (search.hip: beam_search_wide_kernel, workgroup-wide log-softmax and top-k; offline, streams, timestamps and LM fusion)",

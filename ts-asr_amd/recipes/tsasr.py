@@ -221,8 +221,10 @@ class TSASR(core.Brain):
         head = self.modules.transducer_head.w
         tlen = abs_lengths_round(mixed_lens, enc_out.shape[1])
         ulen = abs_lengths_round(batch.tokens.lengths.to(self.device), batch.tokens.data.shape[1])
+        # hparams joint_logits: lazy -> a rnnt.JointLogits handle (the loss / alignment run the fused joint + loss kernels, no logits tensor)
+        lazy = getattr(self.hparams, "joint_logits", "materialized") == "lazy"
         logits = rnnt.fused_joint_logits(enc_out, dec_out, head.weight, head.bias, self.modules.joiner.nonlinearity.negative_slope,
-                                         tlen, ulen)
+                                         tlen, ulen, materialize=not lazy)
         prof.stamp("joint forward done [main]")
         return logits, enc_out, tlen, ulen, epoch
 
