@@ -730,6 +730,20 @@ size_t tsasr_relpos_attn_stream_workspace_bytes(int B, int C, int H, int Dh, int
 int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u, const float *bias_v,
                                  const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax, int t0, int causal, float scale,
                                  int io_dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* The same launch for a batch of slots that do not run in lockstep (same kernels, same key split, same workspace size): the scalar t0 is
+ * replaced by t0s, a DEVICE int32 [B], so no launch argument changes from chunk to chunk.
+ *   t0s[b] >= 0: slot b is active in this launch. Its chunk's queries sit at absolute frames t0s[b] .. t0s[b]+C-1 of its own stream; its
+ *     K and V rows are appended to its cache at t0s[b]; keys < t0s[b] come from its cache, the rest from qkv. key_lens[b], the causal
+ *     limit and the block-causal limit are all on that slot's own absolute frames; the band row is |i - j|.
+ *   t0s[b] < 0: slot b is idle. Nothing of its K/V cache is read or written, its `out` rows are written as exact zeros, its workgroups
+ *     leave at once (split, merge and unsplit launches alike).
+ * The caller checks t0s before the launch (the device array cannot be read here); in the kernel a slot whose t0s[b] + C > Tmax is
+ * treated as idle, so no row past the cache can be written. A slot's output equals tsasr_relpos_attn_stream_fwd's at t0 = t0s[b] for the
+ * same (B, C, Tmax) bit for bit. */
+int tsasr_relpos_attn_stream_slots_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u,
+                                       const float *bias_v, const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax,
+                                       const int32_t *t0s, int causal, float scale, int io_dtype, void *workspace, size_t workspace_bytes,
+                                       void *stream);
 /* tsasr_convmod_fwd with causal = 1 on a chunk y2 [B,C,2D], no saved tensors: the K-1 GLU rows in front of the chunk come from
  * hist_in fp32 [B,K-1,D] (zeros = the offline zero pad), the last K-1 GLU rows of [history | chunk] are written to hist_out (a second
  * buffer: swap the two per chunk). z [B,C,D] (io_dtype). Every row of hist_out is written by every call (rows carried over from
@@ -737,6 +751,12 @@ int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, 
 int tsasr_convmod_stream_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
                              const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
                              float slope, int io_dtype, void *stream);
+/* tsasr_convmod_stream_fwd's arguments plus t0s, the device int32 [B] of tsasr_relpos_attn_stream_slots_fwd (only its sign is read):
+ * t0s[b] >= 0: slot b is active, its z rows and hist_out rows are tsasr_convmod_stream_fwd's bit for bit. t0s[b] < 0: slot b is idle,
+ * hist_out receives hist_in's rows bit for bit and its z rows are zeros. The caller keeps swapping the two buffers per chunk. */
+int tsasr_convmod_stream_slots_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
+                                   const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
+                                   float slope, int io_dtype, const int32_t *t0s, void *stream);
 
 int tsasr_count_nonfinite(const float *x, int n, int *counter, void *stream);
 

@@ -3,6 +3,7 @@
 
     python tools/stream_bench.py [--B 1 32] [--t0 0 1000 3960] [--reps 20] [--json out.json]
     python tools/stream_bench.py --audio                                  # also: the same push fed 1.6 s of waveform (push_audio)
+    python tools/stream_bench.py --slots                                  # slot mode (start(slots=True)) beside the lockstep push
     python tools/stream_bench.py --profile-chunks 20 --B 32 --t0 3960     # under rocprofv3 --kernel-trace --stats: 20 chunks and nothing else timed
 
 A chunk is one push of 160 mel frames = 40 encoder frames = 1.6 s of audio. The time of a push is host wall-clock from the call to
@@ -12,6 +13,9 @@ Kernel launches per chunk are counted with torch.profiler. Real-time factor = ti
 --audio: a second stream of the same model started with audio=True is pushed 25600 samples at a time (in the steady state every such
 push completes exactly one group of 160 causal feature frames: nnet.CausalFeatures, then the same push()); its median is reported beside
 the feature push's, with the median of the feature stage alone (CausalFeatures.forward_chunk on a stream of its own).
+--slots: B = 32 and B = 1, every slot occupied, the slots' offsets spread evenly over 0 .. 3960 (B = 1: at 3960) and put back there
+before every push; the median of 15 pushes, the second half of which each do one release() + admit() inside the timed region. The
+lockstep push at t0 = 1000 and t0 = 3960 is timed in the same run (15 pushes each), with the kernel launches per chunk of all three.
 """
 import argparse
 import importlib
@@ -85,6 +89,43 @@ def time_audio(st, wav, t0, reps):
     return statistics.median(both), statistics.median(alone)
 
 
+def make_slot_stream(streaming, brain, B, max_frames, device):
+    D = brain.modules.encoder.d_model
+    g = torch.Generator(device="cpu").manual_seed(7)
+    spk = (torch.randn(B, 1, D, generator=g) * 0.5).to(device)
+    st = streaming.StreamingTranscriber(brain)
+    st.start(B, max_frames, slots=True)
+    for b in range(B):
+        st.admit(b, speaker_embs=spk[b:b + 1])
+    feats = torch.randn(B, CHUNK_MEL, 80, generator=g).to(device)
+    offs = [3960] if B == 1 else [round(3960 * b / (B - 1) / CHUNK_ENC) * CHUNK_ENC for b in range(B)]
+    return st, feats, spk, offs
+
+
+def place_slots(st, offs):
+    """Move every slot to its encoder frame (the caches keep whatever they hold)."""
+    st.enc_state["t0"] = list(offs)
+    t = torch.tensor(offs, dtype=torch.int32, device=st.mel.device)
+    st.enc_state["t0s"].copy_(t)
+    st.mel.copy_(4 * t.long())
+
+
+def time_slots(st, feats, spk, offs, reps):
+    """ms of `reps` slot pushes at the spread offsets; from the middle on each push also releases and admits one slot."""
+    times, B = [], len(offs)
+    for n in range(reps):
+        place_slots(st, offs)
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        if n >= reps // 2:
+            b = n % B
+            st.release(b)
+            st.admit(b, speaker_embs=spk[b:b + 1])
+        st.push(feats)
+        times.append((time.perf_counter() - s) * 1e3)
+    return times
+
+
 def place(st, t0):
     """Move the stream to encoder frame t0 (the caches keep whatever they hold)."""
     st.enc_state["t0"] = t0
@@ -93,7 +134,7 @@ def place(st, t0):
 
 def count_launches(st, feats, t0):
     from torch.profiler import ProfilerActivity, profile
-    place(st, t0)
+    place_slots(st, t0) if isinstance(t0, list) else place(st, t0)
     with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as p:
         st.push(feats)
         torch.cuda.synchronize()
@@ -115,6 +156,7 @@ def main():
     ap.add_argument("--max-frames", type=int, default=4000)
     ap.add_argument("--no-split", action="store_true", help="attention without the key split (prices the split)")
     ap.add_argument("--audio", action="store_true", help="also time push_audio of 1.6 s of waveform (causal features + the same push)")
+    ap.add_argument("--slots", action="store_true", help="slot mode at spread offsets beside the lockstep push at t0 = 1000 and 3960, 15 pushes each")
     ap.add_argument("--profile-chunks", type=int, default=0)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -125,8 +167,26 @@ def main():
         ops.relpos_attn_stream_workspace = lambda *args, **kw: None
     brain, _ = build(device)
     results = []
+    if a.slots:
+        a.B, a.t0, a.reps = [32, 1], [1000, 3960], 15
     with torch.no_grad():
         for B in a.B:
+            if a.slots:
+                sts, feats_s, spk, offs = make_slot_stream(streaming, brain, B, a.max_frames, device)
+                for _ in range(3):
+                    place_slots(sts, offs)
+                    sts.push(feats_s)
+                times = time_slots(sts, feats_s, spk, offs, a.reps)
+                try:
+                    n, _ = count_launches(sts, feats_s, offs)
+                except Exception as e:
+                    n = f"n/a ({type(e).__name__})"
+                med = statistics.median(times)
+                r = {"B": B, "mode": "slots", "offsets": [offs[0], offs[-1]], "ms_per_chunk_median": round(med, 3), "ms_min": round(min(times), 3),
+                     "ms_max": round(max(times), 3), "kernel_launches_per_chunk": n, "rtf": round(med / AUDIO_MS, 5)}
+                print(json.dumps(r), flush=True)
+                results.append(r)
+                del sts
             st, feats = make_stream(streaming, brain, B, a.max_frames, device)
             for _ in range(0 if a.profile_chunks else 3):     # warm-up: allocations, workspaces, first launches
                 st.push(feats)

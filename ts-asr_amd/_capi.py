@@ -173,6 +173,8 @@ _PROTOS = {
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),
     "tsasr_relpos_attn_stream_fwd": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_float, c_int, c_void_p, c_size_t, c_void_p]),
     "tsasr_convmod_stream_fwd": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_float, c_float, c_int, c_void_p]),
+    "tsasr_relpos_attn_stream_slots_fwd": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "tsasr_convmod_stream_slots_fwd": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_float, c_float, c_int, c_void_p, c_void_p]),
     "tsasr_count_nonfinite": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "tsasr_allreduce_load": (c_int, [ctypes.c_char_p]),
     "tsasr_allreduce_unique_id": (c_int, [c_void_p]),

@@ -165,10 +165,12 @@ class ConformerEncoder(nn.Module):
         return state
 
     # ---- chunk-by-chunk inference of a causal encoder --------------------------------------------------------------------------
-    def init_stream(self, B, max_frames, dtype=None, device=None):
+    def init_stream(self, B, max_frames, dtype=None, device=None, slots=False):
         """Caches for a batch of B streams of up to ``max_frames`` encoder frames: per layer a K/V cache and two conv histories, and
         the half positional table pk_half = linear_pos(PE(d)), d = 0 .. max_frames-1, of every layer (one ops.project_many launch over
-        the non-negative half of RelPosEncXL's symmetric table)."""
+        the non-negative half of RelPosEncXL's symmetric table). ``slots``: the B rows are slots that do not run in lockstep - the
+        state carries a device int32 offset per slot (state["t0s"], what the kernels read; state["launch"] = the array of one chunk,
+        idle slots at -1, always the same buffer) and its host mirror (state["t0"], a list), and forward_chunk takes ``active``."""
         if not self.causal:
             raise ValueError("init_stream: only a causal encoder (causal=True) can run as a stream")
         from .nnet import _pos_cd, compute_dtype
@@ -188,12 +190,20 @@ class ConformerEncoder(nn.Module):
             st = layer.init_stream(B, Tm, dtype, device)
             st["pk"] = pk.contiguous()
             layers.append(st)
-        return {"t0": 0, "max_frames": Tm, "B": int(B), "layers": layers}
+        state = {"t0": 0, "max_frames": Tm, "B": int(B), "layers": layers}
+        if slots:
+            state.update(t0=[0] * int(B), t0s=torch.zeros(int(B), dtype=torch.int32, device=device),
+                         launch=torch.full((int(B),), -1, dtype=torch.int32, device=device))
+        return state
 
-    def forward_chunk(self, src_chunk, state, speaker_embs=None, speaker_embs_length=None, enc_lens=None):
+    def forward_chunk(self, src_chunk, state, speaker_embs=None, speaker_embs_length=None, enc_lens=None, active=None):
         """Encoder output [B,C,D] of the next C front-end frames ``src_chunk`` [B,C,F',C'] of every stream (same speaker injection and
         final norm as forward()). ``enc_lens`` int32 [B]: valid encoder frames of each stream so far (keys at or past it are masked;
-        None = all frames valid). Advances state["t0"] by C. Eval only."""
+        None = all frames valid). Advances state["t0"] by C. Eval only.
+        A state of init_stream(slots=True): ``active`` (bool per slot, a host sequence or a tensor; default all) names the slots this
+        chunk belongs to. Each runs at its own offset and advances by C; an idle slot keeps every bit of its K/V cache, conv history
+        and offset, and its output rows carry no meaning. Before any state moves, ValueError for an active slot whose chunk would pass
+        max_frames (the message names the slot) or whose offset is not a multiple of the attention block."""
         if not self.causal:
             raise ValueError("forward_chunk: only a causal encoder (causal=True) can run as a stream")
         if torch.is_grad_enabled() or self.training:
@@ -202,6 +212,10 @@ class ConformerEncoder(nn.Module):
         if src_chunk.ndim == 4:
             b, t, c1, c2 = src_chunk.shape
             src_chunk = src_chunk.reshape(b, t, c1 * c2)
+        if "t0s" in state:
+            return self._forward_chunk_slots(src_chunk, state, speaker_embs, speaker_embs_length, enc_lens, active)
+        if active is not None:
+            raise ValueError("forward_chunk: `active` needs a state of init_stream(slots=True)")
         t0, Cn = state["t0"], src_chunk.shape[1]
         blk = max(int(getattr(self.layers[0], "chunk_size", 0) or 0), 1)
         if t0 % blk:    # block-causal attention: a frame sees its whole block of `chunk_size` frames, so a chunk cannot end inside one
@@ -217,6 +231,37 @@ class ConformerEncoder(nn.Module):
             if i in self.injection_after and speaker_embs is not None:
                 x = self._inject_speaker_emb(x, speaker_embs, speaker_embs_length)
         state["t0"] = t0 + Cn
+        return self.norm(x)
+
+    def _forward_chunk_slots(self, src_chunk, state, speaker_embs, speaker_embs_length, enc_lens, active):
+        B, Cn = state["B"], src_chunk.shape[1]
+        if active is None:
+            act = [True] * B
+        else:
+            act = [bool(a) for a in (active.tolist() if isinstance(active, torch.Tensor) else active)]
+            if len(act) != B:
+                raise ValueError(f"forward_chunk: active must name {B} slots, got {len(act)}")
+        blk = max(int(getattr(self.layers[0], "chunk_size", 0) or 0), 1)
+        host = state["t0"]
+        for b in range(B):      # from the host mirror, before any state moves
+            if act[b] and host[b] + Cn > state["max_frames"]:
+                raise ValueError(f"slot {b}: stream longer than init_stream's max_frames ({host[b]} + {Cn} > {state['max_frames']})")
+            if act[b] and host[b] % blk:
+                raise ValueError(f"slot {b}: with attention chunks of {blk} frames every chunk but the last must hold a multiple of {blk} "
+                                 f"frames (offset {host[b]})")
+        dev = src_chunk.device
+        act_dev = torch.tensor(act, dtype=torch.bool, device=dev)
+        state["launch"].copy_(torch.where(act_dev, state["t0s"], torch.full_like(state["t0s"], -1)))
+        key_lens = None if enc_lens is None else enc_lens.to(device=dev, dtype=torch.int32)
+        x = self.custom_src_module(_cd(src_chunk))
+        if -1 in self.injection_after and speaker_embs is not None:
+            x = self._inject_speaker_emb(x, speaker_embs, speaker_embs_length)
+        for i, layer in enumerate(self.layers):
+            x = layer.forward_chunk(x, state["layers"][i], state["launch"], key_lens)
+            if i in self.injection_after and speaker_embs is not None:
+                x = self._inject_speaker_emb(x, speaker_embs, speaker_embs_length)
+        state["t0s"] += act_dev.to(torch.int32) * Cn
+        state["t0"] = [t + Cn if a else t for t, a in zip(host, act)]
         return self.norm(x)
 
     def _inject_speaker_emb(self, src, spk, spk_len):

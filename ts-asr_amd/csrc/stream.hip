@@ -17,6 +17,10 @@
 // (2) convmod_stream_kernel: tsasr_convmod_fwd with causal = 1 on a chunk - bias + GLU + depthwise conv (K taps) + LayerNorm + LeakyReLU
 //     - reading the K - 1 GLU rows before the chunk from a history buffer instead of the zero pad, and writing the next chunk's history
 //     to a second buffer (the caller swaps the two per chunk). A zeroed history is the offline causal zero pad.
+// Slots (tsasr_relpos_attn_stream_slots_fwd, tsasr_convmod_stream_slots_fwd): the same kernel bodies with a device array t0s [B] in place
+//     of the scalar t0 (a null t0s selects the scalar), for batches whose rows are sessions that join and leave: row b runs at its own
+//     offset t0s[b] >= 0, or is idle (t0s[b] < 0, or a chunk that would pass Tmax): its workgroups leave at once, its cache and history
+//     keep their bits (hist_out = hist_in), its output rows are exact zeros. The offset is uniform per workgroup and read once.
 #include "common.h"
 
 namespace {
@@ -37,7 +41,16 @@ struct StreamAttnArgs {
     float *part;                 // [B, H, C, nsplit, Dh + 2] when nsplit > 1
     int B, C, H, Dh, Tmax, t0, causal, nsplit, tps;
     float scale;
+    const int *t0s;              // [B] per-slot offsets (tsasr_relpos_attn_stream_slots_fwd) or NULL: every row at t0
 };
+
+// the offset of batch row b, read once per workgroup (uniform); slot launches: < 0 = an idle slot, and a slot whose chunk would pass
+// the cache is treated as idle, so no row past Tmax can be written
+__device__ __forceinline__ int s_offset(const StreamAttnArgs &a, int b) {
+    if (!a.t0s) return a.t0;
+    const int t = a.t0s[b];
+    return (t < 0 || (long long)t + a.C > a.Tmax) ? -1 : t;
+}
 
 __device__ __forceinline__ int s_causal_limit(int i, int causal) { return causal <= 1 ? i : (i / causal + 1) * causal - 1; }
 
@@ -46,8 +59,16 @@ __global__ __launch_bounds__(256) void attn_stream_kernel(const StreamAttnArgs a
     __shared__ float Ks[SKT][SLDD], Vs[SKT][SLDD], Ps[SPB][SLDD], Qu[SQB][SLDD], Qv[SQB][SLDD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = blockIdx.x * SQB, h = blockIdx.y, b = blockIdx.z / a.nsplit, sp = blockIdx.z % a.nsplit;
-    const int Dh = a.Dh, C = a.C, t0 = a.t0, D = a.H * Dh;
+    const int Dh = a.Dh, C = a.C, t0 = s_offset(a, b), D = a.H * Dh;
     const long long ld = 3LL * D;
+    if (t0 < 0) {                                   // idle slot: cache untouched, out rows exact zeros (split: the merge writes them)
+        if (a.nsplit == 1)
+            for (int e = threadIdx.x; e < SQB * Dh; e += 256) {
+                const int ic = i0 + e / Dh;
+                if (ic < C) st1((T *)a.out + ((long long)b * C + ic) * D + h * Dh + e % Dh, 0.f);
+            }
+        return;
+    }
     const T *qkv = (const T *)a.qkv + (long long)b * C * ld + (long long)h * 3 * Dh;
     T *kc = (T *)a.kc + ((long long)b * a.H + h) * a.Tmax * Dh;
     T *vc = (T *)a.vc + ((long long)b * a.H + h) * a.Tmax * Dh;
@@ -136,6 +157,10 @@ template <typename T>
 __global__ __launch_bounds__(64) void attn_stream_merge_kernel(const StreamAttnArgs a) {
     const int lane = threadIdx.x, i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, Dh = a.Dh;
     const float *pp = a.part + (((long long)b * a.H + h) * a.C + i) * a.nsplit * (Dh + 2);
+    if (s_offset(a, b) < 0) {                       // idle slot: no partials were written for it
+        if (lane < Dh) st1((T *)a.out + ((long long)b * a.C + i) * a.H * Dh + h * Dh + lane, 0.f);
+        return;
+    }
     float M = -INFINITY;
     for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, pp[s * (Dh + 2) + Dh]);
     float L = 0.f, O = 0.f;
@@ -178,8 +203,16 @@ __global__ __launch_bounds__(256) void attn_stream_mfma_kernel(const StreamAttnA
     __shared__ __attribute__((aligned(16))) bf16_t Vs[4][32][VLD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5, qb = wave & 1, kp = wave >> 1;
     const int i0 = blockIdx.x * MQB, h = blockIdx.y, b = blockIdx.z / a.nsplit, sp = blockIdx.z % a.nsplit;
-    const int C = a.C, t0 = a.t0, D = a.H * DH;
+    const int C = a.C, t0 = s_offset(a, b), D = a.H * DH;
     const long long ld = 3LL * D;
+    if (t0 < 0) {                                     // idle slot (as attn_stream_kernel)
+        if (a.nsplit == 1)
+            for (int e = threadIdx.x; e < MQB * DH; e += 256) {
+                const int ic = i0 + e / DH;
+                if (ic < C) st1((bf16_t *)a.out + ((long long)b * C + ic) * D + h * DH + e % DH, 0.f);
+            }
+        return;
+    }
     const bf16_t *qkv = (const bf16_t *)a.qkv + (long long)b * C * ld + (long long)h * 3 * DH;
     bf16_t *kc = (bf16_t *)a.kc + ((long long)b * a.H + h) * a.Tmax * DH;
     bf16_t *vc = (bf16_t *)a.vc + ((long long)b * a.H + h) * a.Tmax * DH;
@@ -335,6 +368,7 @@ struct ConvStreamArgs {
     void *z;                     // [B, C, D]
     int B, C, D, K;
     float eps, slope;
+    const int *t0s;              // [B] slot offsets (tsasr_convmod_stream_slots_fwd; < 0 = idle slot) or NULL
 };
 
 __device__ __forceinline__ float sig_f(float x) { return 1.f / (1.f + __expf(-x)); }
@@ -359,6 +393,13 @@ __global__ __launch_bounds__(256) void convmod_stream_kernel(const ConvStreamArg
     const T *y2 = (const T *)a.y2 + (long long)b * a.C * 2 * D;
     const float *hin = a.hin + (long long)b * hk * D;
     float *hout = a.hout + (long long)b * hk * D;
+    if (a.t0s && a.t0s[b] < 0) {                      // idle slot: zero rows, the history carried over bit for bit
+        T *zr = (T *)a.z + ((long long)b * a.C + r) * D;
+        for (int d = tid; d < D; d += 256) st1(zr + d, 0.f);
+        for (int mrow = r; mrow < hk; mrow += a.C)
+            for (int d = tid; d < D; d += 256) hout[(long long)mrow * D + d] = hin[(long long)mrow * D + d];
+        return;
+    }
     float s1 = 0.f;
     for (int d = tid; d < D; d += 256) {
         float acc = a.cb ? a.cb[d] : 0.f;
@@ -398,19 +439,20 @@ size_t tsasr_relpos_attn_stream_workspace_bytes(int B, int C, int H, int Dh, int
     return ns > 1 ? (size_t)B * H * C * ns * (Dh + 2) * sizeof(float) : 0;
 }
 
-int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u, const float *bias_v,
-                                 const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax, int t0, int causal, float scale,
-                                 int io_dtype, void *workspace, size_t workspace_bytes, void *stream) {
-    TSASR_CHECK_ARG(qkv && k_cache && v_cache && pk_half && bias_u && bias_v && out, "tsasr_relpos_attn_stream_fwd: null pointer");
+// one launcher for both entry points: t0s == NULL runs every row at the scalar t0
+static int attn_stream_launch(const char *name, const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u,
+                              const float *bias_v, const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax, int t0,
+                              const int32_t *t0s, int causal, float scale, int io_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+    TSASR_CHECK_ARG(qkv && k_cache && v_cache && pk_half && bias_u && bias_v && out, "%s: null pointer", name);
     TSASR_CHECK_ARG(B > 0 && C > 0 && H > 0 && Dh > 0 && Dh <= SDMAX && t0 >= 0 && causal >= 0 && (long long)t0 + C <= Tmax,
-                    "tsasr_relpos_attn_stream_fwd: bad shape (B=%d C=%d H=%d Dh=%d Tmax=%d t0=%d causal=%d)", B, C, H, Dh, Tmax, t0, causal);
-    TSASR_CHECK_ARG(io_dtype == TSASR_F32 || io_dtype == TSASR_BF16, "tsasr_relpos_attn_stream_fwd: bad dtype");
+                    "%s: bad shape (B=%d C=%d H=%d Dh=%d Tmax=%d t0=%d causal=%d)", name, B, C, H, Dh, Tmax, t0, causal);
+    TSASR_CHECK_ARG(io_dtype == TSASR_F32 || io_dtype == TSASR_BF16, "%s: bad dtype", name);
     int ns, tps;
     stream_split(B, C, H, Tmax, &ns, &tps);
     const size_t need = tsasr_relpos_attn_stream_workspace_bytes(B, C, H, Dh, Tmax);
     if (!workspace || workspace_bytes < need) { ns = 1; tps = cdiv(Tmax, SKT); }   // no workspace: one pass over the keys
     StreamAttnArgs a{qkv, k_cache, v_cache, pk_half, bias_u, bias_v, key_lens, out, (float *)workspace, B, C, H, Dh, Tmax, t0, causal, ns, tps,
-                     scale};
+                     scale, t0s};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(cdiv(C, SQB), H, B * ns), mgrid(C, H, B), qgrid(cdiv(C, MQB), H, B * ns);
     if (io_dtype == TSASR_F32) {                     // exact fp32 arithmetic: the parity mode
@@ -422,23 +464,54 @@ int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, 
         else attn_stream_kernel<bf16_t><<<grid, 256, 0, st>>>(a);    // other head sizes: fp32 arithmetic on bf16 storage
         if (ns > 1) attn_stream_merge_kernel<bf16_t><<<mgrid, 64, 0, st>>>(a);
     }
-    TSASR_CHECK_LAUNCH("tsasr_relpos_attn_stream_fwd");
+    TSASR_CHECK_LAUNCH(name);
+    return 0;
+}
+
+int tsasr_relpos_attn_stream_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u, const float *bias_v,
+                                 const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax, int t0, int causal, float scale,
+                                 int io_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+    return attn_stream_launch("tsasr_relpos_attn_stream_fwd", qkv, k_cache, v_cache, pk_half, bias_u, bias_v, key_lens, out, B, C, H, Dh, Tmax, t0,
+                              nullptr, causal, scale, io_dtype, workspace, workspace_bytes, stream);
+}
+
+int tsasr_relpos_attn_stream_slots_fwd(const void *qkv, void *k_cache, void *v_cache, const void *pk_half, const float *bias_u,
+                                       const float *bias_v, const int32_t *key_lens, void *out, int B, int C, int H, int Dh, int Tmax,
+                                       const int32_t *t0s, int causal, float scale, int io_dtype, void *workspace, size_t workspace_bytes,
+                                       void *stream) {
+    TSASR_CHECK_ARG(t0s, "tsasr_relpos_attn_stream_slots_fwd: null t0s");
+    return attn_stream_launch("tsasr_relpos_attn_stream_slots_fwd", qkv, k_cache, v_cache, pk_half, bias_u, bias_v, key_lens, out, B, C, H, Dh,
+                              Tmax, 0, t0s, causal, scale, io_dtype, workspace, workspace_bytes, stream);
+}
+
+static int convmod_stream_launch(const char *name, const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
+                                 const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
+                                 float slope, const int32_t *t0s, int io_dtype, void *stream) {
+    TSASR_CHECK_ARG(y2 && conv_w && gamma && beta && hist_in && hist_out && z && hist_in != hist_out, "%s: null or aliased pointer", name);
+    TSASR_CHECK_ARG(B > 0 && C > 0 && D > 0 && D <= 8192 && K >= 2 && K <= 64, "%s: bad shape (B=%d C=%d D=%d K=%d)", name, B, C, D, K);
+    TSASR_CHECK_ARG(io_dtype == TSASR_F32 || io_dtype == TSASR_BF16, "%s: bad dtype", name);
+    ConvStreamArgs a{y2, b2, conv_w, conv_b, gamma, beta, hist_in, hist_out, z, B, C, D, K, eps, slope, t0s};
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)D * sizeof(float);
+    if (io_dtype == TSASR_F32) convmod_stream_kernel<float><<<dim3(C, B), 256, lds, st>>>(a);
+    else convmod_stream_kernel<bf16_t><<<dim3(C, B), 256, lds, st>>>(a);
+    TSASR_CHECK_LAUNCH(name);
     return 0;
 }
 
 int tsasr_convmod_stream_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma, const float *beta,
                              const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps, float slope, int io_dtype,
                              void *stream) {
-    TSASR_CHECK_ARG(y2 && conv_w && gamma && beta && hist_in && hist_out && z && hist_in != hist_out, "tsasr_convmod_stream_fwd: null or aliased pointer");
-    TSASR_CHECK_ARG(B > 0 && C > 0 && D > 0 && D <= 8192 && K >= 2 && K <= 64, "tsasr_convmod_stream_fwd: bad shape (B=%d C=%d D=%d K=%d)", B, C, D, K);
-    TSASR_CHECK_ARG(io_dtype == TSASR_F32 || io_dtype == TSASR_BF16, "tsasr_convmod_stream_fwd: bad dtype");
-    ConvStreamArgs a{y2, b2, conv_w, conv_b, gamma, beta, hist_in, hist_out, z, B, C, D, K, eps, slope};
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)D * sizeof(float);
-    if (io_dtype == TSASR_F32) convmod_stream_kernel<float><<<dim3(C, B), 256, lds, st>>>(a);
-    else convmod_stream_kernel<bf16_t><<<dim3(C, B), 256, lds, st>>>(a);
-    TSASR_CHECK_LAUNCH("tsasr_convmod_stream_fwd");
-    return 0;
+    return convmod_stream_launch("tsasr_convmod_stream_fwd", y2, b2, conv_w, conv_b, gamma, beta, hist_in, hist_out, z, B, C, D, K, eps, slope,
+                                 nullptr, io_dtype, stream);
+}
+
+int tsasr_convmod_stream_slots_fwd(const void *y2, const float *b2, const float *conv_w, const float *conv_b, const float *gamma,
+                                   const float *beta, const float *hist_in, float *hist_out, void *z, int B, int C, int D, int K, float eps,
+                                   float slope, int io_dtype, const int32_t *t0s, void *stream) {
+    TSASR_CHECK_ARG(t0s, "tsasr_convmod_stream_slots_fwd: null t0s");
+    return convmod_stream_launch("tsasr_convmod_stream_slots_fwd", y2, b2, conv_w, conv_b, gamma, beta, hist_in, hist_out, z, B, C, D, K, eps,
+                                 slope, t0s, io_dtype, stream);
 }
 
 }  // extern "C"

@@ -404,7 +404,51 @@ class TransducerBeamSearcher(torch.nn.Module):
         out = best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
         return out + ([n[0] for n in nbest_frames], nbest_frames) if timed else out
 
-    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None, return_frames=False):
+    @torch.no_grad()
+    def reset_streams(self, state, slots):
+        """Put the streams ``slots`` (indices into the batch) of a greedy_stream / beam_stream state back to the start of a stream, in
+        place; every other stream keeps its bits. Device greedy: the slot's row of the [B, 2H+J+4] state and its frames_done are zeroed.
+        Device beam: the slot's block of the workspace (B equal blocks, untimed, timed, LM and wide layouts alike) is zeroed, which
+        also clears a sticky status. Host routes: the slot's predictor state / beam list starts afresh. ``state`` None (no call made
+        yet: every stream is at its start) is returned as it is."""
+        if state is None:
+            return state
+        slots = [int(b) for b in slots]
+        if "beams" in state:                                   # beam search, host route
+            timed = "frames_done" in state
+            for b in slots:
+                state["beams"][b] = [self._beam_start(timed)]
+                if timed:
+                    state["frames_done"][b] = 0
+        elif "tok" in state:                                   # greedy search, host route
+            idx = torch.as_tensor(slots, dtype=torch.long, device=state["tok"].device)
+            tok = torch.full((len(slots), 1), self.blank_id, dtype=torch.long, device=idx.device)
+            out_pn, hidden = self._pn(tok, None)
+            state["tok"][idx] = tok
+            state["out_pn"][idx] = out_pn.to(state["out_pn"].dtype)
+            for old, new in zip(state["hidden"], hidden):
+                old[:, idx] = new.to(old.dtype)
+            state["logp_sum"][idx] = 0
+        elif "max_frames" in state:                            # beam search, device route: B equal blocks of the workspace
+            per_utt = state["dev"].numel() // state["B"]
+            for b in slots:
+                state["dev"][b * per_utt:(b + 1) * per_utt].zero_()
+        else:                                                  # greedy search, device route
+            state["dev"][torch.as_tensor(slots, dtype=torch.long, device=state["dev"].device)] = 0
+            if "logp_sum" in state:
+                state["logp_sum"] = state["logp_sum"].clone()
+                state["logp_sum"][slots] = 0
+        if isinstance(state.get("frames_done"), torch.Tensor):
+            state["frames_done"] = state["frames_done"].clone()
+            state["frames_done"][slots] = 0
+        for b in slots:                                        # the n-best lists of the last call describe the stream that left
+            if "nbest" in state:
+                state["nbest"][b], state["scores"][b] = [[]], [0.0]
+            if "frames" in state:
+                state["frames"][b] = [[]]
+        return state
+
+    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None, return_frames=False, raise_stopped=True):
         """Beam search over the next frames of a batch of streams, the counterpart of greedy_stream: enc_chunk [B,C,J], ``state`` the
         value returned by the previous call (None: start of the streams), n_valid int32 [B] = frames of this chunk that belong to each
         stream (None: all C); max_frames = frames a stream may reach (device route; default BEAM_STREAM_FRAMES), read at the first call.
@@ -414,7 +458,9 @@ class TransducerBeamSearcher(torch.nn.Module):
         route carries the beam lists. A stream past ``cap`` hypotheses in a frame cannot be re-decoded chunk by chunk: RuntimeError.
         return_frames=True: the state also carries state["frames"], the n-best lists of emission frames (absolute in the stream) that
         match state["nbest"]. The flag is fixed at the first call of a stream (the timed device workspace has its own layout, the
-        host hypotheses carry their frames): a later call with the other value raises ValueError."""
+        host hypotheses carry their frames): a later call with the other value raises ValueError.
+        raise_stopped=False (device route): stopped streams do not raise; the state is stored for every stream and state["stopped"]
+        lists them (a stopped stream stays stopped until reset_streams)."""
         if torch.is_grad_enabled():
             raise RuntimeError("beam_stream is inference only: run it under torch.no_grad()")
         B, T, _ = enc_chunk.shape
@@ -439,7 +485,7 @@ class TransducerBeamSearcher(torch.nn.Module):
                     else:
                         nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, hid, enc.shape[-1], self.beam_size, self.cap, lm_rnn.num_layers,
                                                                     lm_rnn.hidden_size, timed)
-                state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf}
+                state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf, "B": B}
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")
             if timed:
@@ -448,10 +494,16 @@ class TransducerBeamSearcher(torch.nn.Module):
             else:
                 nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"])
             bad = [b for b in range(B) if int(status[b]) != 0]
-            if bad:
+            state["stopped"] = {b: ops.BEAM_STATUS[int(status[b])] for b in bad}
+            if bad and raise_stopped:
                 raise RuntimeError(f"beam_stream: stream(s) {bad} stopped ({sorted({ops.BEAM_STATUS[int(status[b])] for b in bad})}) with "
                                    f"cap={self.cap} hypotheses per frame and max_frames={state['max_frames']}; restart the stream with a "
                                    f"larger cap (TransducerBeamSearcher(cap=...)) or max_frames")
+            for b in range(B):       # a stream that has not decoded a frame yet (a zeroed state and no valid frame) has no beam to list
+                if not nbest_batch[b]:
+                    nbest_batch[b], nbest_scores[b] = [[]], [0.0]
+                    if timed:
+                        nbest_frames[b] = [[]]
             state["nbest"], state["scores"] = nbest_batch, nbest_scores
             if timed:
                 state["frames"] = nbest_frames

@@ -798,10 +798,12 @@ class ConformerEncoderLayer(nn.Module):
         hist = torch.zeros(2, B, K - 1, D, dtype=torch.float32, device=device)
         return {"k": kv[0], "v": kv[1], "hist": [hist[0], hist[1]], "pk": None, "ws": {}}
 
-    def forward_chunk(self, x, layer_state, t0, key_lens):
+    def forward_chunk(self, x, layer_state, t0, key_lens, active=None):
         """One chunk [B,C,D] of this (causal) layer at absolute frame offset ``t0``; ``key_lens`` int32 [B] = valid frames of each
         stream so far (None: all). The FFNs, norms and projections are the offline ops; the attention reads and extends the layer's
-        K/V cache (ops.relpos_attention_stream), the convolution core carries its K-1 GLU rows (ops.convmod_stream). Eval only."""
+        K/V cache (ops.relpos_attention_stream), the convolution core carries its K-1 GLU rows (ops.convmod_stream). Eval only.
+        Slots: ``t0`` an int32 device tensor [B] of per-row offsets (a negative entry = an idle row) and / or ``active`` bool [B]
+        (default all): an idle row's K/V cache and conv history keep their bits, its attention and convolution outputs are zeros."""
         if not self.causal:
             raise ValueError("forward_chunk needs a causal layer")
         if torch.is_grad_enabled() or self.training:
@@ -810,6 +812,12 @@ class ConformerEncoderLayer(nn.Module):
         ln1, pff1 = self.ffn_module1[0], self.ffn_module1[1].ffn
         ln2, pff2 = self.ffn_module2[0], self.ffn_module2[1].ffn
         x = _cd(x)
+        t0s = None
+        if isinstance(t0, torch.Tensor) or active is not None:      # slot mode: one device array of offsets, idle rows negative
+            t0s = t0 if isinstance(t0, torch.Tensor) else torch.full((x.shape[0],), int(t0), dtype=torch.int32, device=x.device)
+            if active is not None:
+                t0s = torch.where(torch.as_tensor(active, device=x.device).bool(), t0s, torch.full_like(t0s, -1))
+            t0 = t0s = t0s.contiguous()
         y = ops.layer_norm(x, ln1.weight, ln1.bias, 1e-5)
         h = ops.ffn_core(y, pff1[0].weight, pff1[0].bias, pff1[3].weight, self.slope, 0.0, False)
         x, y = ops.add_layer_norm(h, pff1[3].bias, x, self.norm1.norm, 0.5)                          # x + .5*ffn1 ; norm1
@@ -824,7 +832,7 @@ class ConformerEncoderLayer(nn.Module):
         y2 = ops.matmul_nt(y, conv.bottleneck[0].weight)
         hin, hout = layer_state["hist"]
         c = ops.convmod_stream(y2, conv.bottleneck[0].bias, conv.conv.weight, conv.conv.bias, conv.after_conv[0].weight, conv.after_conv[0].bias,
-                               hin, hout, 1e-5, conv.slope)
+                               hin, hout, 1e-5, conv.slope, t0s)
         layer_state["hist"] = [hout, hin]
         x, y = ops.linear_add_layer_norm(c, conv.after_conv[2].weight, conv.after_conv[2].bias, x, ln2)              # + conv ; ffn2 LN
         h = ops.ffn_core(y, pff2[0].weight, pff2[0].bias, pff2[3].weight, self.slope, 0.0, False)

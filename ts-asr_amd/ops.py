@@ -38,7 +38,8 @@ STATUS = {
     "lstm(num_layers > 1, bidirectional, H not a multiple of 16 / > 1024)": "LIB (nn.LSTM -> MIOpen), logged",
     "cross_attention injection with head dim > 64": "LIB (ATen matmul / softmax), logged",
     "relpos_attention(need_weights=True: attention maps for plots)": "LIB (ATen matmul / softmax), logged",
-    "streaming (causal encoder, chunk by chunk)": "HIP (stream.hip: relpos_attention_stream on a K/V cache, convmod_stream with carried history; "
+    "streaming (causal encoder, chunk by chunk)": "HIP (stream.hip: relpos_attention_stream on a K/V cache, convmod_stream with carried history, "
+                                                  "both also per slot with a device array of offsets for sessions that join and leave a batch; "
                                                   "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
     "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search / beam_search_stream, one launch per batch or chunk; "
                                                          "the host loop only for other predictor shapes and utterances past cap)",
@@ -2257,7 +2258,9 @@ def relpos_attn_stream_workspace(B, Cn, H, Dh, Tmax, device):
 def relpos_attention_stream(qkv, k_cache, v_cache, pk_half, pos_bias_u, pos_bias_v, key_lens, H, scale, causal, t0, workspace=None):
     """Context [B,C,D] of a chunk of C query frames at absolute offset ``t0`` (RelPosMHAXL's core): qkv [B,C,H*3*Dh] per-head Q|K|V,
     k_cache / v_cache [B,H,Tmax,Dh] (the chunk's K, V are appended at t0 by the same launch), pk_half [Tmax,D] = linear_pos(PE(|i-j|)),
-    key_lens int32 [B] absolute valid frames or None, causal 1 (look-ahead) or c > 1 (block-causal chunks of c frames)."""
+    key_lens int32 [B] absolute valid frames or None, causal 1 (look-ahead) or c > 1 (block-causal chunks of c frames).
+    ``t0`` an int32 device tensor [B] = slots that do not run in lockstep (tsasr_relpos_attn_stream_slots_fwd): row b at its own offset
+    t0[b] >= 0, or idle (t0[b] < 0: its cache is neither read nor written, its rows of the result are zeros)."""
     _no_grad_only("relpos_attention_stream")
     C.require_gpu(qkv, k_cache, v_cache, pk_half)
     qkvc = qkv.contiguous()
@@ -2269,12 +2272,25 @@ def relpos_attention_stream(qkv, k_cache, v_cache, pk_half, pos_bias_u, pos_bias
         raise ValueError("qkv, the K/V cache and pk_half must share one dtype")
     if tuple(k_cache.shape) != (B, H, Tmax, Dh) or tuple(v_cache.shape) != (B, H, Tmax, Dh) or pk_half.shape[0] < Tmax or pk_half.shape[1] != D:
         raise ValueError(f"cache / table shapes {tuple(k_cache.shape)} {tuple(pk_half.shape)} do not fit qkv {tuple(qkvc.shape)}")
-    if t0 + Cn > Tmax:
+    slots = isinstance(t0, torch.Tensor)
+    if slots:       # per-slot offsets on the device; the caller checks their values from its host mirror (the kernel idles a slot past Tmax)
+        C.require_gpu(t0)
+        if tuple(t0.shape) != (B,) or t0.dtype != torch.int32 or not t0.is_contiguous():
+            raise ValueError(f"relpos_attention_stream: per-slot offsets must be a contiguous int32 [B={B}] tensor")
+    elif t0 + Cn > Tmax:
         raise ValueError(f"stream longer than its cache: t0 {t0} + chunk {Cn} > {Tmax} frames")
     u = _f32(pos_bias_u).reshape(-1).contiguous()      # (Dh,H) storage read as [H,Dh]
     v = _f32(pos_bias_v).reshape(-1).contiguous()
     kl = None if key_lens is None else key_lens.to(torch.int32).contiguous()
     out = torch.empty(B, Cn, D, dtype=qkvc.dtype, device=qkvc.device)
+    if slots:
+        with prof.region("relpos_attn_stream_slots_fwd"):
+            C.check(C.lib().tsasr_relpos_attn_stream_slots_fwd(C.ptr(qkvc), C.ptr(k_cache), C.ptr(v_cache), C.ptr(pk_half.contiguous()), C.ptr(u),
+                                                               C.ptr(v), C.ptr(kl), C.ptr(out), B, Cn, H, Dh, Tmax, C.ptr(t0), int(causal),
+                                                               float(scale), C.io_dtype(qkvc), C.ptr(workspace),
+                                                               0 if workspace is None else workspace.numel(), C.stream_ptr()),
+                    "tsasr_relpos_attn_stream_slots_fwd")
+        return out
     with prof.region("relpos_attn_stream_fwd"):
         C.check(C.lib().tsasr_relpos_attn_stream_fwd(C.ptr(qkvc), C.ptr(k_cache), C.ptr(v_cache), C.ptr(pk_half.contiguous()), C.ptr(u), C.ptr(v),
                                                      C.ptr(kl), C.ptr(out), B, Cn, H, Dh, Tmax, int(t0), int(causal), float(scale),
@@ -2283,9 +2299,10 @@ def relpos_attention_stream(qkv, k_cache, v_cache, pk_half, pos_bias_u, pos_bias
     return out
 
 
-def convmod_stream(y2, b2, conv_w, conv_b, ln_w, ln_b, hist_in, hist_out, eps, slope):
+def convmod_stream(y2, b2, conv_w, conv_b, ln_w, ln_b, hist_in, hist_out, eps, slope, t0s=None):
     """convmod_core(causal=True) on a chunk y2 [B,C,2D] whose K-1 preceding GLU rows are hist_in fp32 [B,K-1,D]; writes the next
-    chunk's history to hist_out (another buffer). Returns z [B,C,D]."""
+    chunk's history to hist_out (another buffer). Returns z [B,C,D]. ``t0s`` int32 device tensor [B] (relpos_attention_stream's slot
+    offsets): a row with t0s[b] < 0 is idle - its history is copied to hist_out bit for bit and its z rows are zeros."""
     _no_grad_only("convmod_stream")
     C.require_gpu(y2, hist_in, hist_out)
     y2c = y2.contiguous()
@@ -2297,6 +2314,15 @@ def convmod_stream(y2, b2, conv_w, conv_b, ln_w, ln_b, hist_in, hist_out, eps, s
     f = lambda t: None if t is None else _f32(t).contiguous()  # noqa: E731
     b2f, cw, cb, g, be = f(b2), f(conv_w).reshape(D, K), f(conv_b), f(ln_w), f(ln_b)
     z = torch.empty(B, Cn, D, dtype=y2c.dtype, device=y2c.device)
+    if t0s is not None:
+        C.require_gpu(t0s)
+        if tuple(t0s.shape) != (B,) or t0s.dtype != torch.int32 or not t0s.is_contiguous():
+            raise ValueError(f"convmod_stream: t0s must be a contiguous int32 [B={B}] tensor")
+        with prof.region("convmod_stream_slots_fwd"):
+            C.check(C.lib().tsasr_convmod_stream_slots_fwd(C.ptr(y2c), C.ptr(b2f), C.ptr(cw), C.ptr(cb), C.ptr(g), C.ptr(be), C.ptr(hist_in),
+                                                           C.ptr(hist_out), C.ptr(z), B, Cn, D, K, float(eps), float(slope), C.io_dtype(y2c),
+                                                           C.ptr(t0s), C.stream_ptr()), "tsasr_convmod_stream_slots_fwd")
+        return z
     with prof.region("convmod_stream_fwd"):
         C.check(C.lib().tsasr_convmod_stream_fwd(C.ptr(y2c), C.ptr(b2f), C.ptr(cw), C.ptr(cb), C.ptr(g), C.ptr(be), C.ptr(hist_in),
                                                  C.ptr(hist_out), C.ptr(z), B, Cn, D, K, float(eps), float(slope), C.io_dtype(y2c),

@@ -39,6 +39,20 @@ whole block, so a push cannot end inside one).
 Streams of different lengths share a batch: each one stops at its own valid count, ``ceil(ceil(L/2)/2)`` encoder frames for L valid
 mel frames pushed so far (``mel_lens`` per push, default the whole push); ``enc_lens`` overrides that count (absolute encoder frames).
 Inference only: eval mode, under torch.no_grad().
+
+Slots (start(..., slots=True)): the B rows of the batch are slots that sessions enter and leave while the batch runs.
+
+    st.start(batch_size=B, max_frames=4000, slots=True, max_speaker_frames=S)      # every slot begins free
+    st.admit(2, speaker_embs=emb)               # or enroll=(signal, length): one utterance through the recipe's speaker branch
+    new = st.push(feats)                        # feats [B, F, 80]; the occupied slots advance, the others keep every bit of state
+    new = st.push(feats, active=[True, False, True])      # an occupied slot left out is paused
+    hyp = st.release(2)                         # the session's hypothesis; the slot is free again
+
+Every slot has its own offset (a device int32 array the kernels read, tsasr_relpos_attn_stream_slots_fwd, and a host mirror), mel
+count, front-end carry, conv histories and search state; admit() resets them for that slot alone. The K/V cache rows are not cleared:
+rows at or past a slot's offset are never read. mel_lens / enc_lens, the emission frames, encoder_out(slot) and encoder_frames(slot) are
+absolute in the slot's own session. A session is still bounded by max_frames. The audio route is lockstep only: CausalFeatures' stream
+state counts samples for the whole batch, so a server runs one CausalFeatures stream per session (B = 1) and pushes its features.
 """
 import types
 
@@ -47,6 +61,18 @@ import torch
 from . import _capi as C
 
 __all__ = ["StreamingTranscriber"]
+
+
+class _SlotFrames(int):
+    """encoder_frames in slot mode: the largest offset as an int, and called with a slot that slot's frames."""
+
+    def __new__(cls, offsets):
+        obj = super().__new__(cls, max(offsets) if offsets else 0)
+        obj.offsets = tuple(offsets)
+        return obj
+
+    def __call__(self, slot):
+        return self.offsets[slot]
 
 
 def _enc_frames(mel):
@@ -81,15 +107,22 @@ class StreamingTranscriber:
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False,
-              audio=False, feature_prior=None):
+              audio=False, feature_prior=None, slots=False, max_speaker_frames=1):
         """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
         ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
         ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
         every chunk's encoder output (before encoder_proj) for encoder_out(). timestamps: keep the emission frame of every token
         (frames(), nbest_frames()). audio: the stream is fed waveforms (push_audio) - causal features over the recipe's Fbank tables,
-        ``feature_prior`` = (mean [n_mels], std [n_mels], n0) optionally starting their running statistics (nnet.CausalFeatures)."""
+        ``feature_prior`` = (mean [n_mels], std [n_mels], n0) optionally starting their running statistics (nnet.CausalFeatures).
+        slots: the B rows are slots, all free to begin with, that sessions enter with admit() and leave with release() (module
+        docstring); the speaker embedding then comes per session with admit(), padded to ``max_speaker_frames`` rows."""
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        if slots and (enroll is not None or speaker_embs is not None):
+            raise ValueError("start(slots=True): the speaker embedding comes per session, with admit(slot, enroll=... / speaker_embs=...)")
+        if slots and audio:
+            raise ValueError("start(slots=True, audio=True): the audio route runs in lockstep only; run one CausalFeatures stream per "
+                             "session and push its features")
         if hasattr(self.brain, "_setup_dtype"):      # the brain's compute dtype (as fit / evaluate set it)
             self.brain._setup_dtype()
         for mod in (self.frontend, self.encoder, self.encoder_proj, self.searcher):
@@ -133,8 +166,139 @@ class StreamingTranscriber:
             self.features = CausalFeatures(fbank, prior=feature_prior).to(fbank.window.device)
         elif feature_prior is not None:
             raise ValueError("feature_prior goes with audio=True")
+        self.slots = bool(slots)
+        if self.slots:
+            self.max_speaker_frames = int(max_speaker_frames)
+            self.occupied = [False] * self.B
+            self.slot_chunks = [[] for _ in range(self.B)]
+            dev = self.encoder.norm.norm.weight.device
+            self.enc_state = self.encoder.init_stream(self.B, self.max_frames, device=dev, slots=True)
+            self.mel = torch.zeros(self.B, dtype=torch.int64, device=dev)
         self._started = True
         return self
+
+    # ---- slots ---------------------------------------------------------------------------------------------------------------------
+    def _need_slots(self, what, slot=None):
+        if not self._started or not getattr(self, "slots", False):
+            raise RuntimeError(f"{what} needs start(..., slots=True)")
+        if slot is not None and not 0 <= int(slot) < self.B:
+            raise ValueError(f"{what}: slot {slot} is not one of the {self.B} slots")
+
+    def admit(self, slot, enroll=None, speaker_embs=None, speaker_embs_length=None):
+        """A new session enters the free ``slot``. Its speaker embedding: ``enroll`` = (one enrollment signal [1, N], its relative
+        length [1]) through the recipe's speaker branch, or ``speaker_embs`` [1, S, D] (+ ``speaker_embs_length`` [1] relative, for
+        cross-attention), S <= max_speaker_frames; neither = no injection. Reset for this slot only: offset and mel count, the
+        front-end carries, both conv histories of every layer, the search state, the hypothesis, its frames and the kept encoder
+        output. The K/V cache keeps its bytes: rows at or past a slot's offset are never read."""
+        self._need_slots("admit()", slot)
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        slot = int(slot)
+        if self.occupied[slot]:
+            raise ValueError(f"admit(): slot {slot} is occupied; release() it first")
+        if enroll is not None and speaker_embs is not None:
+            raise ValueError("admit(): give enroll or speaker_embs, not both")
+        if enroll is not None:
+            sig, lens = enroll
+            batch = types.SimpleNamespace(enroll_sig=(sig, lens))
+            mods = self.brain.modules
+            for name in ("speaker_frontend", "speaker_encoder", "speaker_proj"):
+                if (name in mods) if isinstance(mods, dict) else hasattr(mods, name):
+                    (mods[name] if isinstance(mods, dict) else getattr(mods, name)).eval()
+            speaker_embs, speaker_embs_length = self.brain._speaker_embedding(batch, 0)
+        if speaker_embs is not None:
+            S, Sm = speaker_embs.shape[-2], self.max_speaker_frames
+            if speaker_embs.ndim != 3 or speaker_embs.shape[0] != 1 or S > Sm:
+                raise ValueError(f"admit(): one session's embedding is [1, S <= {Sm}, D], got {tuple(speaker_embs.shape)}")
+            dev = self.mel.device
+            if self.spk is None:
+                self.spk = torch.zeros(self.B, Sm, speaker_embs.shape[-1], dtype=speaker_embs.dtype, device=dev)
+                self.spk_len = torch.ones(self.B, dtype=torch.float32, device=dev)
+            n = S if speaker_embs_length is None else int(torch.round(torch.as_tensor(speaker_embs_length).float().reshape(-1)[0] * S))
+            self.spk[slot] = 0
+            self.spk[slot, :S] = speaker_embs[0].to(device=dev, dtype=self.spk.dtype)
+            self.spk_len[slot] = min(max(n, 1), S) / Sm
+        elif self.spk is not None:
+            self.spk[slot] = 0
+            self.spk_len[slot] = 1.0
+        es = self.enc_state
+        es["t0"][slot] = 0
+        es["t0s"][slot] = 0
+        self.mel[slot] = 0
+        if self.fe_state is not None:
+            for carry in self.fe_state:
+                carry[slot] = 0
+        for layer in es["layers"]:
+            for hist in layer["hist"]:
+                hist[slot] = 0
+        self.searcher.reset_streams(self.search_state, [slot])
+        self.hyps[slot], self.hyp_frames[slot], self.slot_chunks[slot] = [], [], []
+        self.occupied[slot] = True
+        return self
+
+    def release(self, slot):
+        """The session in ``slot`` leaves: returns its hypothesis (what finish() would give for that row) and frees the slot. With beam
+        search nbest() / nbest_frames() still describe the session until the slot is admitted again."""
+        self._need_slots("release()", slot)
+        slot = int(slot)
+        if not self.occupied[slot]:
+            raise ValueError(f"release(): slot {slot} is free")
+        self.occupied[slot] = False
+        return list(self.hyps[slot])
+
+    def _push_slots(self, feats, mel_lens, enc_lens, active, last):
+        B, F = self.B, feats.shape[1]
+        act = list(self.occupied) if active is None else [bool(a) for a in (active.tolist() if isinstance(active, torch.Tensor) else active)]
+        if len(act) != B:
+            raise ValueError(f"active must name {B} slots, got {len(act)}")
+        free = [b for b in range(B) if act[b] and not self.occupied[b]]
+        if free:
+            raise ValueError(f"push(): slot(s) {free} are free; admit() a session before pushing to them")
+        if F == 0 or not any(act):
+            return [list(h) for h in self.hyps] if self.search == "beam" else [[] for _ in range(B)]
+        es, Cn = self.enc_state, _enc_frames(F)
+        for b in range(B):                               # checked before any state of any slot moves
+            if act[b] and es["t0"][b] + Cn > self.max_frames:
+                raise ValueError(f"the push would take slot {b} past start()'s max_frames: {es['t0'][b]} + {Cn} > {self.max_frames} encoder frames")
+        C.require_gpu(feats)
+        dev = feats.device
+        act_dev = torch.tensor(act, dtype=torch.bool, device=dev)
+        ml = torch.full((B,), F, dtype=torch.int64, device=dev) if mel_lens is None else torch.as_tensor(mel_lens, device=dev).long()
+        self.mel = self.mel + ml.clamp(0, F) * act_dev
+        valid = _enc_frames(self.mel) if enc_lens is None else torch.as_tensor(enc_lens, device=dev).long()
+        t0 = es["t0s"].clone().long()                    # each slot's offset before this push
+        x, fe = self.frontend.forward_chunk(feats, self.fe_state)
+        keep = act_dev.view(B, 1, 1, 1)                  # an idle slot keeps its carry (zeros before its first push)
+        self.fe_state = [torch.where(keep, new, torch.zeros_like(new) if self.fe_state is None else self.fe_state[i]) for i, new in enumerate(fe)]
+        e = self.encoder.forward_chunk(x, es, self.spk, self.spk_len, enc_lens=valid.to(torch.int32), active=act)
+        if self.keep:
+            for b in range(B):
+                if act[b]:
+                    self.slot_chunks[b].append(e[b])
+        e = self.encoder_proj(e)
+        n_valid = ((valid - t0).clamp(0, e.shape[1]) * act_dev).to(torch.int32)
+        self.closed = bool(last)
+        if self.search == "beam":
+            best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames,
+                                                                return_frames=self.timestamps, raise_stopped=False)
+            self.hyps = [list(h) for h in best]
+            if self.timestamps:
+                self.hyp_frames = [list(f[0]) for f in self.search_state["frames"]]
+            stopped = {b: why for b, why in self.search_state.get("stopped", {}).items() if self.occupied[b]}
+            if stopped:                                  # every slot's state is stored; the others continue with the next push
+                raise RuntimeError(f"beam_stream: slot(s) {sorted(stopped)} stopped ({sorted(set(stopped.values()))}) with "
+                                   f"cap={self.searcher.cap} hypotheses per frame and max_frames={self.max_frames}; release() and admit() "
+                                   f"them to run again (a larger cap or max_frames needs a new start())")
+            return best
+        if self.timestamps:
+            new, new_frames, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid, return_frames=True)
+            for b, fr in enumerate(new_frames):
+                self.hyp_frames[b].extend(fr)
+        else:
+            new, self.search_state = self.searcher.greedy_stream(e, self.search_state, n_valid)
+        for b, toks in enumerate(new):
+            self.hyps[b].extend(toks)
+        return new
 
     def push_audio(self, wav, wav_lens=None, last=False):
         """start(..., audio=True): feed the next N samples of every stream, wav [B, N], any N. wav_lens [B]: valid samples of this push per
@@ -166,10 +330,15 @@ class StreamingTranscriber:
             self.feat_state = saved
             raise
 
-    def push(self, feats, mel_lens=None, enc_lens=None, last=False):
+    def push(self, feats, mel_lens=None, enc_lens=None, active=None, last=False):
         """Feed the next F feature frames of every stream, feats [B, F, 80]; F must be a multiple of 4 unless ``last`` (no push may
         follow a last one). mel_lens [B]: valid frames of this push per stream (default F); enc_lens [B]: absolute valid encoder frames
-        after this push (default ceil(ceil(L/2)/2) of the mel frames pushed so far). Returns the new symbols of each stream."""
+        after this push (default ceil(ceil(L/2)/2) of the mel frames pushed so far). Returns the new symbols of each stream.
+        start(slots=True): ``active`` (bool per slot, default the occupied slots) names the slots this push belongs to; an occupied
+        slot left out is paused. A slot that is not active keeps every piece of its state bit for bit and returns [] (greedy) or its
+        current hypothesis (beam); mel_lens / enc_lens count in each slot's own session. A push that would take a slot past max_frames
+        raises ValueError naming the slot before any state moves; a beam stream that stops raises RuntimeError naming the slots after
+        every slot's state has been stored."""
         if not self._started:
             raise RuntimeError("push() before start()")
         if self.closed:
@@ -185,6 +354,10 @@ class StreamingTranscriber:
         if (F // 4) % blk and not last:
             raise ValueError(f"with block-causal attention over {blk} frames a push carries a multiple of {4 * blk} feature frames "
                              f"except the last one: got {F}")
+        if getattr(self, "slots", False):
+            return self._push_slots(feats, mel_lens, enc_lens, active, last)
+        if active is not None:
+            raise ValueError("push(active=...) needs start(..., slots=True)")
         if F == 0:
             return [list(h) for h in self.hyps] if self.search == "beam" else [[] for _ in range(self.B)]
         t_done = 0 if self.enc_state is None else self.enc_state["t0"]
@@ -263,10 +436,19 @@ class StreamingTranscriber:
                     del p._bf16_ver
         self._copies = []
 
-    def encoder_out(self):
-        """[B, frames so far, d_model]: the encoder output of every push (start(keep_encoder_out=True))."""
+    def encoder_out(self, slot=None):
+        """[B, frames so far, d_model]: the encoder output of every push (start(keep_encoder_out=True)). start(slots=True):
+        encoder_out(slot) = [frames so far, d_model] of the slot's current session."""
+        if getattr(self, "slots", False):
+            self._need_slots("encoder_out(slot)", slot if slot is not None else -1)
+            chunks = self.slot_chunks[int(slot)]
+            return torch.cat(chunks, dim=0) if chunks else torch.empty(0, self.encoder.d_model, device=self.mel.device)
         return torch.cat(self.enc_chunks, dim=1)
 
     @property
     def encoder_frames(self):
+        """Encoder frames pushed so far. start(slots=True): encoder_frames(slot) = those of the slot's current session (read as a plain
+        number it is the largest over the slots)."""
+        if getattr(self, "slots", False):
+            return _SlotFrames(self.enc_state["t0"])
         return 0 if self.enc_state is None else self.enc_state["t0"]
