@@ -473,6 +473,21 @@ size_t tsasr_running_norm_state_bytes(int B, int n_mels);
 int tsasr_running_norm_fwd(const float *db, const int32_t *n_valid, void *state, void *y, int B, int F, int n_mels, float top_db, double eps,
                            int out_dtype, void *stream);
 
+/* Causal features of slot sessions (StreamingTranscriber.admit(..., audio=True)): every row of the batch is a session with its own sample
+ * count and frame position. The samples live in a ring [B,cap] fp32 on the device, sample s of slot b at ring[b][s % cap]; the host keeps
+ * the counts and sends them per call as a small int32 table.
+ * tsasr_audio_ring_append: tbl [2][B] = {have[b] % cap, lens[b]}; ring[b][(have[b] + i) % cap] = wav[b][i], i < lens[b], wav [B,N] fp32 with
+ * row stride wav_stride elements. One launch; a row with lens[b] == 0 is not touched. N <= cap, cap >= 512.
+ * tsasr_fbank_frames_slots: tbl [3][B] = {first[b], count[b], total[b]} -> out_db [B,F,n_mels] fp32. Row i < count[b] of slot b is the raw
+ * dB of frame first[b] + i of the session's signal with 256 zeros on the left and zeros from sample total[b] on (the right padding of an
+ * ended session; bytes an earlier session left in the ring are never read): the bits tsasr_fbank_fwd / tsasr_fbank_frames compute for the
+ * same samples, from the same frame body. Rows count[b] .. F-1 are zeros. The caller keeps cap large enough that no sample a later frame
+ * reads has been overwritten (csrc/features_stream.hip derives cap). Workspace: tsasr_fbank_frames_workspace_bytes(n_mels).
+ * The normalisation of such frames is tsasr_running_norm_fwd on a [B] state (n_valid[b] = 0 leaves a slot's state alone). */
+int tsasr_audio_ring_append(float *ring, const float *wav, const int32_t *tbl, int B, int N, long long wav_stride, int cap, void *stream);
+int tsasr_fbank_frames_slots(const float *ring, const int32_t *tbl, const float *window, const float *melmat, float *out_db, int B, int cap, int F,
+                             int n_mels, int hop, float amin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Fused seam between two Conformer sub-blocks: s = res + alpha*timemask(dropout_p(x + bias)); y = LayerNorm(s)
  * (Dropout -> [0.5*]x + residual -> masked_fill_ -> nn.LayerNorm; Conformer.py:113-114,194-217,239-259) and its backward
  * (dres = LN_bwd(dy) + dout; dx = alpha*timemask*dropmask/(1-p)*dres; dgamma, dbeta, dbias; dout and any of the three parameter

@@ -4,6 +4,7 @@
     python tools/stream_bench.py [--B 1 32] [--t0 0 1000 3960] [--reps 20] [--json out.json]
     python tools/stream_bench.py --audio                                  # also: the same push fed 1.6 s of waveform (push_audio)
     python tools/stream_bench.py --slots                                  # slot mode (start(slots=True)) beside the lockstep push
+    python tools/stream_bench.py --slots --audio                          # also: every slot a session fed 1.6 s of waveform (admit(audio=True))
     python tools/stream_bench.py --profile-chunks 20 --B 32 --t0 3960     # under rocprofv3 --kernel-trace --stats: 20 chunks and nothing else timed
 
 A chunk is one push of 160 mel frames = 40 encoder frames = 1.6 s of audio. The time of a push is host wall-clock from the call to
@@ -16,6 +17,9 @@ the feature push's, with the median of the feature stage alone (CausalFeatures.f
 --slots: B = 32 and B = 1, every slot occupied, the slots' offsets spread evenly over 0 .. 3960 (B = 1: at 3960) and put back there
 before every push; the median of 15 pushes, the second half of which each do one release() + admit() inside the timed region. The
 lockstep push at t0 = 1000 and t0 = 3960 is timed in the same run (15 pushes each), with the kernel launches per chunk of all three.
+--slots --audio: also B = 32 and B = 1 with every slot an audio session (admit(..., audio=True)) pushed 25600 samples at a time, at the same
+spread offsets: ms per push_audio (median, min, max of 15) and of the feature stage alone (one ring append, the per-slot frame kernel and
+the running normalisation on a state of their own, with their two small host tables), beside the lockstep --audio figures at the same B.
 """
 import argparse
 import importlib
@@ -70,7 +74,7 @@ def make_audio_stream(streaming, brain, B, max_frames, device):
 
 
 def time_audio(st, wav, t0, reps):
-    """Median ms of push_audio (features + push) and of the feature stage alone, at encoder offset t0."""
+    """Median ms of push_audio (features + push) and median, min, max ms of the feature stage alone, at encoder offset t0."""
     both, alone = [], []
     fs = st.features.init_stream(wav.shape[0], wav.device)
     st.features.forward_chunk(wav, fs, group=CHUNK_MEL)
@@ -86,7 +90,7 @@ def time_audio(st, wav, t0, reps):
         torch.cuda.synchronize()
         alone.append((time.perf_counter() - s) * 1e3)
         assert f.shape[1] == CHUNK_MEL
-    return statistics.median(both), statistics.median(alone)
+    return statistics.median(both), statistics.median(alone), min(alone), max(alone)
 
 
 def make_slot_stream(streaming, brain, B, max_frames, device):
@@ -100,6 +104,54 @@ def make_slot_stream(streaming, brain, B, max_frames, device):
     feats = torch.randn(B, CHUNK_MEL, 80, generator=g).to(device)
     offs = [3960] if B == 1 else [round(3960 * b / (B - 1) / CHUNK_ENC) * CHUNK_ENC for b in range(B)]
     return st, feats, spk, offs
+
+
+def make_slot_audio_stream(streaming, brain, B, max_frames, device):
+    D = brain.modules.encoder.d_model
+    g = torch.Generator(device="cpu").manual_seed(7)
+    spk = (torch.randn(B, 1, D, generator=g) * 0.5).to(device)
+    st = streaming.StreamingTranscriber(brain)
+    st.start(B, max_frames, slots=True, max_audio_samples=CHUNK_SAMPLES)
+    for b in range(B):
+        st.admit(b, speaker_embs=spk[b:b + 1], audio=True)
+    wav = (torch.randn(B, CHUNK_SAMPLES, generator=g) * 0.05).to(device)
+    offs = [3960] if B == 1 else [round(3960 * b / (B - 1) / CHUNK_ENC) * CHUNK_ENC for b in range(B)]
+    return st, wav, offs
+
+
+def time_slot_audio(st, wav, offs, reps):
+    """ms of `reps` push_audio calls in slot mode at the spread offsets (every one completes one group of 160 frames per slot), and of the
+    feature stage alone on slot state of its own: the append, the frames of every slot from its ring, the running normalisation."""
+    both, alone, B = [], [], wav.shape[0]
+    cf, cap, dev = st.features, st.feat_slots["ring"].shape[1], wav.device
+    fs = cf.init_slots(B, cap, dev)
+    have = emitted = 0
+
+    def feature_stage(frames):
+        nonlocal have, emitted
+        cf.append_slots(fs, wav, torch.tensor([[have % cap] * B, [CHUNK_SAMPLES] * B], dtype=torch.int32, device=dev))
+        have += CHUNK_SAMPLES
+        if frames:
+            f = cf.frames_slots(fs, torch.tensor([[emitted] * B, [frames] * B, [have] * B], dtype=torch.int32, device=dev), frames)
+            emitted += frames
+            return f
+
+    feature_stage(0)                                 # (the first push completes no group of 160 frames: 16 ms of look-ahead)
+    for _ in range(3):
+        feature_stage(CHUNK_MEL)
+    for _ in range(reps):
+        place_slots(st, offs)
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        st.push_audio(wav)
+        both.append((time.perf_counter() - s) * 1e3)
+        assert st.audio_steps[-1][0] == CHUNK_MEL and all(st.audio_steps[-1][1])
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        feature_stage(CHUNK_MEL)
+        torch.cuda.synchronize()
+        alone.append((time.perf_counter() - s) * 1e3)
+    return both, alone
 
 
 def place_slots(st, offs):
@@ -187,6 +239,19 @@ def main():
                 print(json.dumps(r), flush=True)
                 results.append(r)
                 del sts
+                if a.audio:
+                    sta_s, wav_s, offs = make_slot_audio_stream(streaming, brain, B, a.max_frames, device)
+                    for _ in range(4):
+                        place_slots(sta_s, offs)
+                        sta_s.push_audio(wav_s)
+                    both, alone = time_slot_audio(sta_s, wav_s, offs, a.reps)
+                    med = statistics.median(both)
+                    r = {"B": B, "mode": "slots-audio", "offsets": [offs[0], offs[-1]], "ms_per_audio_chunk_median": round(med, 3),
+                         "ms_min": round(min(both), 3), "ms_max": round(max(both), 3), "ms_features_median": round(statistics.median(alone), 3),
+                         "ms_features_min": round(min(alone), 3), "ms_features_max": round(max(alone), 3), "rtf_audio": round(med / AUDIO_MS, 5)}
+                    print(json.dumps(r), flush=True)
+                    results.append(r)
+                    del sta_s
             st, feats = make_stream(streaming, brain, B, a.max_frames, device)
             for _ in range(0 if a.profile_chunks else 3):     # warm-up: allocations, workspaces, first launches
                 st.push(feats)
@@ -219,8 +284,9 @@ def main():
                 r = {"B": B, "t0": t0, "ms_per_chunk_median": round(med, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
                      "kernel_launches_per_chunk": n, "rtf": round(med / AUDIO_MS, 5), "split": not a.no_split}
                 if a.audio:
-                    med_a, med_f = time_audio(sta, wav, t0, a.reps)
-                    r.update({"ms_per_audio_chunk_median": round(med_a, 3), "ms_features_median": round(med_f, 3), "rtf_audio": round(med_a / AUDIO_MS, 5)})
+                    med_a, med_f, min_f, max_f = time_audio(sta, wav, t0, a.reps)
+                    r.update({"ms_per_audio_chunk_median": round(med_a, 3), "ms_features_median": round(med_f, 3), "ms_features_min": round(min_f, 3),
+                              "ms_features_max": round(max_f, 3), "rtf_audio": round(med_a / AUDIO_MS, 5)})
                 print(json.dumps(r), flush=True)
                 results.append(r)
     if a.json:

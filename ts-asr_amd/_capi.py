@@ -127,6 +127,8 @@ _PROTOS = {
     "tsasr_sentence_norm_fwd": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_int, c_void_p]),
     "tsasr_fbank_frames_workspace_bytes": (c_size_t, [c_int]),
     "tsasr_fbank_frames": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "tsasr_audio_ring_append": (c_int, [c_void_p] * 3 + [c_int, c_int, c_ll, c_int, c_void_p]),
+    "tsasr_fbank_frames_slots": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_float, c_void_p, c_size_t, c_void_p]),
     "tsasr_running_norm_state_bytes": (c_size_t, [c_int] * 2),
     "tsasr_running_norm_fwd": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float, c_double, c_int, c_void_p]),
     "tsasr_add_layernorm_fwd": (c_int, [c_void_p] * 9 + [c_ll, c_int, c_float, c_float, c_ull, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p]),

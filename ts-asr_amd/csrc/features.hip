@@ -12,6 +12,9 @@
 // matrix read through L1/L2) -> dB, plus an order-preserving integer atomicMax per utterance; a second tiny kernel applies
 // the -80 dB floor. Roughly 53 kFLOP and ~1 KB per frame => HBM/latency-bound; everything between the waveform read and
 // the [T,80] write stays in LDS/registers (the reference makes 5 full passes through HBM).
+// The frame arithmetic is one body, fbank_frame<Src>, that three routes instantiate over two sample sources: fbank_kernel (whole
+// utterances, and segments that carry their own padding: LinearSamples) and fbank_slots_kernel (sessions of a slot batch, each read from
+// its own position in its own sample ring: RingSamples). A frame's bits do not depend on the route.
 // sentence_norm: one workgroup per utterance, two passes for mean and unbiased std over the valid frames (lanes own
 // feature bins), one pass to write (x - mean)/max(std, eps) for ALL frames (padded ones too, as the reference does).
 #include "common.h"
@@ -24,12 +27,33 @@ __device__ __forceinline__ unsigned bitrev9(unsigned x) { return __brev(x) >> (3
 __device__ __forceinline__ int f2ord(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
-__global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wav, const float *__restrict__ window,
-                                                    const float *__restrict__ melmat /*[257][n_mels]*/, float *__restrict__ out_db,
-                                                    int *__restrict__ umax, const int *__restrict__ band, int L, int Tn, int n_mels,
-                                                    int hop, float amin, int origin) {
-    // origin: sample offset of frame 0's window start (FB_N / 2 = center=True over the unpadded signal; 0 = frames of a segment that
-    // carries its own padding, tsasr_fbank_frames). umax may be null there: the causal floor is running_norm's business
+// Where a frame's 512 samples come from. has(i): sample i of the frame's window exists (it reads as zero otherwise); at(i): its value.
+// LinearSamples: a row of a [B,L] signal, window sample 0 at signal position ``start`` (negative / past L = the zero padding).
+struct LinearSamples {
+    const float *row;
+    long long start;
+    int L;
+    __device__ __forceinline__ bool has(int i) const { const long long p = start + i; return p >= 0 && p < L; }
+    __device__ __forceinline__ float at(int i) const { return row[start + i]; }
+};
+// RingSamples: a slot's sample ring [cap] (cap >= FB_N) that holds signal sample s at position s % cap. Window sample 0 is signal
+// sample ``s0`` (negative = the left padding) at ring position ``r0`` in [0, cap); samples at or past ``total`` (what the session has
+// received) read as zero: the right padding of an ended session, and bytes an earlier session left in the ring are never read.
+// A wave's 64 loads r0 + i are contiguous except at the one wrap point.
+struct RingSamples {
+    const float *row;
+    long long s0;
+    int r0, cap, total;
+    __device__ __forceinline__ bool has(int i) const { const long long s = s0 + i; return s >= 0 && s < total; }
+    __device__ __forceinline__ float at(int i) const { const int r = r0 + i; return row[r >= cap ? r - cap : r]; }
+};
+
+// One frame per wave, four per workgroup: the frame arithmetic of every log-mel kernel (bit-reversed load, 9 FFT stages, power spectrum,
+// banded mel sum, fp64 log). Every thread of the workgroup calls it (barriers); a wave that is not ``live`` computes nothing. Writes the
+// n_mels dB values to ``out_row`` and returns the wave's maximum (-inf for a wave that is not live). Only ``src`` differs between the kernels.
+template <typename Src>
+__device__ __forceinline__ float fbank_frame(const Src &src, bool live, const float *__restrict__ window, const float *__restrict__ melmat,
+                                             const int *__restrict__ band, float *__restrict__ out_row, int n_mels, float amin) {
     __shared__ float2 buf[4][FB_N];
     __shared__ float2 tw[FB_N / 2];
     __shared__ float pw[4][FB_N / 2 + 1];
@@ -39,15 +63,10 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
         sincospif(-2.f * i / FB_N, &s, &c);
         tw[i] = make_float2(c, s);
     }
-    const long long frame = (long long)blockIdx.x * 4 + wave;
-    const int b = blockIdx.y;
-    const bool live = frame < Tn;
     float2 *x = buf[wave];
     if (live) {
-        const long long start = frame * hop - origin;  // center=True (origin 256): frame t covers [t*hop - 256, t*hop + 256)
         for (int i = lane; i < FB_N; i += 64) {
-            const long long p = start + i;
-            const float v = (p >= 0 && p < L) ? wav[(long long)b * L + p] * window[i] : 0.f;
+            const float v = src.has(i) ? src.at(i) * window[i] : 0.f;
             x[bitrev9(i)] = make_float2(v, 0.f);
         }
     }
@@ -81,12 +100,51 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
                 if (w != 0.f) s += w * pw[wave][k];
             }
             const float db = 10.f * (float)log10((double)fmaxf(s, amin));  // fp64 log: -100 dB exactly for silence, as the reference test asserts
-            out_db[((long long)b * Tn + frame) * n_mels + m] = db;
+            out_row[m] = db;
             mx = fmaxf(mx, db);
         }
     }
+    return mx;
+}
+
+__global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wav, const float *__restrict__ window,
+                                                    const float *__restrict__ melmat /*[257][n_mels]*/, float *__restrict__ out_db,
+                                                    int *__restrict__ umax, const int *__restrict__ band, int L, int Tn, int n_mels,
+                                                    int hop, float amin, int origin) {
+    // origin: sample offset of frame 0's window start (FB_N / 2 = center=True over the unpadded signal; 0 = frames of a segment that
+    // carries its own padding, tsasr_fbank_frames). umax may be null there: the causal floor is running_norm's business
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long frame = (long long)blockIdx.x * 4 + wave;
+    const int b = blockIdx.y;
+    const bool live = frame < Tn;
+    // center=True (origin 256): frame t covers [t*hop - 256, t*hop + 256)
+    const LinearSamples src{wav + (long long)b * L, frame * hop - origin, L};
+    float mx = fbank_frame(src, live, window, melmat, band, out_db + ((long long)b * Tn + frame) * n_mels, n_mels, amin);
     mx = wave_max(mx);
     if (live && lane == 0 && umax) atomicMax(umax + b, f2ord(mx));
+}
+
+// Frames of slot sessions, each from its own position in its own sample ring (tsasr_fbank_frames_slots). tbl [3][B] int32: first[b] =
+// the session's frame index of row 0, count[b] = rows to compute (the rest of the F rows are written as zeros), total[b] = samples the
+// session has received. Row i of slot b is frame first[b] + i of the signal padded with FB_N / 2 zeros on the left and zeros from
+// total[b] on: window sample j is signal sample (first[b] + i) * hop - 256 + j. Whatever tbl holds, no read leaves the slot's ring row.
+__global__ __launch_bounds__(256) void fbank_slots_kernel(const float *__restrict__ ring, const int *__restrict__ tbl, const float *__restrict__ window,
+                                                          const float *__restrict__ melmat, float *__restrict__ out_db, const int *__restrict__ band,
+                                                          int B, int cap, int F, int n_mels, int hop, float amin) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int row = blockIdx.x * 4 + wave;
+    const int first = tbl[b], count = min(max(tbl[B + b], 0), F), total = tbl[2 * B + b];
+    const bool live = row < count;
+    float *out_row = out_db + ((long long)b * F + row) * n_mels;
+    if (!live && row < F)
+        for (int m = lane; m < n_mels; m += 64) out_row[m] = 0.f;
+    if (blockIdx.x * 4 >= count) return;   // (the whole workgroup: no wave of it has a frame)
+    const long long s0 = ((long long)first + row) * hop - FB_N / 2;
+    // s0 >= -FB_N / 2 >= -cap, and a frame with s0 >= total < 2^31 reads no sample: 32 bits (wrapped, if the table is nonsense) serve
+    const int r0 = (int)((unsigned)(s0 + cap) % (unsigned)cap);
+    const RingSamples src{ring + (long long)b * cap, s0, r0, cap, total};
+    fbank_frame(src, live, window, melmat, band, out_row, n_mels, amin);
 }
 
 template <typename T>
@@ -180,6 +238,13 @@ void tsasr_fbank_launch_frames(const float *seg, const float *window, const floa
                                int n_mels, int hop, float amin, hipStream_t st) {
     fbank_bands_kernel<<<cdiv(n_mels, 64), 64, 0, st>>>(melmat, band, n_mels);
     fbank_kernel<<<dim3(cdiv(F, 4), B), 256, 0, st>>>(seg, window, melmat, out_db, nullptr, band, Lseg, F, n_mels, hop, amin, 0);
+}
+
+// csrc/features_stream.hip (tsasr_fbank_frames_slots): per slot the raw dB of count[b] frames from first[b] on, read from its sample ring
+void tsasr_fbank_launch_frames_slots(const float *ring, const int *tbl, const float *window, const float *melmat, float *out_db, int *band, int B,
+                                     int cap, int F, int n_mels, int hop, float amin, hipStream_t st) {
+    fbank_bands_kernel<<<cdiv(n_mels, 64), 64, 0, st>>>(melmat, band, n_mels);
+    fbank_slots_kernel<<<dim3(cdiv(F, 4), B), 256, 0, st>>>(ring, tbl, window, melmat, out_db, band, B, cap, F, n_mels, hop, amin);
 }
 
 extern "C" {

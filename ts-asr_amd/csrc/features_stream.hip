@@ -3,6 +3,8 @@
 //
 // fbank_frames: the offline fbank_kernel (csrc/features.hip) over a segment that carries its own padding: frame i covers
 // seg[i*hop, i*hop + 512) - the bits of the offline center=True frame over the same samples, before the floor.
+// audio_ring_append / fbank_frames_slots: the same frames for sessions that enter and leave a running batch (slots), each with its own
+// sample count and frame position: the samples wait in a ring per slot, the frame kernel (csrc/features.hip) reads them from there.
 // running_norm: per stream a state of fp64 column sums S1, S2 [n_mels], the frame count n (a prior's pseudo-frames included), the running
 // maximum and a flag that it exists. For frame k: rmax = max(rmax, max_m db[k][m]); x = max(db, rmax - top_db) (fp32, as
 // fbank_floor_kernel subtracts); S1 += x, S2 += x*x, n += 1 in fp64 IN FRAME ORDER; y = (x - S1/n) / max(sqrt(max(0, (S2 - S1*S1/n) / (n-1))), eps)
@@ -13,6 +15,30 @@
 
 void tsasr_fbank_launch_frames(const float *seg, const float *window, const float *melmat, float *out_db, int *band, int B, int Lseg, int F,
                                int n_mels, int hop, float amin, hipStream_t st);   // csrc/features.hip
+
+void tsasr_fbank_launch_frames_slots(const float *ring, const int *tbl, const float *window, const float *melmat, float *out_db, int *band, int B,
+                                     int cap, int F, int n_mels, int hop, float amin, hipStream_t st);   // csrc/features.hip
+
+// Slots (sessions that enter and leave a running batch, each fed its own audio): a sample ring [B, cap] fp32 on the device. Slot b holds
+// sample s of its session at ring[b][s % cap]; the host keeps the counts. audio_ring_append writes the lens[b] samples of row b of
+// this push behind the slot's have[b] samples (tbl [2][B] int32: have[b] % cap, lens[b]); one launch for the batch, thread i of a row
+// stores sample i: a wave's 64 stores are contiguous except at the one wrap point. A row with lens[b] == 0 is not touched.
+// The ring must still hold every sample a later frame reads. Frame k reads samples [k*hop - 256, k*hop + 256). With e frames emitted and
+// g frames per group, a drained live session has fewer than g available frames left: (have - 256)/hop + 1 - e <= g - 1, so
+// have < (e + g - 1)*hop + 256, and the oldest sample still needed is e*hop - 256: fewer than (g - 1)*hop + 512 samples are needed.
+// A push adds at most max_audio_samples, so cap = max_audio_samples + (g - 1)*hop + 512 never overwrites a needed sample (the host
+// checks have + lens - max(e*hop - 256, 0) <= cap before every append: a call that a stopped beam stream cut short leaves more).
+#define RA_NT 256
+__global__ __launch_bounds__(RA_NT) void audio_ring_append_kernel(float *__restrict__ ring, const float *__restrict__ wav, const int *__restrict__ tbl,
+                                                                  int B, int N, long long wav_stride, int cap) {
+    const int b = blockIdx.y;
+    const int n = min(min(tbl[B + b], N), cap);
+    const int i = blockIdx.x * RA_NT + threadIdx.x;
+    if (i >= n) return;
+    const int pos = (int)((unsigned)tbl[b] % (unsigned)cap);
+    const int r = pos + i;   // i < cap
+    ring[(long long)b * cap + (r >= cap ? r - cap : r)] = wav[(long long)b * wav_stride + i];
+}
 
 #define RN_NT 128     // threads = bins (n_mels <= 128: 80 bins use both waves)
 #define RN_TILE 128   // frames whose maxima are taken at once
@@ -85,6 +111,32 @@ int tsasr_fbank_frames(const float *seg, const float *window, const float *melma
     TSASR_CHECK_ARG(workspace_bytes >= tsasr_fbank_frames_workspace_bytes(n_mels), "tsasr_fbank_frames: workspace too small");
     tsasr_fbank_launch_frames(seg, window, melmat, out_db, (int *)workspace, B, Lseg, F, n_mels, hop, amin, (hipStream_t)stream);
     TSASR_CHECK_LAUNCH("tsasr_fbank_frames");
+    return 0;
+}
+
+/* ring [B,cap] fp32, wav [B,N] fp32 with row stride wav_stride >= 0 (elements), tbl [2][B] int32 on the device = {have[b] % cap, lens[b]}:
+ * ring[b][(have[b] + i) % cap] = wav[b][i] for i < lens[b] (clamped to N). N <= cap. */
+int tsasr_audio_ring_append(float *ring, const float *wav, const int32_t *tbl, int B, int N, long long wav_stride, int cap, void *stream) {
+    TSASR_CHECK_ARG(ring && wav && tbl, "tsasr_audio_ring_append: null pointer");
+    TSASR_CHECK_ARG(B > 0 && B <= 65535 && N > 0 && cap >= 512 && N <= cap && wav_stride >= 0, "tsasr_audio_ring_append: bad shape (B=%d N=%d cap=%d stride=%lld)", B, N, cap,
+                    wav_stride);
+    audio_ring_append_kernel<<<dim3(cdiv(N, RA_NT), B), RA_NT, 0, (hipStream_t)stream>>>(ring, wav, tbl, B, N, wav_stride, cap);
+    TSASR_CHECK_LAUNCH("tsasr_audio_ring_append");
+    return 0;
+}
+
+/* ring [B,cap] fp32 (tsasr_audio_ring_append), tbl [3][B] int32 on the device = {first[b], count[b], total[b]} -> out_db [B,F,n_mels] fp32:
+ * row i < count[b] of slot b = raw dB of frame first[b] + i of the session's signal padded with 256 zeros on the left and with zeros from
+ * sample total[b] on (the frame arithmetic of tsasr_fbank_fwd / tsasr_fbank_frames, bit for bit); rows count[b] .. F-1 are zeros. The
+ * caller guarantees that the ring still holds samples (first[b]*hop - 256) .. min(total[b], (first[b] + count[b] - 1)*hop + 256) - 1. */
+int tsasr_fbank_frames_slots(const float *ring, const int32_t *tbl, const float *window, const float *melmat, float *out_db, int B, int cap, int F,
+                             int n_mels, int hop, float amin, void *workspace, size_t workspace_bytes, void *stream) {
+    TSASR_CHECK_ARG(ring && tbl && window && melmat && out_db && workspace, "tsasr_fbank_frames_slots: null pointer");
+    TSASR_CHECK_ARG(B > 0 && B <= 65535 && hop > 0 && cap >= 512 && F > 0 && n_mels > 0 && n_mels <= 128,
+                    "tsasr_fbank_frames_slots: bad shape (B=%d cap=%d F=%d n_mels=%d hop=%d)", B, cap, F, n_mels, hop);
+    TSASR_CHECK_ARG(workspace_bytes >= tsasr_fbank_frames_workspace_bytes(n_mels), "tsasr_fbank_frames_slots: workspace too small");
+    tsasr_fbank_launch_frames_slots(ring, tbl, window, melmat, out_db, (int *)workspace, B, cap, F, n_mels, hop, amin, (hipStream_t)stream);
+    TSASR_CHECK_LAUNCH("tsasr_fbank_frames_slots");
     return 0;
 }
 

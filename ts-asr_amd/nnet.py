@@ -377,6 +377,31 @@ class CausalFeatures(nn.Module):
         state["emitted"] = e1
         return feats, n_valid, state
 
+    # ---- slots: every row a session of its own (StreamingTranscriber.admit(..., audio=True)); the caller keeps the counts -----------
+    def init_slots(self, B, cap, device):
+        """State of B slots: a sample ring [B, cap] on the device (sample s of a slot's session at s % cap; never cleared), the
+        normaliser's state (one row per slot) and the filter-band workspace of the frame kernel."""
+        if int(cap) < 2 * self.pad:
+            raise ValueError(f"init_slots: the ring holds at least one window of {2 * self.pad} samples, got cap={cap}")
+        return {"ring": torch.zeros(B, int(cap), dtype=torch.float32, device=device), "norm": ops.running_norm_state(B, self.n_mels, device),
+                "ws": torch.empty(C.lib().tsasr_fbank_frames_workspace_bytes(self.n_mels), dtype=torch.uint8, device=device)}
+
+    def reset_slot(self, state, slot, prior=None):
+        """A new session in ``slot``: its normaliser row is a fresh stream's (zeros, or ``prior`` = (mean, std, n0) as
+        ops.running_norm_state writes it). The ring keeps its bytes: samples a session has not received are never read."""
+        state["norm"][slot] = ops.running_norm_state(1, self.n_mels, state["norm"].device, prior)[0]
+
+    def append_slots(self, state, wav, tbl):
+        """ring[b][(have[b] + i) % cap] = wav[b][i], i < lens[b]; tbl [2,B] int32 on the device = (have % cap, lens). One launch."""
+        ops.audio_ring_append(state["ring"], wav, tbl)
+
+    def frames_slots(self, state, tbl, F):
+        """F normalised frames per slot -> [B,F,n_mels]: row i < count[b] of slot b is frame first[b] + i of its session (the bits of
+        forward() over the session alone), computed from its ring and advancing its normaliser row; a slot with count 0 keeps its
+        state. tbl [3,B] int32 on the device = (first, count, total samples received). Frames (with the tiny filter-band kernel before them) and norm: no copy of the samples, whatever B."""
+        db = ops.fbank_frames_slots(state["ring"], tbl, F, self.fbank.window, self.fbank.fbank_matrix, self.hop, self.fbank.amin, ws=state["ws"])
+        return ops.running_norm(db, state["norm"], tbl[1], self.fbank.top_db, self.eps, self.out_dtype)
+
 # ------------------------------------------------------------------------------------------------------
 # A17 / A18 the two augmenters of compute_forward (TRAIN stage, ``augment: True``; train_librispeechmix_scratch.py:82-94)
 # ------------------------------------------------------------------------------------------------------

@@ -29,6 +29,7 @@ STATUS = {
     "beam search / LM fusion with V > 63 or an embedding past 64 columns (V, E <= 1024, beam_size <= 64)":
         "HIP (search.hip: beam_search_wide_kernel, workgroup-wide log-softmax and top-k; offline, streams, timestamps and LM fusion)",
     "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP", "fbank_frames": "HIP", "running_norm": "HIP (features_stream.hip)",
+    "fbank_frames_slots": "HIP (features.hip: the fbank frame body over per-slot sample rings)", "audio_ring_append": "HIP (features_stream.hip)",
     "relpos_attention": "HIP (forward: everything-in-LDS kernel for T <= 256 and, per chunk of 256 keys, for long sequences in small batches, streaming kernel otherwise; backward = query-major, key-major, d(pk) and partial-sum kernels)",
     # What is NOT hand-written: shapes / modes none of the three recipes reaches. Each of these routes goes through lib_fallback(): counted in
     # LIB_FALLBACKS, announced once (warnings), refused with TsasrHipMissing when ops.STRICT_HIP (env TSASR_STRICT_HIP=1) is set.
@@ -1616,6 +1617,49 @@ def fbank_frames(seg, window, fbank_matrix, hop, amin):
         C.check(C.lib().tsasr_fbank_frames(C.ptr(s), C.ptr(window.float().contiguous()), C.ptr(fbank_matrix.float().contiguous()), C.ptr(out),
                                            B, Lseg, F, n_mels, int(hop), float(amin), C.ptr(ws), ws.numel(), C.stream_ptr()),
                 "tsasr_fbank_frames")
+    return out
+
+
+def audio_ring_append(ring, wav, tbl):
+    """Slot sample rings: ring[b][(have[b] + i) % cap] = wav[b][i] for i < lens[b], IN PLACE, one launch (HIP kernel). ring [B,cap] fp32,
+    wav [B,N] fp32 with unit stride along N (any row stride >= 0: no copy is made), tbl [2,B] int32 on the device = (have % cap, lens)."""
+    C.require_gpu(ring, wav, tbl)
+    B, cap = ring.shape
+    if ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError("audio_ring_append: ring is a contiguous fp32 [B, cap] tensor")
+    if wav.dtype != torch.float32 or wav.ndim != 2 or wav.shape[0] != B or wav.shape[1] > cap or (wav.shape[1] > 1 and wav.stride(1) != 1) or wav.stride(0) < 0:
+        raise ValueError(f"audio_ring_append: wav is fp32 [B={B}, N <= {cap}] with unit stride along N, got {tuple(wav.shape)} {wav.dtype}")
+    if tbl.dtype != torch.int32 or tbl.shape != (2, B) or not tbl.is_contiguous():
+        raise ValueError(f"audio_ring_append: tbl must be int32 [2, {B}]")
+    N = wav.shape[1]
+    if N == 0:
+        return ring
+    with prof.region("audio_ring_append"):
+        C.check(C.lib().tsasr_audio_ring_append(C.ptr(ring), C.ptr(wav), C.ptr(tbl), B, N, int(wav.stride(0)), cap, C.stream_ptr()),
+                "tsasr_audio_ring_append")
+    return ring
+
+
+def fbank_frames_slots(ring, tbl, F, window, fbank_matrix, hop, amin, ws=None):
+    """Raw log-mel dB [B,F,n_mels] fp32 of slot sessions, each from its own position in its own sample ring (HIP kernel; the frame
+    arithmetic of ops.fbank / ops.fbank_frames, bit for bit). ring [B,cap] fp32 (audio_ring_append), tbl [3,B] int32 on the device =
+    (first frame, frames to compute, samples received) per slot; rows at or past a slot's count are zeros."""
+    C.require_gpu(ring, tbl)
+    B, cap = ring.shape
+    if ring.dtype != torch.float32 or not ring.is_contiguous() or cap < 512:
+        raise ValueError("fbank_frames_slots: ring is a contiguous fp32 [B, cap >= 512] tensor")
+    if tbl.dtype != torch.int32 or tbl.shape != (3, B) or not tbl.is_contiguous():
+        raise ValueError(f"fbank_frames_slots: tbl must be int32 [3, {B}]")
+    if int(F) < 1:
+        raise ValueError(f"fbank_frames_slots: F must be >= 1, got {F}")
+    n_mels = fbank_matrix.shape[1]
+    out = torch.empty(B, int(F), n_mels, dtype=torch.float32, device=ring.device)
+    if ws is None:                                   # (a caller that runs every tick keeps one: nnet.CausalFeatures.init_slots)
+        ws = _ws(C.lib().tsasr_fbank_frames_workspace_bytes(n_mels), ring.device)
+    with prof.region("fbank_frames_slots"):
+        C.check(C.lib().tsasr_fbank_frames_slots(C.ptr(ring), C.ptr(tbl), C.ptr(window.float().contiguous()), C.ptr(fbank_matrix.float().contiguous()),
+                                                 C.ptr(out), B, cap, int(F), n_mels, int(hop), float(amin), C.ptr(ws), ws.numel(), C.stream_ptr()),
+                "tsasr_fbank_frames_slots")
     return out
 
 

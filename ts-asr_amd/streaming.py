@@ -51,8 +51,23 @@ Slots (start(..., slots=True)): the B rows of the batch are slots that sessions 
 Every slot has its own offset (a device int32 array the kernels read, tsasr_relpos_attn_stream_slots_fwd, and a host mirror), mel
 count, front-end carry, conv histories and search state; admit() resets them for that slot alone. The K/V cache rows are not cleared:
 rows at or past a slot's offset are never read. mel_lens / enc_lens, the emission frames, encoder_out(slot) and encoder_frames(slot) are
-absolute in the slot's own session. A session is still bounded by max_frames. The audio route is lockstep only: CausalFeatures' stream
-state counts samples for the whole batch, so a server runs one CausalFeatures stream per session (B = 1) and pushes its features.
+absolute in the slot's own session. A session is still bounded by max_frames.
+
+Slot sessions fed audio (admit(slot, ..., audio=True)): every such session has its own sample count, frame position and running
+statistics, in one batch with feature-fed sessions if need be.
+
+    st.start(batch_size=B, max_frames=4000, slots=True, max_audio_samples=32000)
+    st.admit(0, speaker_embs=emb, audio=True)                   # feature_prior=(mean, std, n0) starts this session's statistics
+    new = st.push_audio(wav, wav_lens=[1600, 0, 777])           # wav [B, N]: each active slot's next samples, any number per slot
+    new = st.push_audio(wav, end=[True, False, False])          # session 0's audio stops with this call: its last frames go out
+    hyp = st.release(0)
+
+The samples live in a ring per slot on the device (tsasr_audio_ring_append: one launch per call appends every slot's packet), the frames
+of a step are computed by one launch that reads each slot's frames from its own position in its own ring (tsasr_fbank_frames_slots: the
+frame body of the offline kernel), normalised by the running_norm kernel on a state row per slot, and handed to the slot push():
+whatever B, no per-session launch, copy or concatenation. Which frames go when is plan_audio_steps' rule; audio_steps logs it. A
+session's frames are the bits nnet.CausalFeatures.forward gives for its audio alone. start(slots=True, audio=True) still raises: in
+slot mode audio is a property of a session (admit), not of the batch.
 """
 import types
 
@@ -60,7 +75,52 @@ import torch
 
 from . import _capi as C
 
-__all__ = ["StreamingTranscriber"]
+__all__ = ["StreamingTranscriber", "audio_frames_available", "audio_ring_capacity", "plan_audio_steps"]
+
+
+def audio_frames_available(samples, ended, hop=160, pad=256):
+    """Causal feature frames of a session that has received ``samples`` samples: frame k covers samples [k*hop - pad, k*hop + pad), so
+    a live session has frames 0 .. (samples - pad)//hop once ``pad`` samples are there; an ended one (zeros follow) all 1 + samples//hop."""
+    if ended:
+        return 1 + samples // hop
+    return (samples - pad) // hop + 1 if samples >= pad else 0
+
+
+def audio_ring_capacity(max_audio_samples, group, hop=160, pad=256):
+    """Samples per slot of the ring that feeds audio sessions. The oldest sample a session with e frames emitted still needs is
+    e*hop - pad. After a drain a live session has fewer than ``group`` available frames left, (P - pad)//hop + 1 - e <= group - 1,
+    hence P < (e + group - 1)*hop + pad: it needs fewer than (group - 1)*hop + 2*pad samples (a session with P < pad needs P + pad <
+    2*pad; an ended one is drained completely). The next push adds at most max_audio_samples."""
+    return int(max_audio_samples) + (int(group) - 1) * hop + 2 * pad
+
+
+def _ring_needed(samples, emitted, hop, pad):
+    """Samples of a session the ring must still hold: from the first one its next frame reads to the last one received."""
+    return samples - max(emitted * hop - pad, 0)
+
+
+def plan_audio_steps(samples, emitted, ended, group, hop=160, pad=256):
+    """The engine steps that drain the audio sessions of a slot batch. Per slot: ``samples`` received so far (None: the slot takes no
+    part), ``emitted`` frames already pushed, ``ended`` whether its audio has stopped. A slot is ready with at least ``group`` frames
+    available (audio_frames_available) and not emitted, an ended slot while any frame remains. One step takes the ready slots and
+    pushes F = group*k frames, k the smallest count among them (a live slot counts its complete groups, an ended one
+    ceil(remaining / group)); an ended slot's mel_lens entry is min(remaining, F), the other ready slots' F, the rest are inactive.
+    Steps repeat until no slot is ready. -> (steps = [(F, active [B] bools, mel_lens [B] ints)], emitted after the steps [B])."""
+    g, B = int(group), len(samples)
+    if g < 1:
+        raise ValueError(f"group must be >= 1, got {group}")
+    done = list(emitted)
+    avail = [0 if samples[b] is None else audio_frames_available(samples[b], ended[b], hop, pad) for b in range(B)]
+    steps = []
+    while True:
+        rem = [0 if samples[b] is None else avail[b] - done[b] for b in range(B)]
+        ready = [rem[b] >= g or (bool(ended[b]) and rem[b] > 0) for b in range(B)]
+        if not any(ready):
+            return steps, done
+        F = g * min(-(-rem[b] // g) if ended[b] else rem[b] // g for b in range(B) if ready[b])
+        lens = [(min(rem[b], F) if ended[b] else F) if ready[b] else 0 for b in range(B)]
+        steps.append((F, ready, lens))
+        done = [done[b] + lens[b] for b in range(B)]
 
 
 class _SlotFrames(int):
@@ -107,7 +167,7 @@ class StreamingTranscriber:
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False,
-              audio=False, feature_prior=None, slots=False, max_speaker_frames=1):
+              audio=False, feature_prior=None, slots=False, max_speaker_frames=1, max_audio_samples=32000, keep_features=False):
         """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
         ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
         ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
@@ -115,14 +175,16 @@ class StreamingTranscriber:
         (frames(), nbest_frames()). audio: the stream is fed waveforms (push_audio) - causal features over the recipe's Fbank tables,
         ``feature_prior`` = (mean [n_mels], std [n_mels], n0) optionally starting their running statistics (nnet.CausalFeatures).
         slots: the B rows are slots, all free to begin with, that sessions enter with admit() and leave with release() (module
-        docstring); the speaker embedding then comes per session with admit(), padded to ``max_speaker_frames`` rows."""
+        docstring); the speaker embedding then comes per session with admit(), padded to ``max_speaker_frames`` rows. Slot sessions
+        admitted with audio=True are fed with push_audio(): ``max_audio_samples`` is the most samples one call may carry per slot (it
+        sizes the sample rings, which the first such admit() allocates); keep_features keeps their feature frames for features_out()."""
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
         if slots and (enroll is not None or speaker_embs is not None):
             raise ValueError("start(slots=True): the speaker embedding comes per session, with admit(slot, enroll=... / speaker_embs=...)")
         if slots and audio:
-            raise ValueError("start(slots=True, audio=True): the audio route runs in lockstep only; run one CausalFeatures stream per "
-                             "session and push its features")
+            raise ValueError("start(slots=True, audio=True): in slot mode a session, not the batch, is fed audio: start(slots=True) and "
+                             "admit(slot, ..., audio=True)")
         if hasattr(self.brain, "_setup_dtype"):      # the brain's compute dtype (as fit / evaluate set it)
             self.brain._setup_dtype()
         for mod in (self.frontend, self.encoder, self.encoder_proj, self.searcher):
@@ -171,6 +233,14 @@ class StreamingTranscriber:
             self.max_speaker_frames = int(max_speaker_frames)
             self.occupied = [False] * self.B
             self.slot_chunks = [[] for _ in range(self.B)]
+            if int(max_audio_samples) < 1:
+                raise ValueError(f"start(): max_audio_samples must be >= 1, got {max_audio_samples}")
+            self.max_audio_samples, self.keep_feats = int(max_audio_samples), bool(keep_features)
+            self.feat_slots = None                   # sample rings + normaliser rows: allocated by the first admit(..., audio=True)
+            self.audio_slot = [False] * self.B       # per slot: its session is fed audio; samples received; frames pushed; audio ended
+            self.a_have, self.a_emit, self.a_end = [0] * self.B, [0] * self.B, [False] * self.B
+            self.feat_chunks = [[] for _ in range(self.B)]
+            self.audio_steps = []
             dev = self.encoder.norm.norm.weight.device
             self.enc_state = self.encoder.init_stream(self.B, self.max_frames, device=dev, slots=True)
             self.mel = torch.zeros(self.B, dtype=torch.int64, device=dev)
@@ -184,12 +254,15 @@ class StreamingTranscriber:
         if slot is not None and not 0 <= int(slot) < self.B:
             raise ValueError(f"{what}: slot {slot} is not one of the {self.B} slots")
 
-    def admit(self, slot, enroll=None, speaker_embs=None, speaker_embs_length=None):
+    def admit(self, slot, enroll=None, speaker_embs=None, speaker_embs_length=None, audio=False, feature_prior=None):
         """A new session enters the free ``slot``. Its speaker embedding: ``enroll`` = (one enrollment signal [1, N], its relative
         length [1]) through the recipe's speaker branch, or ``speaker_embs`` [1, S, D] (+ ``speaker_embs_length`` [1] relative, for
         cross-attention), S <= max_speaker_frames; neither = no injection. Reset for this slot only: offset and mel count, the
         front-end carries, both conv histories of every layer, the search state, the hypothesis, its frames and the kept encoder
-        output. The K/V cache keeps its bytes: rows at or past a slot's offset are never read."""
+        output. The K/V cache keeps its bytes: rows at or past a slot's offset are never read. audio: the session is fed waveform
+        (push_audio) instead of features; also reset for this slot are then its sample and emitted-frame counts, its ended flag and its
+        row of the normaliser's state (zeros, or ``feature_prior`` = (mean [n_mels], std [n_mels], n0) as ops.running_norm_state writes
+        it). The sample ring keeps its bytes: samples a session has not received are never read."""
         self._need_slots("admit()", slot)
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
@@ -198,6 +271,8 @@ class StreamingTranscriber:
             raise ValueError(f"admit(): slot {slot} is occupied; release() it first")
         if enroll is not None and speaker_embs is not None:
             raise ValueError("admit(): give enroll or speaker_embs, not both")
+        if feature_prior is not None and not audio:
+            raise ValueError("admit(): feature_prior goes with audio=True")
         if enroll is not None:
             sig, lens = enroll
             batch = types.SimpleNamespace(enroll_sig=(sig, lens))
@@ -233,6 +308,18 @@ class StreamingTranscriber:
                 hist[slot] = 0
         self.searcher.reset_streams(self.search_state, [slot])
         self.hyps[slot], self.hyp_frames[slot], self.slot_chunks[slot] = [], [], []
+        if audio:
+            if self.features is None:
+                from .nnet import CausalFeatures
+                mods = self.brain.modules
+                fbank = mods["feature_extractor"] if isinstance(mods, dict) else mods.feature_extractor
+                self.features = CausalFeatures(fbank).to(fbank.window.device)
+                self.audio_group = 4 * max(int(getattr(self.encoder.layers[0], "chunk_size", 0) or 0), 1)
+                cap = audio_ring_capacity(self.max_audio_samples, self.audio_group, self.features.hop, self.features.pad)
+                self.feat_slots = self.features.init_slots(self.B, cap, fbank.window.device)
+            self.features.reset_slot(self.feat_slots, slot, feature_prior)
+        self.audio_slot[slot] = bool(audio)
+        self.a_have[slot], self.a_emit[slot], self.a_end[slot], self.feat_chunks[slot] = 0, 0, False, []
         self.occupied[slot] = True
         return self
 
@@ -244,16 +331,23 @@ class StreamingTranscriber:
         if not self.occupied[slot]:
             raise ValueError(f"release(): slot {slot} is free")
         self.occupied[slot] = False
+        self.audio_slot[slot] = False                # (samples of an audio session that were still pending are dropped)
         return list(self.hyps[slot])
 
-    def _push_slots(self, feats, mel_lens, enc_lens, active, last):
+    def _push_slots(self, feats, mel_lens, enc_lens, active, last, from_audio=False):
         B, F = self.B, feats.shape[1]
-        act = list(self.occupied) if active is None else [bool(a) for a in (active.tolist() if isinstance(active, torch.Tensor) else active)]
+        if active is None:                               # (with no audio session: the occupied slots)
+            act = [o and not a for o, a in zip(self.occupied, self.audio_slot)]
+        else:
+            act = [bool(a) for a in (active.tolist() if isinstance(active, torch.Tensor) else active)]
         if len(act) != B:
             raise ValueError(f"active must name {B} slots, got {len(act)}")
         free = [b for b in range(B) if act[b] and not self.occupied[b]]
         if free:
             raise ValueError(f"push(): slot(s) {free} are free; admit() a session before pushing to them")
+        fed = [b for b in range(B) if act[b] and self.audio_slot[b]]
+        if fed and not from_audio:
+            raise ValueError(f"push(): the session(s) in slot(s) {fed} are fed audio (admit(..., audio=True)): push_audio() computes their features")
         if F == 0 or not any(act):
             return [list(h) for h in self.hyps] if self.search == "beam" else [[] for _ in range(B)]
         es, Cn = self.enc_state, _enc_frames(F)
@@ -300,14 +394,132 @@ class StreamingTranscriber:
             self.hyps[b].extend(toks)
         return new
 
-    def push_audio(self, wav, wav_lens=None, last=False):
+    def _push_audio_slots(self, wav, wav_lens, active, end):
+        """push_audio() in slot mode: every check first, then one append for the batch, then the planned steps."""
+        B = self.B
+        if self.features is None:
+            raise RuntimeError("push_audio() needs an audio session: admit(slot, ..., audio=True)")
+        if wav.ndim != 2 or wav.shape[0] != B:
+            raise ValueError(f"wav must be [B={B}, N], got {tuple(wav.shape)}")
+        N = wav.shape[1]
+        if N > self.max_audio_samples:
+            raise ValueError(f"push_audio(): {N} samples per slot is more than start()'s max_audio_samples={self.max_audio_samples}")
+        hop, pad, g = self.features.hop, self.features.pad, self.audio_group
+        have, emit, ended = self.a_have, self.a_emit, self.a_end
+        left = [audio_frames_available(have[b], ended[b], hop, pad) - emit[b] for b in range(B)]
+        flags = lambda x: [bool(v) for v in (x.tolist() if isinstance(x, torch.Tensor) else x)]  # noqa: E731
+        if active is None:                               # the audio sessions that go on, and ended ones a stopped call left undrained
+            act = [self.occupied[b] and self.audio_slot[b] and (not ended[b] or left[b] > 0) for b in range(B)]
+        else:
+            act = flags(active)
+            if len(act) != B:
+                raise ValueError(f"active must name {B} slots, got {len(act)}")
+            for b in range(B):
+                if act[b] and not self.occupied[b]:
+                    raise ValueError(f"push_audio(): slot {b} is free; admit() a session before pushing to it")
+                if act[b] and not self.audio_slot[b]:
+                    raise ValueError(f"push_audio(): the session in slot {b} is fed features (push()); admit(..., audio=True) for audio")
+                if act[b] and ended[b] and left[b] <= 0:
+                    raise ValueError(f"push_audio(): the audio of the session in slot {b} has ended; release() it")
+        stop = [False] * B if end is None else flags(end)
+        if len(stop) != B or any(s and not a for s, a in zip(stop, act)):
+            raise ValueError(f"end must name slots among the {B} that are active in this call, got {stop}")
+        if wav_lens is None:
+            lens = [N if act[b] and not ended[b] else 0 for b in range(B)]
+        else:
+            lens = [int(v) for v in torch.as_tensor(wav_lens).reshape(-1).tolist()]
+            if len(lens) != B or any(v < 0 or v > N for v in lens):
+                raise ValueError(f"wav_lens must hold B={B} counts in [0, {N}], got {lens}")
+            lens = [v if act[b] else 0 for b, v in enumerate(lens)]
+            late = [b for b in range(B) if ended[b] and lens[b]]
+            if late:
+                raise ValueError(f"push_audio(): the audio of slot(s) {late} has ended: they carry 0 samples")
+        cap = self.feat_slots["ring"].shape[1]
+        for b in range(B):                               # (audio_ring_capacity: only a call that a stopped beam stream cut short leaves this much)
+            if lens[b] and _ring_needed(have[b] + lens[b], emit[b], hop, pad) > cap:
+                raise ValueError(f"push_audio(): slot {b} holds {_ring_needed(have[b], emit[b], hop, pad)} samples that are not pushed yet; "
+                                 f"{lens[b]} more do not fit its ring of {cap}: drain it with a call that carries 0 samples")
+            if have[b] + lens[b] >= 2 ** 31:
+                raise ValueError(f"push_audio(): slot {b} would pass 2^31 samples")
+        new_have = [have[b] + lens[b] for b in range(B)]
+        new_end = [ended[b] or stop[b] for b in range(B)]
+        steps, _ = plan_audio_steps([new_have[b] if act[b] else None for b in range(B)], emit, new_end, g, hop, pad)
+        t0 = self.enc_state["t0"]
+        for b in range(B):
+            grow = sum(_enc_frames(F) for F, on, _ in steps if on[b])
+            if t0[b] + grow > self.max_frames:
+                raise ValueError(f"the push would take slot {b} past start()'s max_frames: {t0[b]} + {grow} > {self.max_frames} encoder frames")
+        if any(lens):
+            C.require_gpu(wav)
+        # ---- checked: from here on the state moves
+        dev = self.feat_slots["ring"].device
+        if any(lens):
+            w = wav.detach()
+            if w.dtype != torch.float32:
+                w = w.float()
+            if N > 1 and w.stride(1) != 1:
+                w = w.contiguous()
+            self.features.append_slots(self.feat_slots, w, torch.tensor([[h % cap for h in have], lens], dtype=torch.int32, device=dev))
+        self.a_have, self.a_end = new_have, new_end
+        out = [[] for _ in range(B)]
+        best = None
+        for F, on, ml in steps:
+            tbl = torch.tensor([self.a_emit, ml, new_have], dtype=torch.int32, device=dev)
+            feats = self.features.frames_slots(self.feat_slots, tbl, F)
+            for b in range(B):
+                if on[b] and ml[b] < F:                  # the padded tail of an ended session's last group: zeros
+                    feats[b, ml[b]:] = 0
+                if on[b] and self.keep_feats:
+                    self.feat_chunks[b].append(feats[b, :ml[b]])
+            # the step's frames are computed and the normaliser has moved: it counts, even if a beam stream stops in it (RuntimeError
+            # after every slot's state is stored; the later steps' samples stay in the rings and the next call drains them)
+            self.a_emit = [e + m for e, m in zip(self.a_emit, ml)]
+            self.audio_steps.append((F, list(on), list(ml)))
+            best = self._push_slots(feats, tbl[1], None, on, False, from_audio=True)
+            if self.search != "beam":
+                for b, toks in enumerate(best):
+                    out[b].extend(toks)
+        if self.search == "beam":
+            return best if best is not None else [list(h) for h in self.hyps]
+        return out
+
+    def features_out(self, slot):
+        """start(slots=True, keep_features=True): [frames so far, n_mels], the normalised feature frames the audio session in ``slot``
+        has been given (the bits nnet.CausalFeatures.forward computes for its audio alone)."""
+        self._need_slots("features_out(slot)", slot)
+        if not self.keep_feats:
+            raise RuntimeError("features_out() needs start(..., keep_features=True)")
+        chunks = self.feat_chunks[int(slot)]
+        mods = self.brain.modules
+        n_mels = (mods["feature_extractor"] if isinstance(mods, dict) else mods.feature_extractor).n_mels
+        return torch.cat(chunks, dim=0) if chunks else torch.empty(0, n_mels, device=self.mel.device)
+
+    def push_audio(self, wav, wav_lens=None, last=False, active=None, end=None):
         """start(..., audio=True): feed the next N samples of every stream, wav [B, N], any N. wav_lens [B]: valid samples of this push per
         stream (default N; fewer ends that stream, whose later pushes carry 0). The frames whose samples have arrived are computed in
         whole groups of 4 (4 x attention_chunk_size with block-causal attention) and pushed; the rest waits for the next push, every
         remaining frame goes with the ``last`` one. Returns what push() returns (for no frames when no group is complete yet). A push that
-        raises (bad wav_lens, past max_frames) leaves the stream, its buffered samples and running statistics included, as it was."""
+        raises (bad wav_lens, past max_frames) leaves the stream, its buffered samples and running statistics included, as it was.
+        start(slots=True): feeds the sessions admitted with audio=True. wav_lens [B]: this call's samples per slot, 0 .. N <=
+        max_audio_samples (default N for the active slots); ``active`` (bool per slot): the sessions this call belongs to, default the
+        occupied audio sessions whose audio has not ended - a free slot, a feature-fed session or an ended one raises ValueError; ``end``
+        (bool per slot): sessions whose audio stops with this call. The samples are appended to the slots' rings, then the steps
+        plan_audio_steps gives are pushed, each through the slot push(); an ended session's last frames go out as a group padded with
+        zeros and a short mel_lens. Returns per slot the concatenation of its steps' symbols (greedy) or its best hypothesis (beam).
+        Every check runs before anything moves (a plan that would take a slot past max_frames included). A beam stream that stops
+        raises RuntimeError as push() does after that step; the later steps wait for the next call."""
         if not self._started:
             raise RuntimeError("push_audio() before start()")
+        if getattr(self, "slots", False):
+            if self.closed:
+                raise RuntimeError("push_audio() after the last push of the stream")
+            if torch.is_grad_enabled():
+                raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+            if last:
+                raise ValueError("push_audio(last=True) belongs to lockstep streams; a slot session's audio stops with end=[...]")
+            return self._push_audio_slots(wav, wav_lens, active, end)
+        if active is not None or end is not None:
+            raise ValueError("push_audio(active=..., end=...) needs start(..., slots=True)")
         if self.features is None:
             raise RuntimeError("push_audio() needs start(..., audio=True)")
         if self.closed:
@@ -334,8 +546,8 @@ class StreamingTranscriber:
         """Feed the next F feature frames of every stream, feats [B, F, 80]; F must be a multiple of 4 unless ``last`` (no push may
         follow a last one). mel_lens [B]: valid frames of this push per stream (default F); enc_lens [B]: absolute valid encoder frames
         after this push (default ceil(ceil(L/2)/2) of the mel frames pushed so far). Returns the new symbols of each stream.
-        start(slots=True): ``active`` (bool per slot, default the occupied slots) names the slots this push belongs to; an occupied
-        slot left out is paused. A slot that is not active keeps every piece of its state bit for bit and returns [] (greedy) or its
+        start(slots=True): ``active`` (bool per slot, default the occupied slots whose sessions are fed features) names the slots this
+        push belongs to; an occupied slot left out is paused, a session fed audio (admit(..., audio=True)) raises ValueError. A slot that is not active keeps every piece of its state bit for bit and returns [] (greedy) or its
         current hypothesis (beam); mel_lens / enc_lens count in each slot's own session. A push that would take a slot past max_frames
         raises ValueError naming the slot before any state moves; a beam stream that stops raises RuntimeError naming the slots after
         every slot's state has been stored."""
