@@ -711,6 +711,39 @@ int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, 
                            double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
                            double lm_weight);
 
+/* Beam search with contextual biasing (csrc/search.hip, BeamBiasArgs): phrase lists as prefix tries boost the search by shallow fusion.
+ * A graph has states 0 (root) .. S-1; the packed arrays hold the graphs one after another, S + 1 rows each: child_off int32 [rows]
+ * (absolute indices into child_tok / child_to; state row r's edges are child_off[r] .. child_off[r + 1], a graph's last row only closes
+ * the one before it), child_tok int32 [edges] ascending
+ * within a row, child_to int32 [edges] = the graph's own state ids, pending fp64 [rows] = weight * (depth - depth of the deepest
+ * terminal on the path), base int32 [B] = first row of utterance b's graph (< 0 or >= rows: b is not biased), weight fp64 [B]. Each
+ * hypothesis carries a trie state s (0 at the start). A non-blank extension by v: s has a child c on v -> s' = c, d = w; else
+ * d = -pending[s], and if the root has a child c on v -> s' = c, d = d + w, else s' = 0 (no failure links). The extension scores
+ * ((logp(a) + logp_joint[v]) [+ lm_weight * lm_logp[v]]) + d in fp64, d last; the top-k, the expand_beam test and the blank copies
+ * read the joint alone. The n-best is ranked and reported with (logp - pending[s]) / len; the stored beam keeps logp, so a stream in
+ * pieces gives the bits of one call. That child_tok ascends within a row is NOT checked on the device: a binary search reads it, the
+ * host constructor (biasing.ContextGraph) guarantees it. The function takes tsasr_beam_search_lm's arguments, then the descriptor:
+ * n_valid NULL = the offline search, frames NULL = untimed, lm NULL = no LM; V <= 63 with E <= 64 runs the narrow search, any other
+ * shape the wide one (tsasr_beam_search_wide's limits). A NULL descriptor is TSASR_E_INVALID. Workspace: the layout of the same search
+ * without a graph plus one int per tree node: tsasr_beam_search_bias_workspace_bytes = B * (align16(64 + 24 beam) + align16(8 nodes) +
+ * 4 (cap + beam)(J + 2H + (lm_layers > 0 ? (wide ? round_up(V, 4) : 64) + 2 lm_layers lm_hidden : 0)) + (times ? 2 : 1) align16(4 nodes)),
+ * nodes = 1 + (T + 1) beam + cap, wide = V > 63 || E > 64; 0 for a non-positive size. LDS: 4 cap bytes more than the unbiased search. */
+typedef struct tsasr_bias_desc {
+    const int32_t *child_off, *child_tok, *child_to;
+    const double *pending;
+    const int32_t *base;
+    const double *weight;
+    int rows, edges;
+} tsasr_bias_desc;
+size_t tsasr_beam_search_bias_workspace_bytes(int B, int T, int H, int J, int E, int V, int beam, int cap, int lm_layers, int lm_hidden,
+                                              int times);
+int tsasr_beam_search_bias(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                           double lm_weight, const tsasr_bias_desc *bias);
+
 /* ------------------------------------------------------------------------------------------
  * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:
  * 124-334, Kaldi's compute-wer order: the substitution / match only if strictly cheaper than both others, else the deletion if strictly

@@ -27,6 +27,13 @@ like tests/helpers/joint_wide_ref.greedy_net (head scale 1.5, blank bias +3 and 
 [32, --frames, 640] seeded. The device search through the searcher's own call (launch and read-back of the n-best, median of --reps) beside
 the host loop (TSASR_BEAM_KERNEL=0, --host-utts utterances, per utterance), beams --beams; --lm fuses the reference-default RNNLM over V
 symbols into both, --times asks both for the emission frames.
+
+    python tools/beam_bench.py --bias 16 [--lm] [--times] [--vocab 256] [--ab-lib OTHER.so] [--bias-weight 1.0] [--reps 5]
+
+--bias N: contextual biasing (tsasr_beam_search_bias): one graph of N seeded phrases of 3-6 tokens for every utterance; the biased search
+beside the unbiased one through the searcher's own call (launch and read-back of the n-best), the two forms alternating, median of --reps,
+beams --beams; per-utterance time = batch time / 32. --lm fuses the reference-default RNNLM into both, --times asks both for the emission
+frames, --vocab V takes the subword model; --ab-lib: the unbiased search of another build of the library takes part in the same loop.
 """
 import argparse
 import ctypes
@@ -303,6 +310,104 @@ def wide_bench(args):
     return results
 
 
+def bias_bench(args):
+    """--bias N: biased beside unbiased search, device route, per batch; prints one JSON line per dtype and beam."""
+    dec = importlib.import_module("ts-asr_amd.decoders")
+    ops = importlib.import_module("ts-asr_amd.ops")
+    nnet = importlib.import_module("ts-asr_amd.nnet")
+    capi = importlib.import_module("ts-asr_amd._capi")
+    biasing = importlib.import_module("ts-asr_amd.biasing")
+    B, T = 32, args.frames
+    V = args.vocab or 29
+    rng = np.random.default_rng(args.bias)
+    graph = biasing.ContextGraph([rng.integers(1, V, size=int(rng.integers(3, 7))).tolist() for _ in range(args.bias)], args.bias_weight)
+    other = None
+    if args.ab_lib:                                              # the unbiased search of another build, swapped in for its calls
+        other = ctypes.CDLL(os.path.abspath(args.ab_lib))
+        for name, (res, argt) in capi._PROTOS.items():
+            if hasattr(other, name):
+                getattr(other, name).restype, getattr(other, name).argtypes = res, argt
+    results = []
+    for dtype in args.dtypes.split(","):
+        dt = torch.float32 if dtype == "fp32" else torch.bfloat16
+        if args.vocab:
+            sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+            import joint_wide_ref as JW
+            rnnt = importlib.import_module("ts-asr_amd.rnnt")
+            H, J = 512, 640
+            net = {k: torch.from_numpy(v) for k, v in JW.greedy_net(f"beam_bench.v{V}", spec=(V, None, H, J, 1.5)).items()}
+            net["b_head"][0] += args.blank_bias
+            emb = nnet.Embedding(V, consider_as_one_hot=True, blank_id=0)
+            lstm = nnet.LSTM(H, input_size=emb.embedding_dim)
+            lstm.rnn.load_state_dict({"weight_ih_l0": net["w_ih"], "weight_hh_l0": net["w_hh"], "bias_ih_l0": net["b_ih"], "bias_hh_l0": net["b_hh"]})
+            proj, head = nnet.Linear(J, input_size=H), nnet.Linear(V, input_size=J)
+            proj.load_state_dict({"w.weight": net["w_proj"], "w.bias": net["b_proj"]})
+            head.load_state_dict({"w.weight": net["w_head"], "w.bias": net["b_head"]})
+            mods = [m.to("cuda:0").eval() for m in (emb, lstm, proj, head)]
+            nets, joint = (mods[:3], [mods[3]]), rnnt.Transducer_joint()
+            nnet.set_compute_dtype(dt)
+            enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (B, T, J), 1.0)).to("cuda:0", dt)
+        else:
+            brain, h = entry._config1_brain("cuda:0", dtype, joint_dim=640, decoder_neurons=512)
+            brain._setup_dtype()
+            m = brain.modules
+            g = np.load(os.path.join(ROOT, "tests", "golden", "c1_chain_cat.npz"))["enc_proj"]
+            enc = torch.from_numpy(det_tensor("beam_bench.enc_proj", (B, T, 640), float(np.std(g)))).to("cuda:0", dt)
+            with torch.no_grad():
+                m.transducer_head.w.bias[0] += 3.0
+            nets, joint = ([m.embedding, m.decoder, m.decoder_proj], [m.transducer_head]), m.joiner
+        lm = None
+        if args.lm:
+            torch.manual_seed(0)
+            lm = nnet.RNNLM(V, return_hidden=True).to("cuda:0").eval()
+        for beam in (int(b) for b in args.beams.split(",")):
+            s = dec.TransducerBeamSearcher(nets[0], joint, nets[1], blank_id=0, beam_size=beam, nbest=5, lm_module=lm,
+                                           lm_weight=args.lm_weight if lm is not None else 0.0, state_beam=2.3, expand_beam=2.3)
+            kw = {"frames": True} if args.times else {}
+            with torch.no_grad():
+                assert s._device_beam_ok(enc, bias=True)
+                packed = biasing.pack([graph] * B, enc.device)
+                status = {}
+
+                def unbiased_ab():
+                    mine, capi._lib = capi._lib, other
+                    try:
+                        return s._device_beam_call(enc, ops.beam_search, **kw)
+                    finally:
+                        capi._lib = mine
+                forms = {"unbiased": lambda: s._device_beam_call(enc, ops.beam_search, **kw),
+                         "biased": lambda: s._device_beam_call(enc, ops.beam_search, bias=packed, **kw)}
+                if other is not None:
+                    forms["unbiased_ab"] = unbiased_ab
+                names = list(forms)
+                ms = {n: [] for n in names}
+                for n in names:                                  # warm-up
+                    status[n] = forms[n]()[2]
+                torch.cuda.synchronize()
+                for rep in range(args.reps):
+                    order = names[rep % len(names):] + names[:rep % len(names)]
+                    for n in (order if (rep // len(names)) % 2 == 0 else order[::-1]):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        forms[n]()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ms[n].append(e0.elapsed_time(e1))
+            med = {n: float(np.median(v)) for n, v in ms.items()}
+            r = dict(bias=args.bias, bias_weight=args.bias_weight, states=graph.num_states, vocab=V, lm=bool(args.lm), times=bool(args.times),
+                     dtype=dtype, beam=beam, B=B, T=T, reps=args.reps, biased_over_unbiased=round(med["biased"] / med["unbiased"], 4),
+                     biased_ms_per_utt=round(med["biased"] / B, 3), unbiased_ms_per_utt=round(med["unbiased"] / B, 3))
+            for n in names:
+                r[n + "_ms"], r[n + "_min_max_ms"] = round(med[n], 3), [round(min(ms[n]), 3), round(max(ms[n]), 3)]
+                r[n + "_stopped_utts"] = int((status[n] != 0).sum())
+            print(json.dumps(r), flush=True)
+            results.append(r)
+        if not args.vocab:
+            with torch.no_grad():
+                m.transducer_head.w.bias[0] -= 3.0
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -316,7 +421,11 @@ def main():
     ap.add_argument("--lm-weight", type=float, default=0.3)
     ap.add_argument("--vocab", type=int, default=0, help="a subword model of this many symbols (the wide search), with --lm / --times")
     ap.add_argument("--blank-bias", type=float, default=3.0, help="--vocab: added to the head's blank bias beside the seeded net's +3")
+    ap.add_argument("--bias", type=int, default=0, help="time the biased search (this many seeded phrases) beside the unbiased one")
+    ap.add_argument("--bias-weight", type=float, default=1.0)
     args = ap.parse_args()
+    if args.bias:
+        return bias_bench(args)
     if args.vocab:
         return wide_bench(args)
     if args.times:

@@ -22,6 +22,11 @@ Run options and YAML overrides are those of speechbrain.core.parse_arguments (SB
   --lm_ckpt FILE --lm_weight W : the TEST stage's beam search fuses a recurrent LM (decoders.py: LM fusion): FILE is a local state_dict
         of an RNNLM (the reference's keys; torch.save), its shape is read from the tensors; W > 0 is the LM's weight in the score. YAMLs
         that name lm_model / lm_weight themselves need neither option.
+  --bias_file FILE --bias_weight W : contextual biasing of the TEST stage's beam search (ts-asr_amd/biasing.py: a prefix trie of phrases,
+        W > 0 nats per matched token, given back if the phrase is left half-matched). Each line of FILE is one phrase: fields that are all
+        integers are token ids; any other line is text, encoded with the tokenizer's pieces by greedy longest match (a space becomes the
+        boundary piece); a line that cannot be encoded ends the run naming it. Needs a beam_searcher in the YAML; combines with --hyp_ctm
+        and --lm_ckpt.
   --joint_logits lazy : subword vocabularies (32 < V <= 1024): loss and alignment run the fused joint + loss kernels, the [B,T',U+1,V]
         logits / dlogits tensors are never written (hparams key joint_logits: materialized | lazy; default materialized).
 The pretrained-speaker variant is picked from the YAML (conformer-t_wavlm_mi355x.yaml); batches then carry `enroll_emb`."""
@@ -42,7 +47,7 @@ tsasr = importlib.import_module(PKG + ".recipes.tsasr")
 
 EXTRA = {"synthetic": 0, "syn_batch": 8, "syn_seconds": 4.0, "syn_enroll_seconds": 2.0, "syn_tokens": 24, "hip_graph": False,
          "number_of_epochs": 1, "train_json": None, "valid_json": None, "test_json": None, "data_folder": None, "wer_file": None,
-         "align_file": None, "hyp_ctm": None, "lm_ckpt": None, "lm_weight": 0.0}
+         "align_file": None, "hyp_ctm": None, "lm_ckpt": None, "lm_weight": 0.0, "bias_file": None, "bias_weight": 0.0}
 
 
 def load_lm(path, device):
@@ -58,6 +63,17 @@ def load_lm(path, device):
                     dnn_blocks=blocks, dnn_neurons=sd["out.w.weight"].shape[1])
     lm.load_state_dict(sd, strict=True)
     return lm.to(device).eval()
+
+
+def load_bias(path, weight, pieces):
+    """The biasing.ContextGraph of the phrase file ``path`` (module docstring); ``pieces``: the tokenizer's piece texts by id, or None."""
+    biasing = importlib.import_module(PKG + ".biasing")
+    with open(path, encoding="utf-8") as f:
+        lines = f.read().splitlines()
+    try:
+        return biasing.ContextGraph.from_text(lines, pieces if pieces is not None else [], weight)
+    except ValueError as e:
+        raise SystemExit(f"--bias_file {path}: {e}")
 
 
 def synthetic_loader(n_batches, hparams, opts, seed, device):
@@ -132,6 +148,14 @@ def main(argv=None):
         if searcher is None or float(opts["lm_weight"]) <= 0:
             raise SystemExit("--lm_ckpt needs a beam_searcher in the YAML and --lm_weight W with W > 0")
         searcher.lm, searcher.lm_weight = load_lm(str(opts["lm_ckpt"]), brain.device), float(opts["lm_weight"])
+    if opts["bias_file"]:
+        searcher = hparams.get("beam_searcher")
+        if searcher is None or float(opts["bias_weight"]) <= 0:
+            raise SystemExit("--bias_file needs a beam_searcher in the YAML and --bias_weight W with W > 0")
+        try:
+            searcher.bias = load_bias(str(opts["bias_file"]), float(opts["bias_weight"]), getattr(getattr(brain, "tokenizer", None), "pieces", None))
+        except ValueError as e:                                           # a blank or a token outside the vocabulary
+            raise SystemExit(f"--bias_file {opts['bias_file']}: {e}")
     rank = int(os.environ.get("RANK", 0))
     if opts["synthetic"]:
         train = synthetic_loader(int(opts["synthetic"]), hparams, opts, 1234 + 1000 * rank, brain.device)

@@ -170,6 +170,9 @@ _PROTOS = {
     "tsasr_beam_search_wide_workspace_bytes": (c_size_t, [c_int] * 10),
     "tsasr_beam_search_wide": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_double]),
+    "tsasr_beam_search_bias_workspace_bytes": (c_size_t, [c_int] * 11),
+    "tsasr_beam_search_bias": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
     "tsasr_edit_distance_workspace_bytes": (c_size_t, [c_int, c_ll]),
     "tsasr_edit_distance": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_ll] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),
@@ -214,6 +217,12 @@ class LmDesc(ctypes.Structure):
                 ("w_dnn", c_void_p * 2), ("b_dnn", c_void_p * 2), ("ln_g", c_void_p * 2), ("ln_b", c_void_p * 2), ("w_out", c_void_p),
                 ("b_out", c_void_p), ("ln_eps", c_float * 2), ("layers", c_int), ("hidden", c_int), ("emb_dim", c_int), ("dnn_blocks", c_int),
                 ("dnn_neurons", c_int), ("slope", c_float)]
+
+
+class BiasDesc(ctypes.Structure):
+    """tsasr_bias_desc of include/tsasr_hip.h (the packed phrase graphs of tsasr_beam_search_bias), field for field."""
+    _fields_ = [("child_off", c_void_p), ("child_tok", c_void_p), ("child_to", c_void_p), ("pending", c_void_p), ("base", c_void_p),
+                ("weight", c_void_p), ("rows", c_int), ("edges", c_int)]
 
 
 def exported_symbols():

@@ -304,6 +304,15 @@ __global__ __launch_bounds__(SEARCH_THREADS) void greedy_decode_kernel(const Gre
 // scores are those of the untimed form, bit for bit. The frames of a stream are absolute only if its header was zeroed as a whole at the
 // start: the stream form takes "frames decoded so far" from hdr[4] whether or not the stream is primed, so hdr[0] == 0 over a stale
 // hdr[4] would shift every frame of the stream by that stale count (the untimed form only ever adds to the word).
+//
+// Contextual biasing (tsasr_beam_search_bias; the BIAS instantiations, whose arguments alone carry BeamBiasArgs): a prefix trie of phrases per utterance in CSR form
+// (child_off / child_tok / child_to / pending, states relative to the utterance's own graph at row base[b]) and one trie state per
+// hypothesis: Actx beside Afrm in LDS, nctx[node] in the workspace after the node-frame array (align16(4 * nodes) bytes more per
+// utterance), written at promotion beside nfrm. A non-blank extension by sym moves the state (beam_bias_step: a binary search over the
+// state's child_tok by the appending thread) and adds d last, one __dadd_rn: +w for a matched token, -pending[s] for a match given up
+// (+w again if sym opens a phrase at the root). The n-best read-out ranks and reports (logp - pending[state]) / len, the stored beam keeps
+// logp as it is, so pieces give the bits of one call. No failure links: a failed match restarts at the root with the current token only.
+// base[b] < 0: utterance b is not biased (its scores are those of the plain search, bit for bit).
 constexpr int BEAM_MAXK = 64;            // beam_size <= min(V, 64), nbest <= 64
 
 struct BeamEnt {
@@ -330,9 +339,36 @@ __host__ __device__ inline BeamLayout beam_layout(int T, int H, int J, int beam,
 __host__ __device__ inline int beam_lm_slot_floats(bool wide, int V, int layers, int hidden) {
     return (wide ? round4(V) : 64) + 2 * layers * hidden;
 }
-// TIMES: the node-frame array (one int per tree node) follows the untimed layout of each utterance
-__host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times) {
-    return L.per_utt + (times ? beam_align16(sizeof(int) * (size_t)L.nn) : 0);
+// TIMES: the node-frame array (one int per tree node) follows the untimed layout of each utterance; bias: then the node-state array
+__host__ __device__ inline size_t beam_per_utt(const BeamLayout &L, bool times, bool bias = false) {
+    return L.per_utt + ((times ? 1 : 0) + (bias ? 1 : 0)) * beam_align16(sizeof(int) * (size_t)L.nn);
+}
+
+struct BeamBiasArgs {
+    const int *child_off, *child_tok, *child_to;   // CSR over the packed rows; child_off holds absolute edge indices
+    const double *pending;                          // [rows] bonus a half-matched phrase would have to give back
+    const int *base;                                // [B] first row of the utterance's graph (< 0: none)
+    const double *weight;                           // [B] nats per matched token
+    int rows;
+};
+
+// step(s, v) of the graph at row gb: the child of s on v, else the root's child on v, else the root
+__device__ __forceinline__ int beam_bias_child(const BeamBiasArgs &G, int row, int v) {
+    int lo = G.child_off[row], hi = G.child_off[row + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1, t = G.child_tok[mid];
+        if (t == v) return G.child_to[mid];
+        if (t < v) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+}
+__device__ __forceinline__ int beam_bias_step(const BeamBiasArgs &G, int gb, double w, int s, int v, double &d) {
+    int c = beam_bias_child(G, gb + s, v);
+    if (c >= 0) { d = w; return c; }
+    d = -G.pending[gb + s];
+    c = beam_bias_child(G, gb, v);
+    if (c >= 0) { d = __dadd_rn(d, w); return c; }
+    return 0;
 }
 
 struct BeamArgs {
@@ -368,8 +404,10 @@ struct BeamLmArgs {
     float slope;
     double weight;
 };
-template <bool LM> struct BeamKernArgs : BeamArgs {};
-template <> struct BeamKernArgs<true> : BeamArgs { BeamLmArgs lm; };
+template <bool LM, bool BIAS = false> struct BeamKernArgs : BeamArgs {};
+template <> struct BeamKernArgs<true, false> : BeamArgs { BeamLmArgs lm; };
+template <> struct BeamKernArgs<false, true> : BeamArgs { BeamBiasArgs bias; };
+template <> struct BeamKernArgs<true, true> : BeamArgs { BeamLmArgs lm; BeamBiasArgs bias; };
 
 template <typename P> __device__ __forceinline__ P beam_pick4(const P (&a)[4], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
 
@@ -492,8 +530,8 @@ __device__ __forceinline__ void beam_topk_pick(float &k, int &i, float k2, int i
 //   - the appends: by thread 0 behind a barrier instead of by lane 0 of wave 0 behind a wave fence.
 // Dynamic LDS: h | c | pn | z | gates | x[Ep] | lg[Vp] | WIDE: red[96] | A arrays (cap) | LM: lx | lh | lgt | llg[Vp] | s_lmlp[Vp] |
 // s_stat[2], Ep = Vp = 64 unless WIDE; red = wave maxima[16] | wave sums[16] | top-k wave values[2][16] | top-k wave indices[2][16].
-template <typename T, typename WT, bool TIMES, bool LM, bool WIDE>
-__global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamKernArgs<LM> A) {
+template <typename T, typename WT, bool TIMES, bool LM, bool WIDE, bool BIAS>
+__global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamKernArgs<LM, BIAS> A) {
     extern __shared__ __attribute__((aligned(16))) float bsm[];
     const int H = A.H, J = A.J, cap = A.cap;
     const int Ep = WIDE ? round4(A.E) : 64, Vp = WIDE ? round4(A.V) : 64;
@@ -503,12 +541,14 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
     int *Apar = reinterpret_cast<int *>(Akey + cap), *Atok = Apar + cap, *Alen = Atok + cap, *Aslot = Alen + cap, *Anode = Aslot + cap,
         *Aflag = Anode + cap;                               // flag bit 0: live in A, bit 1: on a path of the closing beam
     int *Afrm = Aflag + cap;                                 // TIMES: frame at which the extension was appended (cap ints more of LDS)
+    constexpr bool biased = BIAS;
+    int *Actx = Aflag + cap + (TIMES ? cap : 0);             // bias: trie state of the hypothesis (cap ints more of LDS)
     // LM: the LM step's own LDS after the A arrays: lx[max(E, Hl, D)] | lh[2 Hl] | lgt[max(4 Hl, D)] | llg[Vp] (beam_lm_step) |
     // s_lmlp[Vp] (lm_logp of the node being expanded) | s_stat[2] (LayerNorm mean, rstd)
     float *lx = nullptr, *lh = nullptr, *lgt = nullptr, *llg = nullptr, *s_lmlp = nullptr, *s_stat = nullptr;
     int lmw = 0;
     if constexpr (LM) {
-        lx = reinterpret_cast<float *>(Aflag + cap + (TIMES ? cap : 0));
+        lx = reinterpret_cast<float *>(Aflag + cap + (TIMES ? cap : 0) + (biased ? cap : 0));
         lh = lx + max(max(A.lm.E, A.lm.Hl), A.lm.D);
         lgt = lh + 2 * A.lm.Hl;
         llg = lgt + max(4 * A.lm.Hl, A.lm.D);
@@ -524,12 +564,20 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
     __shared__ int s_ctl[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const BeamLayout L = beam_layout(A.max_frames, H, J, A.beam, cap, lmw);
-    unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES);
+    unsigned char *wsu = A.ws + (size_t)b * beam_per_utt(L, TIMES, biased);
     int *hdr = reinterpret_cast<int *>(wsu);
     BeamEnt *bent = reinterpret_cast<BeamEnt *>(wsu + 64);
     int2 *tree = reinterpret_cast<int2 *>(wsu + L.hdr);
     float *slots = reinterpret_cast<float *>(wsu + L.hdr + L.tree);
     int *nfrm = reinterpret_cast<int *>(wsu + L.per_utt);   // TIMES: nfrm[node] = emission frame of the node's token
+    int *nctx = reinterpret_cast<int *>(wsu + beam_per_utt(L, TIMES));   // bias: nctx[node] = trie state of the node's path
+    int gb = -1;                                             // bias: first row of this utterance's graph (< 0: not biased)
+    double bw = 0.0;
+    if constexpr (BIAS) {
+        gb = A.bias.base[b];
+        if (gb < 0 || gb + 1 >= A.bias.rows) gb = -1;       // (a graph holds at least its root's row and the closing one)
+        else bw = A.bias.weight[b];
+    }
     const int SWP = J + 2 * H;                               // floats per slot: pn | h | c
     const int SW = SWP + lmw;                                // LM: | lm_logp[Vp] | lm_h | lm_c
     const T *enc = (const T *)A.enc + (size_t)b * A.T * J;
@@ -562,10 +610,14 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
         Aslot[tid] = e.slot;
         Anode[tid] = e.node;
         Aflag[tid] = 1;
+        if (biased) Actx[tid] = primed ? nctx[e.node] : 0;
     }
     __syncthreads();
     const bool run = s_ctl[4] == 0 && tend > 0;              // workgroup-uniform
-    if (run && !primed && tid == 0) tree[0] = make_int2(A.blank, -1);
+    if (run && !primed && tid == 0) {
+        tree[0] = make_int2(A.blank, -1);
+        if (biased) nctx[0] = 0;
+    }
 
     for (int t = 0; run && t < tend; ++t) {
         if (tid == 0) { s_ctl[0] = s_ctl[5]; s_ctl[1] = 0; s_ctl[6] = 0; s_ctl[3] = 0; }
@@ -658,6 +710,15 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
                         if (nA >= cap) { s_ctl[4] = 1; s_ctl[11] = 1; break; }
                         double sx = sc;                      // LM: (alp + joint) + weight * lm, a product and a sum (no fused multiply-add)
                         if constexpr (LM) sx = __dadd_rn(sc, __dmul_rn(A.lm.weight, (double)s_lmlp[sym]));
+                        if constexpr (BIAS) {                // the trie step of a's state on sym; its bonus comes last
+                            int cs = 0;
+                            if (gb >= 0) {
+                                double d;
+                                cs = beam_bias_step(A.bias, gb, bw, Actx[a], sym, d);
+                                sx = __dadd_rn(sx, d);
+                            }
+                            Actx[nA] = cs;
+                        }
                         Alp[nA] = sx;
                         Akey[nA] = sx / (double)(alen + 1);
                         Apar[nA] = a;
@@ -752,15 +813,18 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
                 if (Aflag[i] & 2) {
                     tree[Anode[i]] = make_int2(Atok[i], Anode[Apar[i]]);
                     if (TIMES) nfrm[Anode[i]] = Afrm[i];
+                    if (biased) nctx[Anode[i]] = Actx[i];
                 }
             if (lane == 0) s_ctl[7] = base;
         }
         __syncthreads();
         BeamEnt ne{};
+        int nc = 0;
         const int nb = s_ctl[1];
         if (tid < nb) {
             const int e = s_bidx[tid];
             ne = BeamEnt{s_blp[tid], Anode[e], Alen[e], Aslot[e], Atok[e]};
+            if (biased) nc = Actx[e];
         }
         __syncthreads();
         if (tid < nb) {
@@ -772,6 +836,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
             Aslot[tid] = ne.slot;
             Anode[tid] = ne.node;
             Aflag[tid] = 1;
+            if (biased) Actx[tid] = nc;
         }
         if (tid == 0) s_ctl[5] = nb;
         __syncthreads();
@@ -790,6 +855,10 @@ __global__ __launch_bounds__(SEARCH_THREADS) void beam_search_kernel(const BeamK
         }
         A.status[b] = st;
         // n-best: sorted(beam, key=logp/len, reverse=True)[:nbest], stable -> repeated first-maximum selection
+        // bias: ranked and reported with the bonus of a half-matched phrase given back (Alp, the stored beam, keeps it)
+        if constexpr (BIAS)
+            if (gb >= 0 && st == 0)
+                for (int j = 0; j < nbeam; ++j) Akey[j] = __dsub_rn(Alp[j], A.bias.pending[gb + Actx[j]]) / (double)Alen[j];
         for (int r = 0; r < A.nbest; ++r) {
             int best = -1;
             if (st == 0)
@@ -909,9 +978,9 @@ size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, i
     return (size_t)B * beam_layout(T, H, J, beam, cap).per_utt;
 }
 
-static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times, int lmw = 0) {
+static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times, int lmw = 0, bool bias = false) {
     if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
-    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap, lmw), times);
+    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap, lmw), times, bias);
 }
 
 /* The LM-fused search's workspace: every slot also holds lm_logp[64] | lm_h | lm_c (64 + 2 lm_layers lm_hidden floats); times != 0: the
@@ -951,7 +1020,7 @@ static int beam_launch(const char *name, bool wide, const void *enc, const NetAr
                        const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores, int *status, int B, int T,
                        int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
                        double expand_beam, float slope, int io_dtype, int wdtype, void *stream, const tsasr_lm_desc *lm = nullptr,
-                       double lm_weight = 0.0) {
+                       double lm_weight = 0.0, const tsasr_bias_desc *bias = nullptr) {
     TSASR_CHECK_ARG(enc && net.emb && net.w_ih && net.w_hh && net.w_proj && net.w_head && workspace && hyps && lens && scores && status &&
                     (frames || !times), "%s: null pointer", name);
     TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= (wide ? 1024 : 64) && V > 1 &&
@@ -969,21 +1038,30 @@ static int beam_launch(const char *name, bool wide, const void *enc, const NetAr
         lm_lds = (size_t)(std::max(std::max(m.E, m.Hl), m.D) + 2 * m.Hl + std::max(4 * m.Hl, m.D) + 2 * Vp + 2) * sizeof(float);
     }
     const int lmw = lm ? beam_lm_slot_floats(wide, V, lm->layers, lm->hidden) : 0;
-    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw);
+    BeamBiasArgs g{};
+    if (bias) {
+        TSASR_CHECK_ARG(bias->child_off && bias->child_tok && bias->child_to && bias->pending && bias->base && bias->weight,
+                        "%s: null bias pointer", name);
+        TSASR_CHECK_ARG(bias->rows >= 1 && bias->edges >= 0, "%s: bad bias sizes (rows=%d edges=%d)", name, bias->rows, bias->edges);
+        g = BeamBiasArgs{bias->child_off, bias->child_tok, bias->child_to, bias->pending, bias->base, bias->weight, bias->rows};
+    }
+    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw, bias != nullptr);
     TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
     // dynamic LDS (the kernel's comment); wide: + 4 KB for its static arrays (the beam's and the top-k's, 2.4 KB) within the CU's 160 KB
     const size_t lds = (size_t)(6 * H + 2 * J + Ep + Vp + (wide ? 96 : 0)) * sizeof(float) +
-                       (size_t)cap * (2 * sizeof(double) + (times ? 7 : 6) * sizeof(int)) + lm_lds;
+                       (size_t)cap * (2 * sizeof(double) + ((times ? 7 : 6) + (bias ? 1 : 0)) * sizeof(int)) + lm_lds;
     if (wide) TSASR_CHECK_ARG(lds + 4096 <= 160 * 1024, "%s: H=%d J=%d E=%d V=%d cap=%d need %zu B of LDS", name, H, J, E, V, cap, lds);
     else TSASR_CHECK_ARG(lds <= 152 * 1024, "%s: H=%d J=%d cap=%d need %zu B of LDS", name, H, J, cap, lds);
     const BeamArgs a{enc, net, (unsigned char *)workspace, n_valid, hyps, lens, scores, status, B, T, J, H, E, V, blank, beam, nbest, cap,
                      Lmax, max_frames, state_beam, expand_beam, slope, frames};
-#define BEAM_KERN(TT, WW, LM) (wide ? (times ? beam_search_kernel<TT, WW, true, LM, true> : beam_search_kernel<TT, WW, false, LM, true>) \
-                                    : (times ? beam_search_kernel<TT, WW, true, LM, false> : beam_search_kernel<TT, WW, false, LM, false>))
-#define BEAM(TT, WW)                                                                              \
-    {                                                                                             \
-        if (lm) search_launch(BEAM_KERN(TT, WW, true), B, lds, stream, BeamKernArgs<true>{a, m}); \
-        else search_launch(BEAM_KERN(TT, WW, false), B, lds, stream, BeamKernArgs<false>{a});     \
+#define BEAM_KERN(TT, WW, LM, BS) (wide ? (times ? beam_search_kernel<TT, WW, true, LM, true, BS> : beam_search_kernel<TT, WW, false, LM, true, BS>) \
+                                        : (times ? beam_search_kernel<TT, WW, true, LM, false, BS> : beam_search_kernel<TT, WW, false, LM, false, BS>))
+#define BEAM(TT, WW)                                                                                                      \
+    {                                                                                                                     \
+        if (lm && bias) search_launch(BEAM_KERN(TT, WW, true, true), B, lds, stream, BeamKernArgs<true, true>{a, m, g});  \
+        else if (bias) search_launch(BEAM_KERN(TT, WW, false, true), B, lds, stream, BeamKernArgs<false, true>{a, g});    \
+        else if (lm) search_launch(BEAM_KERN(TT, WW, true, false), B, lds, stream, BeamKernArgs<true, false>{a, m});      \
+        else search_launch(BEAM_KERN(TT, WW, false, false), B, lds, stream, BeamKernArgs<false, false>{a});               \
     }
     SEARCH_DTYPES(io_dtype, wdtype, BEAM)
 #undef BEAM
@@ -1082,6 +1160,30 @@ int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, 
     return beam_launch("tsasr_beam_search_wide", true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
                        n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
                        Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
+}
+
+/* The biased search's workspace (see BeamBiasArgs): the layout of the same search without a graph - narrow for V <= 63 and E <= 64, wide
+ * otherwise; lm_layers 0: no LM; times != 0: the timed layout - plus one int per tree node, the trie state of the node's path. */
+size_t tsasr_beam_search_bias_workspace_bytes(int B, int T, int H, int J, int E, int V, int beam, int cap, int lm_layers, int lm_hidden,
+                                              int times) {
+    if (E <= 0 || V <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
+    const bool wide = V > 63 || E > 64;
+    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_lm_slot_floats(wide, V, lm_layers, lm_hidden) : 0, true);
+}
+
+/* Beam search with contextual biasing: tsasr_beam_search_lm's arguments, then the packed phrase graphs. n_valid NULL: the offline search;
+ * frames NULL: untimed; lm NULL: no LM fusion (lm_weight is then not read). V <= 63 with E <= 64 runs the narrow instantiation, every
+ * other shape the wide one with its limits. bias NULL is an argument error: a search without a graph takes the entry points above. */
+int tsasr_beam_search_bias(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
+                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
+                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
+                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
+                           double lm_weight, const tsasr_bias_desc *bias) {
+    TSASR_CHECK_ARG(bias, "tsasr_beam_search_bias: null bias");
+    return beam_launch("tsasr_beam_search_bias", V > 63 || E > 64, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
+                       workspace_bytes, n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank,
+                       beam, nbest, cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight, bias);
 }
 
 }  // extern "C"

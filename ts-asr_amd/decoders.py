@@ -23,6 +23,12 @@ emitted token i, absolute from the start of the utterance or stream. Greedy emit
 token's column in the kernel's ``preds``; the beam search never merges paths, so each hypothesis carries one frame list (the device
 search records it per tree node, tsasr_beam_search_timed; the host loop carries it with the hypothesis). Seconds and word spans:
 align.frame_seconds / align.word_spans.
+
+Contextual biasing (``bias``: a biasing.ContextGraph for every utterance, or a list of B entries, each a graph or None; biasing.py
+states the rule): a hypothesis also carries a trie state, 0 at the start; a blank copy keeps it; a non-blank extension by sym moves it
+(graph.step) and adds the step's bonus d last, after the joint's and the LM's terms; the n-best is ranked and reported with
+(logp - pending[state]) / len while the beam itself keeps logp. The host loop below is the definition; the device search carries the
+state per tree node (tsasr_beam_search_bias). With no graph (None, an empty graph, a list of them) every call is today's.
 """
 import os
 import warnings
@@ -34,11 +40,12 @@ GREEDY_WIDE_MAX = 1024          # vocabulary and embedding columns the device gr
 BEAM_CAP = 512                  # hypotheses one frame of the device beam search may hold (its A list); past it: the host loop
 BEAM_STREAM_FRAMES = 4096       # frames a beam_stream workspace is laid out for when the caller does not say
 BEAM_HOST_REDECODES = {"utterances": 0}     # utterances the device beam search handed back to the host loop (status != 0)
+_NO_GRAPH_YET = object()        # beam_stream: a stream of a biased state whose graph has not been named since its (re)start
 
 
 class TransducerBeamSearcher(torch.nn.Module):
     def __init__(self, decode_network_lst, tjoint, classifier_network, blank_id, beam_size=4, nbest=5, lm_module=None,
-                 lm_weight=0.0, state_beam=2.3, expand_beam=2.3, cap=BEAM_CAP):
+                 lm_weight=0.0, state_beam=2.3, expand_beam=2.3, cap=BEAM_CAP, bias=None):
         super().__init__()
         self.decode_network_lst, self.tjoint, self.classifier_network = decode_network_lst, tjoint, classifier_network
         self.blank_id, self.beam_size, self.nbest = blank_id, beam_size, nbest
@@ -47,19 +54,60 @@ class TransducerBeamSearcher(torch.nn.Module):
         self.lm, self.lm_weight = lm_module, lm_weight
         if lm_module is None and lm_weight > 0:
             raise ValueError("Language model is not provided.")
+        self.bias = bias
 
-    def forward(self, tn_output):
+    @property
+    def bias(self):
+        """The phrase graphs of the beam search (biasing.py): None, one ContextGraph for every utterance, or a list with one entry
+        (a graph or None) per utterance of the batches to come. Set like ``lm``; ``forward(..., bias=)`` overrides it for a call."""
+        return self._bias
+
+    @bias.setter
+    def bias(self, value):
+        self._check_bias(value)
+        self._bias = value
+
+    def _vocab(self):
+        head = self.classifier_network[0] if len(self.classifier_network) else None
+        lin = getattr(head, "w", head)
+        return getattr(lin, "out_features", None)
+
+    def _check_bias(self, bias):
+        from .biasing import ContextGraph
+        if bias is None:
+            return
+        for g in ([bias] if isinstance(bias, ContextGraph) else list(bias)):
+            if g is not None:
+                if not isinstance(g, ContextGraph):
+                    raise ValueError("bias must be a biasing.ContextGraph or a list whose entries are ContextGraph or None")
+                g.check(self.blank_id, self._vocab())
+
+    def _bias_graphs(self, bias, B):
+        """The call's graphs as a list of B entries (a graph or None), checked against the blank and the vocabulary; None if no utterance
+        is biased."""
+        from .biasing import as_list
+        self._check_bias(bias)
+        graphs = as_list(bias, B)
+        return graphs if any(g is not None for g in graphs) else None
+
+    def forward(self, tn_output, bias=None):
+        bias = self.bias if bias is None else bias
         if self.beam_size <= 1:
-            return self.transducer_greedy_decode(tn_output)
-        return self.transducer_beam_search_decode(tn_output)
+            return self.transducer_greedy_decode(tn_output)           # (greedy search is not biased)
+        if bias is None:
+            return self.transducer_beam_search_decode(tn_output)
+        return self.transducer_beam_search_decode(tn_output, bias=bias)
 
-    def forward_timed(self, tn_output):
+    def forward_timed(self, tn_output, bias=None):
         """forward's four values (the same lists, the same score bits) and then ``frames`` and ``nbest_frames``: frames[b][i] is the
         encoder frame that emitted hyps[b][i], nbest_frames[b][r][i] that of nbest_hyps[b][r][i] (None for greedy). Every frame of
         tn_output is decoded, padding included, so a frame may lie past an utterance's valid length."""
+        bias = self.bias if bias is None else bias
         if self.beam_size <= 1:
             return self.transducer_greedy_decode(tn_output, timed=True)
-        return self.transducer_beam_search_decode(tn_output, timed=True)
+        if bias is None:
+            return self.transducer_beam_search_decode(tn_output, timed=True)
+        return self.transducer_beam_search_decode(tn_output, timed=True, bias=bias)
 
     @staticmethod
     def _unpack_preds(preds, base=None):
@@ -95,7 +143,7 @@ class TransducerBeamSearcher(torch.nn.Module):
     def _greedy_is_wide(self):
         return self.decode_network_lst[0].embedding_dim > 64 or self.classifier_network[0].w.out_features > 63
 
-    def _device_beam_ok(self, tn_output):
+    def _device_beam_ok(self, tn_output, bias=False):
         """The one-launch device beam search (csrc/search.hip) takes the networks the greedy decoder takes, with 2 <= beam_size <= V,
         nbest <= 64 and cap >= beam_size; subword models (_beam_is_wide) also need beam_size <= 64 and a shape whose search fits the
         kernel's LDS. TSASR_BEAM_KERNEL=0 sends every call to the host loop."""
@@ -111,7 +159,7 @@ class TransducerBeamSearcher(torch.nn.Module):
             lm_rnn = self.lm.rnn.rnn if self.lm_weight > 0 else None
             lm_dims = (self.lm.embedding.embedding_dim, lm_rnn.hidden_size, self.lm.out.w.in_features) if lm_rnn is not None else None
             ok = self.beam_size <= 64 and ops.beam_wide_lds_bytes(rnn.hidden_size, tn_output.shape[-1], self.decode_network_lst[0].embedding_dim,
-                                                                  V, self.cap, lm_dims) <= ops.BEAM_WIDE_LDS_MAX
+                                                                  V, self.cap, lm_dims, bias=bool(bias)) <= ops.BEAM_WIDE_LDS_MAX
         return ok
 
     def _beam_is_wide(self):
@@ -296,7 +344,7 @@ class TransducerBeamSearcher(torch.nn.Module):
         return hyps, logp_sum.exp().mean(), None, None
 
     @torch.no_grad()
-    def transducer_beam_search_decode(self, tn_output, timed=False):
+    def transducer_beam_search_decode(self, tn_output, timed=False, bias=None):
         """Returns (best hyps, mean exp(normalised score), n-best hyps, n-best normalised log-scores) like the reference.
         A = hypotheses still to be extended at this frame, B = those that emitted blank here (the next frame's A). Until
         |B| >= beam: take the best a in A by logp / len(prediction); stop once the best b in B has logp >= state_beam + logp(a);
@@ -304,21 +352,29 @@ class TransducerBeamSearcher(torch.nn.Module):
         a into B, a non-blank symbol within expand_beam of the best non-blank extends a (new predictor state) back into A.
         The recipes' networks run on the device (_device_beam_ok); an utterance the device search could not finish within ``cap``
         hypotheses per frame is decoded again by the host loop (counted in BEAM_HOST_REDECODES). ``timed`` (forward_timed): two more
-        values, the best hypotheses' emission frames and the n-best's."""
+        values, the best hypotheses' emission frames and the n-best's. ``bias``: the call's phrase graphs (biasing.py)."""
+        graphs = self._bias_graphs(bias, tn_output.shape[0]) if bias is not None else None
+        if graphs is not None:
+            if self._device_beam_ok(tn_output, bias=True):
+                return self._beam_on_device(tn_output, timed=timed, graphs=graphs)
+            return self._beam_host_loop(tn_output, timed, graphs)
         if self._device_beam_ok(tn_output):
             # (the untimed call keeps its one-argument form: callers and tests wrap _beam_on_device(tn_output))
             return self._beam_on_device(tn_output, timed=True) if timed else self._beam_on_device(tn_output)
         return self._beam_host_loop(tn_output, timed)
 
-    def _beam_host_loop(self, tn_output, timed=False):
+    def _beam_host_loop(self, tn_output, timed=False, graphs=None):
+        """``graphs``: None, or one entry per utterance (a ContextGraph or None); with it every hypothesis carries a trie state."""
         nbest_batch, nbest_scores, nbest_frames = [], [], []
+        biased = graphs is not None
         for b in range(tn_output.shape[0]):
             # (prediction incl. the blank prefix, logp, predictor state); timed: + the emission frames of the prediction's tokens;
-            # LM fusion: + the LM's state, last
-            beam = [self._beam_start(timed)]
+            # biased: + the trie state; LM fusion: + the LM's state, last
+            g = graphs[b] if biased else None
+            beam = [self._beam_start(timed, biased)]
             for t in range(tn_output.shape[1]):
-                beam = self._beam_frame(beam, tn_output[b, t, :], t if timed else None)
-            ranked = self._beam_rank(beam, timed)
+                beam = self._beam_frame(beam, tn_output[b, t, :], t if timed else None, g, biased)
+            ranked = self._beam_rank(beam, timed, g, biased)
             nbest_batch.append(ranked[0])
             nbest_scores.append(ranked[1])
             if timed:
@@ -327,16 +383,19 @@ class TransducerBeamSearcher(torch.nn.Module):
         out = best, torch.tensor([s_[0] for s_ in nbest_scores]).exp().mean(), nbest_batch, nbest_scores
         return out + ([n[0] for n in nbest_frames], nbest_frames) if timed else out
 
-    def _beam_start(self, timed=False):
-        """The hypothesis a search starts from: ([blank], 0.0, no predictor state) + ([] if timed) + (no LM state if the LM is used)."""
-        return ([self.blank_id], 0.0, None) + (([],) if timed else ()) + ((None,) if self.lm_weight > 0 else ())
+    def _beam_start(self, timed=False, biased=False):
+        """The hypothesis a search starts from: ([blank], 0.0, no predictor state) + ([] if timed) + (trie state 0 if biased) + (no LM
+        state if the LM is used)."""
+        return ([self.blank_id], 0.0, None) + (([],) if timed else ()) + ((0,) if biased else ()) + ((None,) if self.lm_weight > 0 else ())
 
-    def _beam_frame(self, A, enc_t, t=None):
+    def _beam_frame(self, A, enc_t, t=None, graph=None, biased=False):
         """One frame of the host loop: the beam that leaves frame ``enc_t`` [J] when ``A`` enters it. ``t`` (not None: the hypotheses
-        carry their frame lists at index 3) = absolute index of this frame, recorded for every token emitted here. With the LM in use
-        the last element of a hypothesis is its LM state."""
+        carry their frame lists at index 3) = absolute index of this frame, recorded for every token emitted here. ``biased``: the
+        hypotheses carry a trie state behind the frames (index 3, timed: 4), moved by ``graph`` (None: this utterance has no graph, the
+        state stays 0 and nothing is added). With the LM in use the last element of a hypothesis is its LM state."""
         key = lambda hyp: hyp[1] / len(hyp[0])  # noqa: E731
         use_lm = self.lm_weight > 0
+        ci = 3 if t is None else 4
         dev = enc_t.device
         frame = enc_t.view(1, 1, 1, -1)
         beam = []
@@ -361,14 +420,24 @@ class TransducerBeamSearcher(torch.nn.Module):
                     beam.append((a[0][:], a[1] + lp, a[2]) + a[3:])
                 elif lp >= best_nonblank - self.expand_beam:
                     sc = (a[1] + lp) + self.lm_weight * lm_logp[sym] if use_lm else a[1] + lp
-                    A.append((a[0] + [sym], sc, new_state) + (() if t is None else (a[3] + [t],)) + ((lm_state,) if use_lm else ()))
+                    ctx = ()
+                    if biased:
+                        ctx = (0,)
+                        if graph is not None:                # the trie step of a's state on sym; its bonus comes last
+                            cs, d = graph.step(a[ci], sym)
+                            sc, ctx = sc + d, (cs,)
+                    A.append((a[0] + [sym], sc, new_state) + (() if t is None else (a[3] + [t],)) + ctx + ((lm_state,) if use_lm else ()))
         return beam
 
-    def _beam_rank(self, beam, timed=False):
+    def _beam_rank(self, beam, timed=False, graph=None, biased=False):
         """(n-best symbol lists, their logp / len) of a beam: sorted(beam, key, reverse=True)[:nbest] (stable, as the reference);
-        ``timed``: and their frame lists."""
-        ranked = sorted(beam, key=lambda hyp: hyp[1] / len(hyp[0]), reverse=True)[: self.nbest]
-        out = [h[0][1:] for h in ranked], [h[1] / len(h[0]) for h in ranked]
+        ``timed``: and their frame lists. ``graph``: ranked and reported with (logp - pending[state]) / len, a phrase left half-matched
+        earns nothing; the beam itself is left as it is."""
+        ci = 4 if timed else 3
+        key = (lambda hyp: (hyp[1] - float(graph.pending[hyp[ci]])) / len(hyp[0])) if biased and graph is not None else (
+            lambda hyp: hyp[1] / len(hyp[0]))
+        ranked = sorted(beam, key=key, reverse=True)[: self.nbest]
+        out = [h[0][1:] for h in ranked], [key(h) for h in ranked]
         return out + ([list(h[3]) for h in ranked],) if timed else out
 
     def _device_beam_call(self, enc, fn, *extra, **kw):
@@ -381,10 +450,15 @@ class TransducerBeamSearcher(torch.nn.Module):
                   self.nbest, self.state_beam, self.expand_beam, self.cap, *extra, **kw)
 
     @torch.no_grad()
-    def _beam_on_device(self, tn_output, timed=False):
+    def _beam_on_device(self, tn_output, timed=False, graphs=None):
         from . import ops
         enc = tn_output.contiguous()
-        if timed:
+        if graphs is not None:
+            from .biasing import pack
+            out = self._device_beam_call(enc, ops.beam_search, frames=bool(timed), bias=pack(graphs, enc.device))
+            nbest_batch, nbest_scores, status = out[:3]
+            nbest_frames = out[3] if timed else None
+        elif timed:
             nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search, frames=True)
         else:
             nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search)
@@ -396,7 +470,7 @@ class TransducerBeamSearcher(torch.nn.Module):
                               f"loop (counted in decoders.BEAM_HOST_REDECODES)", RuntimeWarning, stacklevel=3)
             BEAM_HOST_REDECODES["utterances"] += len(bad)
             for b in bad:
-                redo = self._beam_host_loop(enc[b:b + 1], timed)
+                redo = self._beam_host_loop(enc[b:b + 1], timed, None if graphs is None else [graphs[b]])
                 nbest_batch[b], nbest_scores[b] = redo[2][0], redo[3][0]
                 if timed:
                     nbest_frames[b] = redo[5][0]
@@ -408,16 +482,19 @@ class TransducerBeamSearcher(torch.nn.Module):
     def reset_streams(self, state, slots):
         """Put the streams ``slots`` (indices into the batch) of a greedy_stream / beam_stream state back to the start of a stream, in
         place; every other stream keeps its bits. Device greedy: the slot's row of the [B, 2H+J+4] state and its frames_done are zeroed.
-        Device beam: the slot's block of the workspace (B equal blocks, untimed, timed, LM and wide layouts alike) is zeroed, which
-        also clears a sticky status. Host routes: the slot's predictor state / beam list starts afresh. ``state`` None (no call made
+        Device beam: the slot's block of the workspace (B equal blocks, untimed, timed, LM, wide and biased layouts alike) is zeroed,
+        which also clears a sticky status; a biased state also forgets the slot's graph. Host routes: the slot's predictor state / beam list starts afresh. ``state`` None (no call made
         yet: every stream is at its start) is returned as it is."""
         if state is None:
             return state
         slots = [int(b) for b in slots]
+        if "graphs" in state:                                  # biased beam search: the streams' graphs are forgotten
+            for b in slots:
+                state["graphs"][b] = _NO_GRAPH_YET
         if "beams" in state:                                   # beam search, host route
             timed = "frames_done" in state
             for b in slots:
-                state["beams"][b] = [self._beam_start(timed)]
+                state["beams"][b] = [self._beam_start(timed, "graphs" in state)]
                 if timed:
                     state["frames_done"][b] = 0
         elif "tok" in state:                                   # greedy search, host route
@@ -448,7 +525,7 @@ class TransducerBeamSearcher(torch.nn.Module):
                 state["frames"][b] = [[]]
         return state
 
-    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None, return_frames=False, raise_stopped=True):
+    def beam_stream(self, enc_chunk, state=None, n_valid=None, max_frames=None, return_frames=False, raise_stopped=True, bias=None):
         """Beam search over the next frames of a batch of streams, the counterpart of greedy_stream: enc_chunk [B,C,J], ``state`` the
         value returned by the previous call (None: start of the streams), n_valid int32 [B] = frames of this chunk that belong to each
         stream (None: all C); max_frames = frames a stream may reach (device route; default BEAM_STREAM_FRAMES), read at the first call.
@@ -460,7 +537,12 @@ class TransducerBeamSearcher(torch.nn.Module):
         match state["nbest"]. The flag is fixed at the first call of a stream (the timed device workspace has its own layout, the
         host hypotheses carry their frames): a later call with the other value raises ValueError.
         raise_stopped=False (device route): stopped streams do not raise; the state is stored for every stream and state["stopped"]
-        lists them (a stopped stream stays stopped until reset_streams)."""
+        lists them (a stopped stream stays stopped until reset_streams).
+        bias (biasing.py; one ContextGraph or a list of B entries, each a graph or None): read at the first call of a state, where any
+        value but None selects the biased layout for good (the device workspace holds a trie state per node, the host hypotheses carry
+        theirs), also a list of None. The state remembers each stream's graph by identity: a later call names the same graphs or passes
+        None (= as before); another graph for a stream that has not been reset raises ValueError. reset_streams forgets the graph of the
+        streams it restarts, the next call names their new one (None again: no graph)."""
         if torch.is_grad_enabled():
             raise RuntimeError("beam_stream is inference only: run it under torch.no_grad()")
         B, T, _ = enc_chunk.shape
@@ -469,14 +551,36 @@ class TransducerBeamSearcher(torch.nn.Module):
         timed = bool(return_frames)
         if state is not None and ("frames" in state) != timed:
             raise ValueError(f"beam_stream: this stream was started with return_frames={'frames' in state}")
-        if self._device_beam_ok(enc_chunk):
+        if state is None and bias is None:
+            bias = self.bias
+        biased = bias is not None if state is None else "graphs" in state
+        graphs = None
+        if bias is not None and not biased:
+            raise ValueError("beam_stream: this stream was started without bias")
+        if biased:
+            from .biasing import as_list
+            self._check_bias(bias)
+            named = as_list(bias, B) if bias is not None else None
+            graphs = [_NO_GRAPH_YET] * B if state is None else state["graphs"]
+            for b in range(B):
+                if graphs[b] is _NO_GRAPH_YET:
+                    graphs[b] = named[b] if named is not None else None
+                elif named is not None and named[b] is not graphs[b]:
+                    raise ValueError(f"beam_stream: stream {b} was started with another graph; reset_streams it before changing its graph")
+        if self._device_beam_ok(enc_chunk, bias=biased):
             from . import ops
             enc = enc_chunk.contiguous()
             if state is None:
                 mf = int(max_frames or BEAM_STREAM_FRAMES)
                 size = ops.beam_stream_timed_workspace_bytes if timed else ops.beam_stream_workspace_bytes
                 nbytes = size(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
-                if self.lm_weight > 0:
+                if biased:
+                    lm_rnn = self.lm.rnn.rnn if self.lm_weight > 0 else None
+                    nbytes = ops.beam_bias_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1],
+                                                           self.decode_network_lst[0].embedding_dim, self.classifier_network[0].w.out_features,
+                                                           self.beam_size, self.cap, lm_rnn.num_layers if lm_rnn is not None else 0,
+                                                           lm_rnn.hidden_size if lm_rnn is not None else 0, timed)
+                elif self.lm_weight > 0:
                     lm_rnn = self.lm.rnn.rnn
                     hid, V = self.decode_network_lst[1].rnn.hidden_size, self.classifier_network[0].w.out_features
                     if self._beam_is_wide():
@@ -486,9 +590,17 @@ class TransducerBeamSearcher(torch.nn.Module):
                         nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, hid, enc.shape[-1], self.beam_size, self.cap, lm_rnn.num_layers,
                                                                     lm_rnn.hidden_size, timed)
                 state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf, "B": B}
+                if biased:
+                    state["graphs"] = graphs
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")
-            if timed:
+            if biased:
+                from .biasing import pack
+                out = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"], frames=timed,
+                                             bias=pack(graphs, dev))
+                nbest_batch, nbest_scores, status = out[:3]
+                nbest_frames = out[3] if timed else None
+            elif timed:
                 nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv,
                                                                                          state["max_frames"], frames=True)
             else:
@@ -509,19 +621,22 @@ class TransducerBeamSearcher(torch.nn.Module):
                 state["frames"] = nbest_frames
             return [n[0] for n in nbest_batch], state
         if state is None:
-            state = {"beams": [[self._beam_start(timed)] for _ in range(B)]}
+            state = {"beams": [[self._beam_start(timed, biased)] for _ in range(B)]}
             if timed:
                 state["frames_done"] = [0] * B
+            if biased:
+                state["graphs"] = graphs
         elif "beams" not in state:
             raise ValueError("beam_stream: this state was made by the device route")
         counts = nv.cpu().tolist()
         for b in range(B):
             n = min(max(int(counts[b]), 0), T)
             for t in range(n):
-                state["beams"][b] = self._beam_frame(state["beams"][b], enc_chunk[b, t, :], state["frames_done"][b] + t if timed else None)
+                state["beams"][b] = self._beam_frame(state["beams"][b], enc_chunk[b, t, :], state["frames_done"][b] + t if timed else None,
+                                                     graphs[b] if biased else None, biased)
             if timed:
                 state["frames_done"][b] += n
-        ranked = [self._beam_rank(beam, timed) for beam in state["beams"]]
+        ranked = [self._beam_rank(beam, timed, graphs[b] if biased else None, biased) for b, beam in enumerate(state["beams"])]
         state["nbest"], state["scores"] = [r[0] for r in ranked], [r[1] for r in ranked]
         if timed:
             state["frames"] = [r[2] for r in ranked]

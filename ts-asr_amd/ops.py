@@ -2448,14 +2448,68 @@ def beam_wide_workspace_bytes(B, T, H, J, V, beam, cap, lm_layers=0, lm_hidden=0
     return base + (B * 4 * (cap + beam) * ((V + 3) // 4 * 4 + 2 * Ll * Hl) if Ll > 0 else 0)
 
 
-def beam_wide_lds_bytes(H, J, E, V, cap, lm_dims=None, times=True):
-    """Dynamic LDS of beam_search_wide_kernel (include/tsasr_hip.h); lm_dims = (emb_dim, hidden, dnn_neurons) of a fused LM."""
+def beam_wide_lds_bytes(H, J, E, V, cap, lm_dims=None, times=True, bias=False):
+    """Dynamic LDS of beam_search_wide_kernel (include/tsasr_hip.h); lm_dims = (emb_dim, hidden, dnn_neurons) of a fused LM; ``bias``:
+    the biased search's trie state per hypothesis, 4 * cap bytes more."""
     r4 = lambda v: (int(v) + 3) // 4 * 4  # noqa: E731
-    n = 4 * (6 * H + 2 * J + r4(E) + r4(V) + 96) + int(cap) * (16 + 4 * (7 if times else 6))
+    n = 4 * (6 * H + 2 * J + r4(E) + r4(V) + 96) + int(cap) * (16 + 4 * ((7 if times else 6) + (1 if bias else 0)))
     if lm_dims is not None:
         El, Hl, D = (int(v) for v in lm_dims)
         n += 4 * (max(El, Hl, D) + 2 * Hl + max(4 * Hl, D) + 2 * r4(V) + 2)
     return n
+
+
+def beam_bias_workspace_bytes(B, T, H, J, E, V, beam, cap, lm_layers=0, lm_hidden=0, times=False):
+    """Bytes of the biased searches' workspace (``bias=``; tsasr_beam_search_bias_workspace_bytes): the layout of the same search
+    without a graph - narrow for V <= 63 and E <= 64, wide otherwise; lm_layers 0: no LM; ``times``: timed - plus one int32 per
+    token-tree node, the trie state of the node's path."""
+    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
+    B, T, H, J, E, V, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, E, V, beam, cap, lm_layers, lm_hidden))
+    if min(B, T, H, J, E, V, beam, cap) <= 0 or Ll < 0 or (Ll > 0 and Hl <= 0):
+        return 0
+    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
+    lm_part = ((V + 3) // 4 * 4 if (V > 63 or E > 64) else 64) + 2 * Ll * Hl if Ll > 0 else 0
+    return base + B * 4 * (cap + beam) * lm_part + B * a16(4 * (1 + (T + 1) * beam + cap))
+
+
+_BIAS_KEYS = (("child_off", torch.int32), ("child_tok", torch.int32), ("child_to", torch.int32), ("pending", torch.float64),
+              ("base", torch.int32), ("weight", torch.float64))
+
+
+def _beam_bias_desc(bias, B, device):
+    """C.BiasDesc of a ``bias=`` dict (biasing.pack): child_off / child_tok / child_to int32, pending / weight float64, base int32 [B],
+    all contiguous on ``device``; child_off and pending of one length (the rows), every base below it. ValueError otherwise."""
+    if not isinstance(bias, dict) or any(k not in bias for k, _ in _BIAS_KEYS):
+        raise ValueError(f"beam_search: bias must be a dict with the keys {[k for k, _ in _BIAS_KEYS]} (biasing.pack)")
+    for k, dt in _BIAS_KEYS:
+        t = bias[k]
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError(f"beam_search: bias[{k!r}] must be a non-empty contiguous 1-D {dt} tensor")
+        if not t.is_cuda or t.device != device:
+            raise ValueError(f"beam_search: bias[{k!r}] must be on {device}")
+    rows, edges = bias["pending"].numel(), bias["child_tok"].numel()
+    if bias["child_off"].numel() != rows or bias["child_to"].numel() != edges or rows < 2:
+        raise ValueError("beam_search: bias child_off / pending hold one entry per row (>= 2), child_tok / child_to one per edge")
+    if tuple(bias["base"].shape) != (B,) or tuple(bias["weight"].shape) != (B,):
+        raise ValueError(f"beam_search: bias base and weight must have B={B} entries")
+    base = bias.get("base_host")
+    base = bias["base"].cpu().tolist() if base is None else list(base)
+    if len(base) != B or any(int(v) >= rows - 1 for v in base):
+        raise ValueError(f"beam_search: a bias base outside the {rows} packed rows")
+    d = C.BiasDesc()
+    d.child_off, d.child_tok, d.child_to, d.pending = (bias[k].data_ptr() for k in ("child_off", "child_tok", "child_to", "pending"))
+    d.base, d.weight, d.rows, d.edges = bias["base"].data_ptr(), bias["weight"].data_ptr(), rows, edges
+    return d
+
+
+def _beam_bias_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam,
+                      slope, wdtype, fr, lm_desc, lm_weight, bias_desc):
+    """tsasr_beam_search_bias's return code: n_valid None = the offline search, fr None = untimed, lm_desc None = no LM."""
+    return C.lib().tsasr_beam_search_bias(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank),
+                                          int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
+                                          C.io_dtype(encc), wdtype, C.stream_ptr(), C.ptr(fr),
+                                          None if lm_desc is None else C.ctypes.byref(lm_desc), float(lm_weight),
+                                          None if bias_desc is None else C.ctypes.byref(bias_desc))
 
 
 _LM_KEYS = ("emb", "w_ih", "w_hh", "b_ih", "b_hh", "w_dnn", "b_dnn", "ln_g", "ln_b", "ln_eps", "w_out", "b_out", "slope", "weight")
@@ -2583,7 +2637,7 @@ def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
 
 
 def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                workspace=None, frames=False, lm=None, wide=False):
+                workspace=None, frames=False, lm=None, wide=False, bias=None):
     """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
     lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
     n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap).
@@ -2593,15 +2647,24 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
     beam_stream_lm_workspace_bytes.
     ``wide=True`` (tsasr_beam_search_wide, subword models): V and the embedding's columns up to 1024, beam_size <= 64; every form above
     through the one entry point; with an LM the workspace has beam_wide_workspace_bytes. Without it the narrow limits hold (V <= 63, 64
-    embedding columns)."""
+    embedding columns).
+    ``bias`` (tsasr_beam_search_bias): the packed phrase graphs of the batch (biasing.pack); every form above through that one entry
+    point (which picks narrow or wide by the shape: ``wide`` must say the same); the workspace has beam_bias_workspace_bytes. None:
+    the entry points and bytes above."""
     _no_grad_only("beam_search")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, T, H, J, beam_size, cap)
-    desc, lm_weight = None, 0.0
+    desc, lm_weight, lm_layers, lm_hidden = None, 0.0, 0, 0
     if lm is not None:
         desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
         need = (beam_wide_workspace_bytes(B, T, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
                 beam_stream_lm_workspace_bytes(B, T, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
+    bdesc = None
+    if bias is not None:
+        if bool(wide) != (V > 63 or E > 64):
+            raise ValueError(f"beam_search: bias with wide={wide} but V={V}, E={E} (the biased entry point picks by V <= 63 and E <= 64)")
+        bdesc = _beam_bias_desc(bias, B, enc.device)
+        need = beam_bias_workspace_bytes(B, T, H, J, E, V, beam_size, cap, lm_layers, lm_hidden, bool(frames))
     if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
         raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
     C.require_gpu(enc, table, *mats)
@@ -2614,6 +2677,10 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
         tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
                 C.io_dtype(encc), wdtype, C.stream_ptr())
         outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
+        if bdesc is not None:
+            C.check(_beam_bias_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
+                                      state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight, bdesc), "tsasr_beam_search_bias")
+            return
         if lm is not None or wide:
             name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
             C.check(_beam_lm_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
@@ -2634,21 +2701,29 @@ def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdty
 
 
 def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                       workspace, n_valid, max_frames, frames=False, lm=None, wide=False):
+                       workspace, n_valid, max_frames, frames=False, lm=None, wide=False, bias=None):
     """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
     (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
     beam_search returns, for the beam after the chunk. ``frames=True`` (tsasr_beam_search_stream_timed): also the n-best frame lists,
     absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed.
     ``lm``: as in beam_search; the workspace has beam_stream_lm_workspace_bytes and every call of the stream carries the same LM.
-    ``wide``: as in beam_search, the same for every call of the stream."""
+    ``wide``: as in beam_search, the same for every call of the stream.
+    ``bias``: as in beam_search; the workspace has beam_bias_workspace_bytes and every call of the stream is biased (the graph of a
+    stream stays the same from its zeroed start on; the packed arrays around it may change)."""
     _no_grad_only("beam_search_stream")
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
     need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, max_frames, H, J, beam_size, cap)
-    desc, lm_weight = None, 0.0
+    desc, lm_weight, lm_layers, lm_hidden = None, 0.0, 0, 0
     if lm is not None:
         desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
         need = (beam_wide_workspace_bytes(B, max_frames, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
                 beam_stream_lm_workspace_bytes(B, max_frames, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
+    bdesc = None
+    if bias is not None:
+        if bool(wide) != (V > 63 or E > 64):
+            raise ValueError(f"beam_search_stream: bias with wide={wide} but V={V}, E={E}")
+        bdesc = _beam_bias_desc(bias, B, enc.device)
+        need = beam_bias_workspace_bytes(B, max_frames, H, J, E, V, beam_size, cap, lm_layers, lm_hidden, bool(frames))
     if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
         raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
     if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
@@ -2660,6 +2735,11 @@ def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slop
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
 
     def run(hyps, lens, scores, status, Lmax, readout, fr):
+        if bdesc is not None:
+            C.check(_beam_bias_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,
+                                      max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr,
+                                      desc, lm_weight, bdesc), "tsasr_beam_search_bias")
+            return
         if lm is not None or wide:
             name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
             C.check(_beam_lm_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,

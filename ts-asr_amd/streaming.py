@@ -167,7 +167,7 @@ class StreamingTranscriber:
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def start(self, batch_size, max_frames, enroll=None, speaker_embs=None, speaker_embs_length=None, keep_encoder_out=False, timestamps=False,
-              audio=False, feature_prior=None, slots=False, max_speaker_frames=1, max_audio_samples=32000, keep_features=False):
+              audio=False, feature_prior=None, slots=False, max_speaker_frames=1, max_audio_samples=32000, keep_features=False, bias=None):
         """Begin B streams of at most ``max_frames`` encoder frames (4 mel frames each). The speaker embedding is computed once here:
         ``enroll`` = (enrollment signals or features, relative lengths) through the recipe's own speaker branch, or given directly as
         ``speaker_embs`` (+ ``speaker_embs_length`` for cross-attention); neither = no injection (variant none). keep_encoder_out: keep
@@ -177,9 +177,26 @@ class StreamingTranscriber:
         slots: the B rows are slots, all free to begin with, that sessions enter with admit() and leave with release() (module
         docstring); the speaker embedding then comes per session with admit(), padded to ``max_speaker_frames`` rows. Slot sessions
         admitted with audio=True are fed with push_audio(): ``max_audio_samples`` is the most samples one call may carry per slot (it
-        sizes the sample rings, which the first such admit() allocates); keep_features keeps their feature frames for features_out()."""
+        sizes the sample rings, which the first such admit() allocates); keep_features keeps their feature frames for features_out().
+        bias (search="beam"; biasing.py): the streams' phrase graphs, one ContextGraph for all or a list of B entries (a graph or
+        None). start(slots=True, bias=True) reserves the biased search layout; each session then names its graph with
+        admit(slot, ..., bias=graph or None). Greedy search is not biased: ValueError."""
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
+        if bias is not None and bias is not False and self.search != "beam":
+            raise ValueError("start(bias=...): contextual biasing needs StreamingTranscriber(brain, search='beam')")
+        if slots and not isinstance(bias, bool) and bias is not None:
+            raise ValueError("start(slots=True): bias=True reserves the biased search; the graphs come per session, with admit(slot, bias=...)")
+        if not slots and isinstance(bias, bool):
+            raise ValueError("start(bias=True/False) goes with slots=True; give the streams' graph(s) otherwise")
+        if bias is None or bias is False:
+            self.bias_graphs = None
+        elif slots:
+            self.bias_graphs = [None] * int(batch_size)
+        else:
+            from .biasing import as_list
+            self.searcher._check_bias(bias)
+            self.bias_graphs = as_list(bias, int(batch_size))
         if slots and (enroll is not None or speaker_embs is not None):
             raise ValueError("start(slots=True): the speaker embedding comes per session, with admit(slot, enroll=... / speaker_embs=...)")
         if slots and audio:
@@ -254,7 +271,7 @@ class StreamingTranscriber:
         if slot is not None and not 0 <= int(slot) < self.B:
             raise ValueError(f"{what}: slot {slot} is not one of the {self.B} slots")
 
-    def admit(self, slot, enroll=None, speaker_embs=None, speaker_embs_length=None, audio=False, feature_prior=None):
+    def admit(self, slot, enroll=None, speaker_embs=None, speaker_embs_length=None, audio=False, feature_prior=None, bias=None):
         """A new session enters the free ``slot``. Its speaker embedding: ``enroll`` = (one enrollment signal [1, N], its relative
         length [1]) through the recipe's speaker branch, or ``speaker_embs`` [1, S, D] (+ ``speaker_embs_length`` [1] relative, for
         cross-attention), S <= max_speaker_frames; neither = no injection. Reset for this slot only: offset and mel count, the
@@ -262,8 +279,15 @@ class StreamingTranscriber:
         output. The K/V cache keeps its bytes: rows at or past a slot's offset are never read. audio: the session is fed waveform
         (push_audio) instead of features; also reset for this slot are then its sample and emitted-frame counts, its ended flag and its
         row of the normaliser's state (zeros, or ``feature_prior`` = (mean [n_mels], std [n_mels], n0) as ops.running_norm_state writes
-        it). The sample ring keeps its bytes: samples a session has not received are never read."""
+        it). The sample ring keeps its bytes: samples a session has not received are never read. bias (start(slots=True,
+        bias=True)): the session's phrase graph (None: the session is not biased); the graphs of the other slots stay as they are."""
         self._need_slots("admit()", slot)
+        if bias is not None:
+            if self.bias_graphs is None:
+                raise ValueError("admit(bias=...) needs start(..., slots=True, bias=True)")
+            self.searcher._check_bias(bias)
+            if not hasattr(bias, "step"):
+                raise ValueError("admit(bias=...): one session's graph is a biasing.ContextGraph or None")
         if torch.is_grad_enabled():
             raise RuntimeError("StreamingTranscriber is inference only: run it under torch.no_grad()")
         slot = int(slot)
@@ -307,6 +331,8 @@ class StreamingTranscriber:
             for hist in layer["hist"]:
                 hist[slot] = 0
         self.searcher.reset_streams(self.search_state, [slot])
+        if self.bias_graphs is not None:                 # the search learns the slot's new graph with the next push
+            self.bias_graphs[slot] = None if bias is None or bias.empty else bias
         self.hyps[slot], self.hyp_frames[slot], self.slot_chunks[slot] = [], [], []
         if audio:
             if self.features is None:
@@ -374,7 +400,7 @@ class StreamingTranscriber:
         self.closed = bool(last)
         if self.search == "beam":
             best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames,
-                                                                return_frames=self.timestamps, raise_stopped=False)
+                                                                return_frames=self.timestamps, raise_stopped=False, bias=self.bias_graphs)
             self.hyps = [list(h) for h in best]
             if self.timestamps:
                 self.hyp_frames = [list(f[0]) for f in self.search_state["frames"]]
@@ -592,7 +618,7 @@ class StreamingTranscriber:
         n_valid = (valid - t0).clamp(0, e.shape[1]).to(torch.int32)
         if self.search == "beam":                 # the best hypothesis so far (its prefix may change with later frames)
             best, self.search_state = self.searcher.beam_stream(e, self.search_state, n_valid, max_frames=self.max_frames,
-                                                                return_frames=self.timestamps)
+                                                                return_frames=self.timestamps, bias=self.bias_graphs)
             self.hyps = [list(h) for h in best]
             if self.timestamps:
                 self.hyp_frames = [list(f[0]) for f in self.search_state["frames"]]
