@@ -91,6 +91,11 @@ int tsasr_joint_wide_bwd(const float *dlogits, const void *enc, const void *dec,
  * bwd writes dlogits[b,t,u,v] = gscale[b] * d costs[b] / d logits  (zeros outside the lattice / v >= V).
  * ------------------------------------------------------------------------------------------ */
 long long tsasr_rnnt_loss_error_word_offset(int B, int T, int U1);   /* split lattices (long targets, small batches): byte offset of the time-out word (1 = timed out), -1 = none */
+/* Read-only, host-only view of the workspace's plane layout under the current lattice plan (tests read the planes cell by cell). Fills
+ * out[0 .. min(n, 17)): plane size in floats, R, U1P, sh, K, KT, NW, NC, skew flag, then the float offsets of lpb, lpe_in, lpe_out, alpha,
+ * beta, lse, xch (the split lattice's exchange rows) and logp. Element (b, t, u) of a plane is ((b * R + t + (u >> sh)) * U1P + u)
+ * (sh = 31: frame-major planes). Returns 17, or -1 for a shape the loss does not take. */
+int tsasr_rnnt_loss_workspace_layout(int B, int T, int U1, long long *out, int n);
 size_t tsasr_rnnt_loss_workspace_bytes(int B, int T, int U1);
 int tsasr_rnnt_loss_fwd(const float *logits, const int32_t *targets, int ldt, const int32_t *tlen,
                         const int32_t *ulen, float *costs, int B, int T, int U1, int V, int ldl, int blank,

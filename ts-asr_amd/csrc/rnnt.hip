@@ -1535,6 +1535,22 @@ long long tsasr_rnnt_loss_error_word_offset(int B, int T, int U1) {
     return w.err ? (long long)(reinterpret_cast<char *>(w.err) - base) : -1;
 }
 
+/* Read-only view of the loss workspace's plane layout under the current lattice plan (tests read the planes cell by cell; nothing in the
+ * product path calls this). Fills out[0 .. min(n, 17)): plane size in floats, R, U1P, sh, K, KT, NW, NC, skew flag, then the float offsets of
+ * lpb, lpe_in, lpe_out, alpha, beta, lse, xch (the split lattice's exchange rows; unused otherwise) and logp. Element (b, t, u) of a plane
+ * is ((b * R + t + (u >> sh)) * U1P + u); sh = 31 when the planes are frame-major. Returns the number of values the layout has (17), or -1
+ * for a shape the loss does not take. */
+int tsasr_rnnt_loss_workspace_layout(int B, int T, int U1, long long *out, int n) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 64 * 32 || (n > 0 && !out)) return -1;
+    char base[1];
+    const RnntWs w = rnnt_carve(base, B, T, U1);
+    auto off = [&](const float *p) { return (long long)((reinterpret_cast<const char *>(p) - base) / (ptrdiff_t)sizeof(float)); };
+    const long long v[17] = {(long long)rnnt_plane_floats(B, T, U1), w.R, w.U1P, w.sh, w.K, w.KT, w.NW, w.NC, w.sh != 31 ? 1 : 0,
+                             off(w.lpb), off(w.lpe_in), off(w.lpe_out), off(w.alpha), off(w.beta), off(w.lse), off(w.xch), off(w.logp)};
+    for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
+    return 17;
+}
+
 size_t tsasr_rnnt_loss_workspace_bytes(int B, int T, int U1) {
     if (B <= 0 || T <= 0 || U1 <= 0) return 0;
     return align_up((6 * rnnt_plane_floats(B, T, U1) + align_up((size_t)B, 64) + rnnt_xch_floats(B, T, U1)) * sizeof(float), 256);
