@@ -112,6 +112,36 @@ int tsasr_rnnt_loss_bwd(const float *logits, const int32_t *targets, int ldt, co
 void tsasr_rnnt_lattice_plan(int skew, int waves, int mc);
 
 /* ------------------------------------------------------------------------------------------
+ * Auxiliary CTC loss on the encoder's frames  (csrc/ctc.hip; replaces SB/nnet/losses.py `ctc_loss` -> torch.nn.functional.ctc_loss with
+ * zero_infinity=True on the output of `proj_ctc`, call site SB recipes/LibriSpeech/ASR/transducer/train.py:104-174, and
+ * SB/decoders/ctc.py `ctc_greedy_decode`).
+ *   logits [B,T,ldl]: the RAW per-frame scores (io_dtype); the row log-softmax over the V valid columns is fused, no log-prob tensor exists.
+ *   costs[b] = -log P(y_b | x_b) over the S_b = 2 U_b + 1 extended states, T_b = clamp(tlen[b], 1, T), U_b = clamp(ulen[b], 0, U);
+ *   target ids are clamped into [0, V-1] (as the RNN-T loss clamps them), columns of `targets` [B,ldt] at or beyond U_b never reach a result;
+ *   an infeasible utterance (T_b < U_b + number of adjacent equal labels) gets costs[b] = 0 and an all-zero gradient (zero_infinity);
+ *   dlogits[b,t,v] = gscale[b] * (softmax(x_{b,t})_v - occ_b(t,v)), occ = posterior occupancy of the states that carry v; EVERY row is
+ *   written: rows t >= T_b and columns V <= v < ldl are zero.
+ * Ranges: 1 <= V <= 1024, ldl >= V and ldl % 8 == 0, T >= 1, 0 <= U <= 2047 (one workgroup of at most 1024 threads owns an utterance's
+ * lattice, four consecutive states per thread: S <= 4095), ldt >= U, 0 <= blank < V; anything else is TSASR_E_INVALID before any launch.
+ * fwd: row pass (lse + compact emission planes lp(blank), lp(y_u)), the per-vocabulary chains of target positions, then one workgroup per
+ * utterance and direction (alpha, beta in fp32 log space, kept in `workspace`; one barrier per frame). bwd: one kernel over all rows; a
+ * label that occurs several times has its occupancies summed along its chain in ascending position: no float atomics. Nothing waits for
+ * another workgroup, allocates or reads on the host: capturable, re-entrant per stream, identical bits run to run. The workspace size is
+ * a function of (B, T, U, V) alone; bwd takes the forward's workspace.
+ * tsasr_ctc_greedy: per-frame argmax over the V valid columns (lowest index among equal scores) of frames t < clamp(tlen[b], 0, T),
+ * repeats collapsed, blanks dropped, compacted on the device in one launch: tokens[b, :ntok[b]], the rest of the row (ldo >= T) is -1.
+ * ------------------------------------------------------------------------------------------ */
+size_t tsasr_ctc_loss_workspace_bytes(int B, int T, int U, int V);
+int tsasr_ctc_loss_fwd(const void *logits /* [B,T,ldl] */, const int32_t *targets /* [B,ldt] */, int ldt, const int32_t *tlen,
+                       const int32_t *ulen, float *costs /* [B] */, int B, int T, int U, int V, int ldl, int blank, int io_dtype,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int tsasr_ctc_loss_bwd(const void *logits, const int32_t *targets, int ldt, const int32_t *tlen, const int32_t *ulen,
+                       const float *gscale /* [B] */, void *dlogits /* [B,T,ldl], io dtype */, int B, int T, int U, int V, int ldl, int blank,
+                       int io_dtype, const void *workspace /* the forward's */, size_t workspace_bytes, void *stream);
+int tsasr_ctc_greedy(const void *logits, const int32_t *tlen, int32_t *tokens /* [B,ldo] */, int ldo, int32_t *ntok /* [B] */,
+                     int B, int T, int V, int ldl, int blank, int io_dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Forced alignment on the same lattice (no reference counterpart): the best path instead of the sum over all paths.
  *   delta(0,0) = 0,  delta(t,u) = max(delta(t-1,u) + lp_blank(t-1,u), delta(t,u-1) + lp_label(t,u-1)),  fp32, lp_* as in the loss;
  *   scores[b] = delta(T_b-1, U_b) + lp_blank(T_b-1, U_b)  = log-probability of the best path  (<= -costs[b]);

@@ -52,6 +52,10 @@ _PROTOS = {
     "tsasr_rnnt_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
     "tsasr_rnnt_align_workspace_bytes": (c_size_t, [c_int] * 3),
     "tsasr_rnnt_align": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "tsasr_ctc_loss_workspace_bytes": (c_size_t, [c_int] * 4),
+    "tsasr_ctc_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
+    "tsasr_ctc_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
+    "tsasr_ctc_greedy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p]),
     "tsasr_joint_wide_loss_workspace_bytes": (c_size_t, [c_int] * 5),
     "tsasr_joint_wide_loss_error_word_offset": (ctypes.c_longlong, [c_int] * 5),
     "tsasr_joint_wide_loss_fwd": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),

@@ -31,6 +31,8 @@ ALIASES = {
     "speechbrain.lobes.models.RNNLM.RNNLM": _PKG + ".nnet.RNNLM",
     "speechbrain.nnet.transducer.transducer_joint.Transducer_joint": _PKG + ".rnnt.Transducer_joint",
     "speechbrain.nnet.losses.transducer_loss": _PKG + ".rnnt.transducer_loss",
+    "speechbrain.nnet.losses.ctc_loss": _PKG + ".ctc.ctc_loss",
+    "speechbrain.nnet.activations.Softmax": _PKG + ".ctc.Softmax",
     "speechbrain.nnet.schedulers.NoamScheduler": _PKG + ".core.NoamScheduler",
     "speechbrain.utils.epoch_loop.EpochCounter": _PKG + ".core.EpochCounter",
     "speechbrain.decoders.transducer.TransducerBeamSearcher": _PKG + ".decoders.TransducerBeamSearcher",

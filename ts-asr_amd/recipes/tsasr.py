@@ -3,15 +3,18 @@
 Mirrors train_librispeechmix_scratch.py:33-195 (and the ``pretrained`` / ``none`` variants, which differ only in
 the speaker branch: train_librispeechmix_pretrained.py:45-63, train_librispeechmix_none.py): same module names in
 ``self.modules``, same call order, same return values (``compute_forward -> (logits [B,T',U+1,V], hyps or None)``,
-``compute_objectives -> 0-dim loss with autograd``). Differences: joiner + head run as ONE fused HIP kernel
+``compute_objectives -> 0-dim loss with autograd``); with ``ctc_weight > 0`` the SpeechBrain transducer recipe's auxiliary CTC branch
+(``proj_ctc`` on the projected encoder output, a third element ``ctc_scores`` in the forward's tuple). Differences: joiner + head run as ONE fused HIP kernel
 (the [B,T',U+1,J] joint tensor is never built), lengths stay on the device, WER / CER are scored on the device
 (metrics.py); plotting, logging and checkpoint selection are left to the caller (out of scope).
 """
+import contextlib
+import functools
 import os
 
 import torch
 
-from .. import core, prof, rnnt
+from .. import core, ctc, prof, rnnt
 from ..hparams import Unavailable
 from ..metrics import merge_across_ranks, undo_padding
 from ..nnet import abs_lengths_round
@@ -24,6 +27,9 @@ Stage = core.Stage
 # a high-priority side stream - were measured equal or slower and are gone: profiles/r02_notes.md section 5.)
 _OVERLAP_MODE = os.environ.get("TSASR_OVERLAP", "1")
 _OVERLAP_DEFAULT = _OVERLAP_MODE != "0"
+# TSASR_CTC_STREAM: "main" (default) the auxiliary CTC branch (proj_ctc, loss) runs on the main stream between encoder_proj and the joint;
+# "side" on a stream of its own, beside the joint and the transducer loss (profiles/ctc_notes.md section 4 has both timed)
+_CTC_STREAM = os.environ.get("TSASR_CTC_STREAM", "main")
 _PRED_STREAM_MIN_U = int(os.environ.get("TSASR_PRED_STREAM_MIN_U", "512"))      # tokens from which the predictor gets a stream of its own
 
 
@@ -47,6 +53,15 @@ class TSASR(core.Brain):
         if variant not in ("scratch", "pretrained", "none"):
             raise ValueError(f"unknown TSASR variant {variant!r}")
         self.variant = variant
+        # Auxiliary CTC head (SB recipes/LibriSpeech/ASR/transducer/hparams/conformer_transducer.yaml:198-200 `proj_ctc`): built here, before
+        # the optimizer and the gradient arena exist, unless the YAML brought one; with ctc_weight == 0 there is none and nothing changes
+        self.ctc_weight = float(hp.get("ctc_weight", 0.0) or 0.0)
+        if not 0.0 <= self.ctc_weight <= 1.0:
+            raise ValueError(f"ctc_weight must lie in [0, 1], got {self.ctc_weight}")
+        if self.ctc_weight > 0 and "proj_ctc" not in self.modules:
+            from ..nnet import Linear
+            head = self.modules.transducer_head.w.weight
+            self.modules["proj_ctc"] = Linear(input_size=head.shape[1], n_neurons=head.shape[0]).to(self.device)
 
     # ---- speaker branch (train_librispeechmix_scratch.py:44-80) ------------------------------------
     def _speaker_embedding(self, batch, epoch):
@@ -99,6 +114,12 @@ class TSASR(core.Brain):
             self._aux_streams.append(self._side)      # Brain joins it after backward
         return self._side
 
+    def _ctc_stream(self):
+        if getattr(self, "_ctc_side", None) is None:
+            self._ctc_side = torch.cuda.Stream(device=self.device)
+            self._aux_streams.append(self._ctc_side)
+        return self._ctc_side
+
     def _pred_stream(self):
         if getattr(self, "_third", None) is None:
             self._third = torch.cuda.Stream(device=self.device)
@@ -127,8 +148,22 @@ class TSASR(core.Brain):
             cf = self._causal_feats = CausalFeatures(self.modules.feature_extractor)
         return cf
 
+    def _ctc_train(self, epoch):
+        """Does this TRAIN step carry the CTC term (train.py:111,153: ctc_weight > 0 and current_epoch <= number_of_ctc_epochs)?"""
+        return self.ctc_weight > 0 and epoch <= int(getattr(self.hparams, "number_of_ctc_epochs", 0) or 0)
+
+    def _host_draws(self):
+        """Whether a step carries the CTC term is decided on the host, by the epoch: part of the captured graph's key, so the steps after
+        the CTC epochs replay a graph of their own (nothing is added with ctc_weight == 0)."""
+        draws = super()._host_draws()
+        if self.ctc_weight > 0:
+            hp = self.hparams
+            draws += (("ctc", self._ctc_train(hp.epoch_counter.current if hasattr(hp, "epoch_counter") else 0)),)
+        return draws
+
     def _forward_logits(self, batch, stage):
-        """The forward up to the fused joint logits, shared by compute_forward and align_batch: (logits, enc_out, tlen, ulen, epoch)."""
+        """The forward up to the fused joint logits, shared by compute_forward and align_batch: (logits, enc_out, tlen, ulen, epoch).
+        The CTC head's scores (or None) are left in ``self._ctc_scores``: TRAIN steps of the CTC epochs, and the VALID stage."""
         hp = self.hparams
         epoch = hp.epoch_counter.current if hasattr(hp, "epoch_counter") else 0
         batch = batch.to(self.device)
@@ -208,6 +243,16 @@ class TSASR(core.Brain):
         prof.stamp("mixture encoder forward done [main]")
         if prof.STAMPS and enc_out.requires_grad:
             enc_out.register_hook(lambda g: prof.stamp("joint backward done [main]"))
+        self._ctc_scores = None
+        if "proj_ctc" in self.modules and ((stage == Stage.TRAIN and self._ctc_train(epoch)) or stage == Stage.VALID):
+            fork = _CTC_STREAM == "side" and stage == Stage.TRAIN and torch.device(self.device).type == "cuda"
+            if fork:
+                cur, cs = torch.cuda.current_stream(), self._ctc_stream()
+                cs.wait_stream(cur)
+                enc_out.record_stream(cs)
+            with (torch.cuda.stream(cs) if fork else contextlib.nullcontext()):
+                self._ctc_scores = ctc.project(self.modules.proj_ctc, enc_out)      # raw scores [B,T',V]: the loss normalises the rows itself
+            prof.stamp("ctc head forward done [main]")
 
         if dec_out is None:
             dec_out = self._predictor(tokens_bos, tokens_bos_lens)
@@ -241,6 +286,8 @@ class TSASR(core.Brain):
                 self.hyp_times.append((getattr(batch, "id", None), hyps, frames))
             else:
                 hyps, _, _, _ = hp.beam_searcher(enc_out)
+        if "proj_ctc" in self.modules:
+            return logits, hyps, self._ctc_scores
         return logits, hyps
 
     def align_batch(self, batch):
@@ -258,17 +305,42 @@ class TSASR(core.Brain):
                 self.modules.train()
 
     def compute_objectives(self, predictions, batch, stage):
-        logits, hyps = predictions
+        logits, hyps = predictions[:2]
+        ctc_scores = predictions[2] if len(predictions) > 2 else None
         _, mixed_lens = batch.mixed_sig
         tokens, tokens_lens = batch.tokens
         t32 = getattr(self, "_tokens32", None)
         if t32 is not None and t32[0].data_ptr() == tokens.data_ptr() and t32[0].shape == tokens.shape:
             tokens = t32[1]
         loss = self.hparams.transducer_loss(logits, tokens, mixed_lens, tokens_lens)
+        if stage == Stage.TRAIN and self.ctc_weight > 0:
+            # train.py:153-160: ctc_weight * CTC + (1 - ctc_weight) * transducer during the CTC epochs; afterwards the CTC term is 0 and the
+            # factor (1 - ctc_weight) stays
+            loss = (1.0 - self.ctc_weight) * loss
+            if ctc_scores is not None:
+                cost = getattr(self.hparams, "ctc_cost", None)
+                if cost is None or isinstance(cost, Unavailable):      # a YAML without the key: the recipe files' own setting
+                    cost = functools.partial(ctc.ctc_loss, blank_index=getattr(self.hparams, "blank_index", 0), reduction="batchmean")
+                fork = _CTC_STREAM == "side" and getattr(self, "_ctc_side", None) is not None
+                if fork:     # (the scores were made on that stream; the term joins the main stream below)
+                    cur, cs = torch.cuda.current_stream(), self._ctc_side
+                    cs.wait_stream(cur)
+                with (torch.cuda.stream(cs) if fork else contextlib.nullcontext()):
+                    term = self.ctc_weight * cost(ctc_scores, tokens, mixed_lens, tokens_lens)
+                if fork:
+                    cur.wait_stream(cs)
+                    term.record_stream(cur)
+                loss = loss + term
         prof.stamp("loss forward done [main]")
         if hyps is not None:
             self.last_hyps = hyps
             self._score(hyps, batch)
+        if stage == Stage.VALID and ctc_scores is not None:      # how far the CTC head has learnt: its greedy decoding, scored like the searcher's
+            # (one device-to-host copy of the compacted tokens per VALID batch, as the searcher's own hypotheses make one: _score takes lists)
+            self.last_ctc_hyps = ctc.ctc_greedy_decode(ctc_scores, mixed_lens, getattr(self.hparams, "blank_index", 0))
+            cwer, ccer = getattr(self, "ctc_wer_metric", None), getattr(self, "ctc_cer_metric", None)
+            if cwer is not None or ccer is not None:
+                self._score(self.last_ctc_hyps, batch, cwer, ccer)
         return loss
 
     # ---- WER / CER statistics (train_librispeechmix_scratch.py:162-188, 197-262), scored on the device by metrics.ErrorRateStats ----
@@ -276,11 +348,12 @@ class TSASR(core.Brain):
         make = getattr(self.hparams, key, None)
         return make() if callable(make) and not isinstance(make, Unavailable) else None
 
-    def _score(self, hyps, batch):
-        """Appends a searched batch to the stage's statistics: launches only, nothing is read back before the stage ends. With a
+    def _score(self, hyps, batch, wer=None, cer=None):
+        """Appends a searched batch to the stage's statistics (the searcher's WER / CER objects, or the pair handed in): launches only, nothing is read back before the stage ends. With a
         tokenizer (the caller's, called as the reference calls its SentencePiece wrapper) words against batch.target_words into the
         CER and WER objects; without one the hypothesis token ids against batch.tokens cut to their lengths, into one token-level object."""
-        wer, cer = getattr(self, "wer_metric", None), getattr(self, "cer_metric", None)
+        if wer is None and cer is None:
+            wer, cer = getattr(self, "wer_metric", None), getattr(self, "cer_metric", None)
         tokenizer = getattr(self, "tokenizer", None)
         if wer is None and (cer is None or tokenizer is None):
             return
@@ -300,6 +373,8 @@ class TSASR(core.Brain):
         super().on_stage_start(stage, epoch)
         if stage != Stage.TRAIN:
             self.cer_metric, self.wer_metric = self._metric("cer_computer"), self._metric("wer_computer")
+        if stage == Stage.VALID and "proj_ctc" in self.modules:
+            self.ctc_cer_metric, self.ctc_wer_metric = self._metric("cer_computer"), self._metric("wer_computer")
         if stage == Stage.TEST:
             self.hyp_times = []      # (utterance ids, hypotheses, emission frames) per batch when hparams.hyp_ctm is set
 
@@ -325,6 +400,19 @@ class TSASR(core.Brain):
                 stats["WER"] = wer.summarize("error_rate")
             else:
                 stats["TER"] = wer.summarize("error_rate")
+        cwer, ccer = getattr(self, "ctc_wer_metric", None), getattr(self, "ctc_cer_metric", None)
+        if stage == Stage.VALID and "proj_ctc" in self.modules and cwer is not None:      # the CTC head's greedy decoding, every VALID stage
+            if self.distributed:
+                for m in (ccer, cwer):
+                    if m is not None:
+                        merge_across_ranks(m)
+            if len(cwer.ids) > 0 or len(cwer.scores) > 0:
+                if getattr(self, "tokenizer", None) is not None:
+                    if ccer is not None:
+                        stats["ctc_CER"] = ccer.summarize("error_rate")
+                    stats["ctc_WER"] = cwer.summarize("error_rate")
+                else:
+                    stats["ctc_TER"] = cwer.summarize("error_rate")
         # (the reference logs through hparams.train_logger and keeps checkpoints by WER here: both are Unavailable, the caller's)
         if stage == Stage.VALID:
             self.valid_stats = stats
