@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void joint_f32_bwd_x_kernel(const float *__res
                                                               int T, int U1, int J, int V, int ldl, float slope) {
     __shared__ float g[UT][VMAX];
     const int b = blockIdx.y, u0 = blockIdx.x * UT;
-    const int tl = tlen ? min(tlen[b], T) : T, ul = ulen ? min(ulen[b] + 1, U1) : U1;     // dlogits are zero outside the utterance's lattice
+    // dlogits are zero outside the utterance's lattice; T_b = clamp(tlen, 1, T), U_b = clamp(ulen, 0, U1 - 1) as the loss that wrote them clamps
+    const int tl = tlen ? min(max(tlen[b], 1), T) : T, ul = ulen ? min(max(ulen[b], 0) + 1, U1) : U1;
     float w[KPT][VMAX], dw[KPT][VMAX], dd[KPT][UT], dcv[KPT][UT], db = 0.f;
 #pragma unroll
     for (int c = 0; c < KPT; ++c) {
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void joint_f32_bwd_y_kernel(const float *__res
                                                               const int *__restrict__ ulen, int T, int U1, int J, int V, int ldl, float slope) {
     __shared__ float g[UT][VMAX];
     const int b = blockIdx.y, t = blockIdx.x;
-    const int tl = tlen ? min(tlen[b], T) : T, ul = ulen ? min(ulen[b] + 1, U1) : U1;
+    const int tl = tlen ? min(max(tlen[b], 1), T) : T, ul = ulen ? min(max(ulen[b], 0) + 1, U1) : U1;
     float w[KPT][VMAX], e[KPT], acc[KPT];
 #pragma unroll
     for (int c = 0; c < KPT; ++c) {
@@ -192,7 +193,8 @@ size_t tsasr_joint_f32_bwd_workspace_bytes(int B, int U1, int J) {
 }
 
 /* denc [B,T,J], ddec [B,U1,J] fully written; dW [V,J], dbias [V] through the deferrable batched reduction. tlen / ulen (may be NULL):
- * dlogits outside frame < tlen[b], column <= ulen[b] are taken as zero (the loss writes zeros there). */
+ * dlogits outside frame < T_b, column <= U_b are taken as zero (the loss writes zeros there; T_b = clamp(tlen[b], 1, T) and
+ * U_b = clamp(ulen[b], 0, U1 - 1), as tsasr_rnnt_loss_fwd clamps them). */
 int tsasr_joint_f32_bwd(const float *dlogits, const float *enc, const float *dec, const float *W, float *denc, float *ddec, float *dW,
                         float *dbias, const int32_t *tlen, const int32_t *ulen, int B, int T, int U1, int J, int V, int ldl, float slope,
                         void *workspace, size_t workspace_bytes, void *stream) {
