@@ -618,95 +618,44 @@ int tsasr_inject_fwd(const void *src, const void *spk, void *out, int B, int T, 
 int tsasr_inject_bwd(const void *dout, const void *src, const void *spk, void *dsrc, void *dspk, int B, int T, int D, int mode, int io_dtype,
                      void *stream);
 /* ------------------------------------------------------------------------------------------
- * Greedy transducer search on the device (SB/decoders/transducer.py:138-218, transducer_greedy_decode): one launch decodes the batch,
- * one persistent workgroup per utterance; predictor = embedding table -> one-layer LSTM -> Linear, joiner = LeakyReLU(enc + pn) -> Linear
- * head; at most one symbol per frame, the predictor advances only on a non-blank. enc [B,T,J] (io_dtype); emb fp32 [n_emb, E], E <= 64;
- * LSTM weights in torch layout (w_ih [4H,E], w_hh [4H,H], gate order i,f,g,o); w_proj [J,H]; w_head [V,J], V <= 63; matrices in `wdtype`
- * (TSASR_F32 | TSASR_BF16), biases fp32 or NULL; H, J multiples of 4. preds int32 [B,T]: symbol emitted at frame t or -1;
- * logp_sum fp32 [B]: sum of the emitted symbols' log-probabilities.
+ * Greedy transducer search on the device (SB/decoders/transducer.py:138-218, transducer_greedy_decode; csrc/search.hip
+ * greedy_decode_kernel): one launch decodes the batch, one persistent workgroup per utterance; predictor = embedding table -> one-layer
+ * LSTM -> Linear, joiner = LeakyReLU(enc + pn) -> Linear head; at most one symbol per frame, the predictor advances only on a non-blank;
+ * the arg max takes the lowest index among ties. enc [B,T,J] (io_dtype); emb fp32 [n_emb, E]; LSTM weights in torch layout (w_ih [4H,E],
+ * w_hh [4H,H], gate order i,f,g,o); w_proj [J,H]; w_head [V,J]; matrices in `wdtype` (TSASR_F32 | TSASR_BF16), biases fp32 or NULL;
+ * H, J multiples of 4 and <= 1024. preds int32 [B,T]: symbol emitted at frame t or -1; logp_sum fp32 [B]: sum of the emitted symbols'
+ * log-probabilities.
+ * wide == 0: V <= 63 and E <= 64 (character models). wide != 0, the WIDE instantiations for subword vocabularies: V <= 1024 and E <= 1024
+ * (a one-hot table has E = V - 1; E % 4 == 0 runs a dense product, any other E adds the columns of w_ih that meet a non-zero entry of the
+ * embedding row); a character model through them gives its own result.
+ * state and n_valid both NULL: the offline search. Both given: one chunk of a stream; state fp32 [B, 2H + J + 4] (caller-owned, zeroed
+ * before the first chunk) carries h, c, the projected predictor output, the last symbol, the running log-prob sum and a primed flag
+ * between calls; n_valid int32 [B] = frames of this chunk to decode per utterance (preds of the others are -1; a zero count leaves the
+ * state untouched); logp_sum [B] receives the running sum. A tensor decoded in pieces gives the bits of one offline call over it.
+ * Exactly one of the two NULL is TSASR_E_INVALID.
  * ------------------------------------------------------------------------------------------ */
 int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                        const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
-                        int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream);
-
-/* The same search over one chunk of a stream (csrc/search.hip): state fp32 [B, 2H + J + 4] (caller-owned, zeroed before the first chunk)
- * carries h, c, the projected predictor output, the last symbol, the running log-prob sum and a primed flag between calls; n_valid int32 [B]
- * = frames of this chunk to decode per utterance (preds of the others are -1; a zero count leaves the state untouched); logp_sum [B]
- * receives the running sum. A tensor decoded in pieces gives the bits of one tsasr_greedy_decode call over it. */
-int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                               const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
-                               const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
-                               float slope, int io_dtype, int wdtype, void *stream);
-
-/* The two greedy searches for subword vocabularies (csrc/search.hip greedy_decode_kernel's WIDE instantiations): arguments, outputs and the stream state
- * [B, 2H + J + 4] of the two calls above, with V <= 1024 and E <= 1024 (a one-hot table has E = V - 1; E % 4 == 0 runs a dense product, any
- * other E adds the columns of w_ih that meet a non-zero entry of the embedding row). The arg max takes the lowest index among ties. */
-int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
-                             int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream);
-int tsasr_greedy_decode_stream_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                                    const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
-                                    const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
-                                    float slope, int io_dtype, int wdtype, void *stream);
+                        const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state, const int32_t *n_valid,
+                        int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype,
+                        int wdtype, void *stream, int wide);
 
 /* ------------------------------------------------------------------------------------------
- * Beam transducer search on the device (SB/decoders/transducer.py:220-373, transducer_beam_search_decode, no LM fusion) for the networks
- * tsasr_greedy_decode takes: one persistent workgroup per utterance, one launch decodes the batch. Scores in fp64 as the host loop;
- * list order as the reference (first maximum of logp / len, appends in top-k order, stable n-best sort, top-k ties: lower index). Each
- * node of the hypothesis tree runs its predictor step once. 2 <= beam <= V, 1 <= nbest <= 64, cap >= beam = hypotheses a frame may
- * hold (its A list). workspace >= tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap) = B * (align16(64 + 24 beam) +
- * align16(8 (1 + (max_frames + 1) beam + cap)) + 4 (cap + beam)(J + 2H)). hyps int32 [B,nbest,Lmax] (first min(len, Lmax) tokens),
- * lens int32 [B,nbest] (-1: the beam holds fewer), scores fp64 [B,nbest] = logp / len(prediction incl. the blank prefix), status int32
- * [B]: 0 ok, 1 a frame needed more than cap hypotheses, 2 token tree full, 3 no hypothesis left to expand; such an utterance stops
- * there, the others are unaffected. The offline call starts the workspace afresh and leaves the final beam in it.
+ * The beam search's workspace, a function of the shape alone:
+ *   B * (align16(64 + 24 beam) + align16(8 nodes) + 4 (cap + beam)(J + 2H + lmw) + ((times ? 1 : 0) + (bias ? 1 : 0)) align16(4 nodes)),
+ *   nodes = 1 + (T + 1) beam + cap, lmw = lm_layers > 0 ? (wide ? round_up(V, 4) : 64) + 2 lm_layers lm_hidden : 0
+ * per utterance a header with the beam, the token tree, cap + beam predictor slots (each with the node's LM step lm_logp | lm_h | lm_c
+ * when an LM is fused: lm_layers 0 = no LM, lm_hidden is then not read), one int per tree node for the emission frames of a timed search
+ * and one for the trie states of a biased one. T = max_frames of the calls that use it. 0 when B, T, H, J, V, beam or cap is not
+ * positive, lm_layers < 0, or lm_layers > 0 with lm_hidden <= 0 (V sizes nothing unless wide and lm_layers > 0).
  * ------------------------------------------------------------------------------------------ */
-size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, int cap);
-int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                      const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
-                      int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
-                      int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
+size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times,
+                                         int bias, int wide);
 
-/* The same search over one chunk of a stream: resumes the beam, token tree and predictor slots from the workspace (laid out for
- * max_frames; zeroed = start of the stream); n_valid int32 [B] = frames of this chunk to decode per utterance (0: the state is left as
- * it is, the outputs describe it). A nonzero status is sticky. A tensor decoded in pieces gives the bits of one call over it. */
-int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                             size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                             int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                             double expand_beam, float slope, int io_dtype, int wdtype, void *stream);
-
-/* The two searches with emission frames: the arguments of their untimed twins plus frames int32 [B,nbest,Lmax], frames[b,r,i] = index of
- * the encoder frame whose joint emitted hyps[b,r,i], absolute from the start of the utterance or stream, written for the first
- * min(len, Lmax) tokens. Frames are non-decreasing along a hypothesis (several tokens may share a frame); the offline search decodes
- * padded frames too, so a frame may lie past an utterance's valid length. hyps, lens, scores and status are the bits of the untimed
- * calls. The workspace has its own layout, the untimed one plus one int per tree node: tsasr_beam_search_timed_workspace_bytes =
- * B * (untimed per-utterance bytes + align16(4 (1 + (max_frames + 1) beam + cap))), 0 for a non-positive argument. A timed stream
- * resumes only a workspace that timed calls started (zeroed = start of the stream) and continued; a zero count leaves the state alone
- * and reads the n-best and their frames out again. The kernel takes 4 cap bytes more LDS than the untimed one. */
-size_t tsasr_beam_search_timed_workspace_bytes(int B, int T, int H, int J, int beam, int cap);
-int tsasr_beam_search_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                            const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                            size_t workspace_bytes, int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V,
-                            int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype,
-                            int wdtype, void *stream, int *frames);
-int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                                   const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                                   size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B,
-                                   int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
-                                   double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames);
-
-/* Beam search with LM fusion (SB/decoders/transducer.py:264-266, 311-351, 386-409 with SB/lobes/models/RNNLM.py): beside the predictor, a
- * recurrent LM = embedding -> `layers` stacked LSTM cells -> `dnn_blocks` blocks of Linear, LayerNorm, LeakyReLU -> Linear to V, evaluated
- * once per hypothesis node on the node's token (blank = the LM's BOS) from the parent's LM state. A non-blank extension by sym scores
- * (logp(a) + logp_joint[sym]) + lm_weight * log_softmax(lm)[sym] in fp64; the top-k, the expand_beam test and the blank copies read the
- * joint alone. 1 <= layers <= 4, 0 <= dnn_blocks <= 2; hidden, emb_dim, dnn_neurons multiples of 4 <= 1024 (dnn_blocks == 0: dnn_neurons
- * == hidden). Matrices in the call's wdtype, torch layouts (w_ih[l] [4 hidden, l == 0 ? emb_dim : hidden], w_hh[l] [4 hidden, hidden],
- * w_dnn[k] [dnn_neurons, k == 0 ? hidden : dnn_neurons], w_out [V, dnn_neurons]); emb [V, emb_dim], biases and LayerNorm vectors fp32
- * (NULL: none). The function takes tsasr_beam_search_stream_timed's arguments, then the LM and its weight: n_valid NULL = the offline search (the
- * workspace is started afresh, max_frames = T), frames NULL = untimed. Each predictor slot of the workspace also holds 64 + 2 layers
- * hidden floats (lm_logp | lm_h | lm_c): the workspace-bytes function below = B * (align16(64 + 24 beam) + align16(8 nodes) + 4 (cap + beam)
- * (J + 2H + 64 + 2 layers hidden) + (times ? align16(4 nodes) : 0)), nodes = 1 + (T + 1) beam + cap. LDS: the search's own plus
- * 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden, dnn_neurons) + 130) bytes, together <= 152 KB. */
+/* LM of the fused beam search: embedding -> `layers` stacked LSTM cells -> `dnn_blocks` blocks of Linear, LayerNorm, LeakyReLU -> Linear
+ * to V (SB/lobes/models/RNNLM.py). 1 <= layers <= 4, 0 <= dnn_blocks <= 2; hidden, emb_dim, dnn_neurons multiples of 4 <= 1024
+ * (dnn_blocks == 0: dnn_neurons == hidden). Matrices in the call's wdtype, torch layouts (w_ih[l] [4 hidden, l == 0 ? emb_dim : hidden],
+ * w_hh[l] [4 hidden, hidden], w_dnn[k] [dnn_neurons, k == 0 ? hidden : dnn_neurons], w_out [V, dnn_neurons]); emb [V, emb_dim], biases
+ * and LayerNorm vectors fp32 (NULL: none). */
 typedef struct tsasr_lm_desc {
     const float *emb;
     const void *w_ih[4], *w_hh[4];
@@ -719,50 +668,13 @@ typedef struct tsasr_lm_desc {
     int layers, hidden, emb_dim, dnn_blocks, dnn_neurons;
     float slope; /* LeakyReLU of the dnn blocks */
 } tsasr_lm_desc;
-size_t tsasr_beam_search_lm_workspace_bytes(int B, int T, int H, int J, int beam, int cap, int lm_layers, int lm_hidden, int times);
-int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                         size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                         int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                         double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                         double lm_weight);
 
-/* The beam search for subword vocabularies (csrc/search.hip beam_search_kernel's WIDE instantiations): the search, outputs, status words and stream
- * resume of the entry points above for 2 <= V <= 1024 and an embedding of E <= 1024 columns (E <= 64: a side operand of the recurrent
- * product; E % 4 == 0: a dense second product; any other E, the frozen one-hot table's V - 1: one gate row per thread over the non-zero
- * columns), 2 <= beam <= min(V, 64). One entry point: tsasr_beam_search_lm's arguments with n_valid NULL = the offline search (the
- * workspace is started afresh, max_frames = T), frames NULL = untimed, lm NULL = no LM fusion. The log-softmax and the top-k are taken
- * over the workgroup in a fixed order: two calls give the same bits. The workspace has the narrow layout with a slot's LM part
- * lm_logp[Vp] | lm_h | lm_c, Vp = round_up(V, 4): tsasr_beam_search_wide_workspace_bytes = B * (align16(64 + 24 beam) + align16(8 nodes)
- * + 4 (cap + beam)(J + 2H + (lm_layers > 0 ? Vp + 2 lm_layers lm_hidden : 0)) + (times ? align16(4 nodes) : 0)), nodes = 1 + (T + 1) beam
- * + cap; 0 for a non-positive size. LDS: 4 (6H + 2J + round_up(E, 4) + Vp + 96) + cap (16 + 4 (times ? 7 : 6)) bytes, with an LM
- * 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden, dnn_neurons) + 2 Vp + 2) more, together <= 156 KB: a shape past it
- * is TSASR_E_INVALID. The narrow entry points are untouched; the host sends V <= 63 with E <= 64 there. */
-size_t tsasr_beam_search_wide_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times);
-int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                           double lm_weight);
-
-/* Beam search with contextual biasing (csrc/search.hip, BeamBiasArgs): phrase lists as prefix tries boost the search by shallow fusion.
- * A graph has states 0 (root) .. S-1; the packed arrays hold the graphs one after another, S + 1 rows each: child_off int32 [rows]
- * (absolute indices into child_tok / child_to; state row r's edges are child_off[r] .. child_off[r + 1], a graph's last row only closes
- * the one before it), child_tok int32 [edges] ascending
- * within a row, child_to int32 [edges] = the graph's own state ids, pending fp64 [rows] = weight * (depth - depth of the deepest
- * terminal on the path), base int32 [B] = first row of utterance b's graph (< 0 or >= rows: b is not biased), weight fp64 [B]. Each
- * hypothesis carries a trie state s (0 at the start). A non-blank extension by v: s has a child c on v -> s' = c, d = w; else
- * d = -pending[s], and if the root has a child c on v -> s' = c, d = d + w, else s' = 0 (no failure links). The extension scores
- * ((logp(a) + logp_joint[v]) [+ lm_weight * lm_logp[v]]) + d in fp64, d last; the top-k, the expand_beam test and the blank copies
- * read the joint alone. The n-best is ranked and reported with (logp - pending[s]) / len; the stored beam keeps logp, so a stream in
- * pieces gives the bits of one call. That child_tok ascends within a row is NOT checked on the device: a binary search reads it, the
- * host constructor (biasing.ContextGraph) guarantees it. The function takes tsasr_beam_search_lm's arguments, then the descriptor:
- * n_valid NULL = the offline search, frames NULL = untimed, lm NULL = no LM; V <= 63 with E <= 64 runs the narrow search, any other
- * shape the wide one (tsasr_beam_search_wide's limits). A NULL descriptor is TSASR_E_INVALID. Workspace: the layout of the same search
- * without a graph plus one int per tree node: tsasr_beam_search_bias_workspace_bytes = B * (align16(64 + 24 beam) + align16(8 nodes) +
- * 4 (cap + beam)(J + 2H + (lm_layers > 0 ? (wide ? round_up(V, 4) : 64) + 2 lm_layers lm_hidden : 0)) + (times ? 2 : 1) align16(4 nodes)),
- * nodes = 1 + (T + 1) beam + cap, wide = V > 63 || E > 64; 0 for a non-positive size. LDS: 4 cap bytes more than the unbiased search. */
+/* Phrase graphs of the biased beam search, as prefix tries. A graph has states 0 (root) .. S-1; the packed arrays hold the graphs one
+ * after another, S + 1 rows each: child_off int32 [rows] (absolute indices into child_tok / child_to; state row r's edges are
+ * child_off[r] .. child_off[r + 1], a graph's last row only closes the one before it), child_tok int32 [edges] ascending within a row,
+ * child_to int32 [edges] = the graph's own state ids, pending fp64 [rows] = weight * (depth - depth of the deepest terminal on the
+ * path), base int32 [B] = first row of utterance b's graph (< 0 or >= rows: b is not biased), weight fp64 [B]. That child_tok ascends
+ * within a row is NOT checked on the device: a binary search reads it, the host constructor (biasing.ContextGraph) guarantees it. */
 typedef struct tsasr_bias_desc {
     const int32_t *child_off, *child_tok, *child_to;
     const double *pending;
@@ -770,14 +682,49 @@ typedef struct tsasr_bias_desc {
     const double *weight;
     int rows, edges;
 } tsasr_bias_desc;
-size_t tsasr_beam_search_bias_workspace_bytes(int B, int T, int H, int J, int E, int V, int beam, int cap, int lm_layers, int lm_hidden,
-                                              int times);
-int tsasr_beam_search_bias(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                           double lm_weight, const tsasr_bias_desc *bias);
+
+/* ------------------------------------------------------------------------------------------
+ * Beam transducer search on the device (SB/decoders/transducer.py:220-373, transducer_beam_search_decode; csrc/search.hip
+ * beam_search_kernel) for the networks tsasr_greedy_decode takes: one persistent workgroup per utterance, one launch decodes the batch.
+ * Scores in fp64 as the host loop; list order as the reference (first maximum of logp / len, appends in top-k order, stable n-best
+ * sort, top-k ties: lower index); the log-softmax and the top-k are taken in a fixed order: two calls give the same bits. Each node of
+ * the hypothesis tree runs its predictor step once. 2 <= beam <= min(V, 64), 1 <= nbest <= 64, cap >= beam = hypotheses a frame may
+ * hold (its A list). workspace >= tsasr_beam_search_workspace_bytes(B, max_frames, H, J, V, beam, cap, lm layers, lm hidden, frames != NULL,
+ * bias != NULL, wide). hyps int32 [B,nbest,Lmax] (first min(len, Lmax) tokens), lens int32 [B,nbest] (-1: the beam holds fewer),
+ * scores fp64 [B,nbest] = logp / len(prediction incl. the blank prefix), status int32 [B]: 0 ok, 1 a frame needed more than cap
+ * hypotheses, 2 token tree full, 3 no hypothesis left to expand; such an utterance stops there, the others are unaffected.
+ * n_valid NULL: the offline search over every frame of enc, padding included; it starts the workspace afresh, leaves the final beam in
+ * it and takes max_frames == T. n_valid int32 [B]: one chunk of a stream; the beam, token tree and predictor slots are resumed from the
+ * workspace (laid out for max_frames; zeroed = start of the stream); n_valid[b] = frames of this chunk to decode (0: the state is left
+ * as it is, the outputs describe it, so a zero-count call reads the n-best out again). A nonzero status is sticky. A tensor decoded in
+ * pieces gives the bits of one offline call over it. Every call on a workspace has the same frames / lm / bias / wide form.
+ * frames NULL: untimed. frames int32 [B,nbest,Lmax]: frames[b,r,i] = index of the encoder frame whose joint emitted hyps[b,r,i],
+ * absolute from the start of the utterance or stream, for the first min(len, Lmax) tokens; non-decreasing along a hypothesis (several
+ * tokens may share a frame; the offline search decodes padded frames too). hyps, lens, scores and status are the bits of the untimed call.
+ * lm NULL: no LM fusion (lm_weight is not read). Else (SB/decoders/transducer.py:264-266, 311-351, 386-409) the LM is evaluated once per
+ * hypothesis node on the node's token (blank = the LM's BOS) from the parent's LM state, and a non-blank extension by sym scores
+ * (logp(a) + logp_joint[sym]) + lm_weight * log_softmax(lm)[sym] in fp64; the top-k, the expand_beam test and the blank copies read the
+ * joint alone.
+ * bias NULL: no phrase graphs. Else each hypothesis carries a trie state s (0 at the start). A non-blank extension by v: s has a child
+ * c on v -> s' = c, d = w; else d = -pending[s], and if the root has a child c on v -> s' = c, d = d + w, else s' = 0 (no failure
+ * links). The extension scores ((logp(a) + logp_joint[v]) [+ lm_weight * lm_logp[v]]) + d in fp64, d last; the top-k, the expand_beam
+ * test and the blank copies read the joint alone. The n-best is ranked and reported with (logp - pending[s]) / len; the stored beam
+ * keeps logp, so a stream in pieces gives the bits of one call.
+ * wide == 0: V <= 63 and E <= 64. LDS: 4 (6H + 2J + 128) + cap (16 + 4 (6 + timed + biased)) bytes, with an LM
+ * 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden, dnn_neurons) + 130) more, together <= 152 KB.
+ * wide != 0, the WIDE instantiations for subword vocabularies: 2 <= V <= 1024 and E <= 1024 (E <= 64: a side operand of the recurrent
+ * product; E % 4 == 0: a dense second product; any other E, the frozen one-hot table's V - 1: one gate row per thread over the non-zero
+ * columns); a character model through them gives the bits of wide == 0. LDS, Vp = round_up(V, 4): 4 (6H + 2J + round_up(E, 4) + Vp +
+ * 96) + cap (16 + 4 (6 + timed + biased)) bytes, with an LM 4 (max(emb_dim, hidden, dnn_neurons) + 2 hidden + max(4 hidden,
+ * dnn_neurons) + 2 Vp + 2) more, together <= 156 KB. A shape past its LDS budget is TSASR_E_INVALID. With a graph, wide must equal
+ * V > 63 || E > 64 (the instantiation the biased search of that shape has always run), else TSASR_E_INVALID.
+ * ------------------------------------------------------------------------------------------ */
+int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
+                      const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
+                      const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T, int max_frames, int J, int H,
+                      int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope,
+                      int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm, double lm_weight,
+                      const tsasr_bias_desc *bias, int wide);
 
 /* ------------------------------------------------------------------------------------------
  * Edit distance of N pairs of symbol sequences with the path choice of the reference's WER/CER statistics (SB/utils/edit_distance.py:

@@ -295,27 +295,19 @@ def test_bias_workspace_bytes():
     tree node; the C side and the wrapper agree."""
     ops = importlib.import_module("ts-asr_amd.ops")
     a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
-    try:
-        lib = importlib.import_module("ts-asr_amd._capi").lib()
-    except Exception:                     # the library is not built: the formula alone
-        lib = None
+    lib = importlib.import_module("ts-asr_amd._capi").lib()
     for B, T, H, J, E, V_, beam, cap in ((32, 250, 512, 640, 28, 29, 15, 512), (1, 1, 4, 4, 1, 2, 2, 2), (3, 40, 128, 160, 99, 100, 4, 37),
                                          (2, 9, 64, 32, 72, 40, 4, 9)):
         wide = V_ > 63 or E > 64
         nodes = a16(4 * (1 + (T + 1) * beam + cap))
         for times in (0, 1):
             for L, Hl in ((0, 0), (2, 40)):
-                if L == 0:
-                    base = (ops.beam_stream_timed_workspace_bytes if times else ops.beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
-                elif wide:
-                    base = ops.beam_wide_workspace_bytes(B, T, H, J, V_, beam, cap, L, Hl, bool(times))
-                else:
-                    base = ops.beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, L, Hl, bool(times))
+                lm_part = ((V_ + 3) // 4 * 4 if wide else 64) + 2 * L * Hl if L > 0 else 0
+                base = B * (a16(64 + 24 * beam) + a16(8 * (1 + (T + 1) * beam + cap)) + 4 * (cap + beam) * (J + 2 * H + lm_part) + times * nodes)
+                assert ops.beam_workspace_bytes(B, T, H, J, V_, beam, cap, L, Hl, bool(times), False, wide) == base
                 want = base + B * nodes
-                assert ops.beam_bias_workspace_bytes(B, T, H, J, E, V_, beam, cap, L, Hl, bool(times)) == want
-                if lib is not None:
-                    assert lib.tsasr_beam_search_bias_workspace_bytes(B, T, H, J, E, V_, beam, cap, L, Hl, times) == want
-    assert ops.beam_bias_workspace_bytes(0, 1, 4, 4, 1, 2, 2, 2) == 0
+                assert ops.beam_workspace_bytes(B, T, H, J, V_, beam, cap, L, Hl, bool(times), True, wide) == want
+                assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, V_, beam, cap, L, Hl, times, 1, int(wide)) == want
+    assert ops.beam_workspace_bytes(0, 1, 4, 4, 2, 2, 2, bias=True) == 0
+    assert lib.tsasr_beam_search_workspace_bytes(2, 8, 128, 160, 29, 4, 16, 1, 0, 0, 1, 0) == 0
     assert ops.beam_wide_lds_bytes(128, 160, 99, 100, 512, bias=True) == ops.beam_wide_lds_bytes(128, 160, 99, 100, 512) + 4 * 512
-    if lib is not None:
-        assert lib.tsasr_beam_search_bias_workspace_bytes(2, 8, 128, 160, 28, 29, 4, 16, 1, 0, 0) == 0

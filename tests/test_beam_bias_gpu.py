@@ -1,4 +1,4 @@
-"""Contextual biasing of the device beam search on the MI355X (csrc/search.hip: tsasr_beam_search_bias): the device route against the
+"""Contextual biasing of the device beam search on the MI355X (csrc/search.hip: tsasr_beam_search with bias): the device route against the
 float64 restatement (tests/helpers/beam_bias_ref.py) and against the host loop, which is the definition; the bit identities (streams in
 pieces, timed and untimed, per-utterance graph lists, no graph = today's entry points); workspace bounds; overflow and the host
 re-decode; StreamingTranscriber in lockstep and in slots; the launcher's refusals; the recipe."""
@@ -270,20 +270,24 @@ def test_stream_pieces_timed_and_lists_bit_identical(brains, golden):
 
 
 class _Recorder:
-    """Stands in for the loaded library and notes which beam entry points were called."""
+    """Stands in for the loaded library and notes, per tsasr_beam_search call, which form it took: whether n_valid, frames, lm and bias
+    were NULL, and the value of wide."""
 
     def __init__(self, lib):
         self._lib, self.calls = lib, []
 
+    def tsasr_beam_search(self, *a):
+        assert len(a) == 40
+        self.calls.append(dict(n_valid=a[12] is None, frames=a[35] is None, lm=a[36] is None, bias=a[38] is None, wide=a[39]))
+        return self._lib.tsasr_beam_search(*a)
+
     def __getattr__(self, name):
-        if name.startswith("tsasr_beam_search") and not name.endswith("_bytes"):
-            self.calls.append(name)
         return getattr(self._lib, name)
 
 
 def test_no_graph_is_todays_entry_points(brains, golden, monkeypatch):
-    """A batch whose entries are all None or empty graphs equals the plain search, bit for bit, and calls only the entry points of the
-    plain search; a real graph calls tsasr_beam_search_bias."""
+    """A batch whose entries are all None or empty graphs equals the plain search, bit for bit, and makes the calls of the plain
+    search, each without a graph (bias NULL); a real graph passes its descriptor in every call."""
     brain, h = brains("fp32")
     m = brain.modules
     enc = T(golden["c1_chain_cat"]["enc_proj"])[:, :24].to(DEV)
@@ -293,8 +297,8 @@ def test_no_graph_is_todays_entry_points(brains, golden, monkeypatch):
         s = searcher(m, 4)
         plain, plain_t = s(enc), s.forward_timed(enc)
         want_calls = list(rec.calls)
-        assert want_calls and all(c in ("tsasr_beam_search", "tsasr_beam_search_timed", "tsasr_beam_search_stream",
-                                        "tsasr_beam_search_stream_timed") for c in want_calls)
+        assert want_calls and all(c["bias"] and c["lm"] and c["wide"] == 0 for c in want_calls)
+        assert [c["frames"] for c in want_calls if c["n_valid"]] == [True, False]        # the untimed and the timed offline launch
         del rec.calls[:]
         nothing = [None, ContextGraph([], 1.0), None, ContextGraph([], 3.0)]
         a, a_t = s(enc, bias=nothing), s.forward_timed(enc, bias=ContextGraph([], 1.0))
@@ -303,11 +307,11 @@ def test_no_graph_is_todays_entry_points(brains, golden, monkeypatch):
         assert a_t[2] == plain_t[2] and bits(a_t[3]) == bits(plain_t[3]) and a_t[5] == plain_t[5]
         del rec.calls[:]
         s(enc, bias=ContextGraph([[3, 4]], 1.0))
-        assert set(rec.calls) == {"tsasr_beam_search_bias"}
+        assert rec.calls and not any(c["bias"] for c in rec.calls)
 
 
 def test_workspace_bounds_and_garbage_start(brains, golden):
-    """The biased search stays inside tsasr_beam_search_bias_workspace_bytes (a 0xA5 canary behind it is intact), and the offline call
+    """The biased search stays inside its tsasr_beam_search_workspace_bytes (a 0xA5 canary behind it is intact), and the offline call
     on a workspace full of garbage gives the bits of the call on a fresh one (it starts the workspace itself, the trie states too)."""
     brain, h = brains("fp32")
     _, graph, _ = reference(golden, "golden50", 4)
@@ -318,8 +322,8 @@ def test_workspace_bounds_and_garbage_start(brains, golden):
         s = searcher(m, 4)
         packed = biasing.pack([graph] * B, enc.device)
         for frames in (False, True):
-            need = ops.beam_bias_workspace_bytes(B, Tn, 128, 160, 28, V, 4, s.cap, 0, 0, frames)
-            assert need == capi.lib().tsasr_beam_search_bias_workspace_bytes(B, Tn, 128, 160, 28, V, 4, s.cap, 0, 0, int(frames))
+            need = ops.beam_workspace_bytes(B, Tn, 128, 160, V, 4, s.cap, 0, 0, frames, bias=True)
+            assert need == capi.lib().tsasr_beam_search_workspace_bytes(B, Tn, 128, 160, V, 4, s.cap, 0, 0, int(frames), 1, 0)
             ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
             got = s._device_beam_call(enc, ops.beam_search, ws[:need], frames=frames, bias=packed)
             assert got[2].tolist() == [0] * B
@@ -479,9 +483,10 @@ def test_streaming_slots_bias_sessions(golden):
 
 # ---- the launcher's refusals --------------------------------------------------------------------------------------------------------------
 def test_launcher_refuses_bad_bias_arguments(brains, golden):
-    """A NULL descriptor, wrong dtypes, a base outside the packed rows, a descriptor without rows, a short workspace: an error before
-    anything is launched (the status words keep their fill). Unsorted child_tok is the one thing nobody checks on the device: the
-    header says so, ContextGraph guarantees the order."""
+    """Wrong dtypes, a base outside the packed rows, a descriptor without rows, a short workspace, a graph with the wrong ``wide``, a
+    greedy stream state without counts: an error before anything is launched (the status words keep their fill). A NULL descriptor is
+    the unbiased search, bit for bit. Unsorted child_tok is the one thing nobody checks on the device: the header says so,
+    ContextGraph guarantees the order."""
     brain, h = brains("fp32")
     m = brain.modules
     enc = T(golden["c1_chain_cat"]["enc_proj"])[:2, :8].to(DEV).contiguous()
@@ -493,23 +498,43 @@ def test_launcher_refuses_bad_bias_arguments(brains, golden):
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
         good = biasing.pack([graph, None], enc.device)
 
-        def call(desc, ws_delta=0):
-            need = ops.beam_bias_workspace_bytes(B, Tn, H, J, E, V, 4, s.cap)
+        def call(desc, ws_delta=0, wide=False, out=None):
+            need = ops.beam_workspace_bytes(B, Tn, H, J, V, 4, s.cap, bias=True)
             ws = torch.empty(need + ws_delta, dtype=torch.uint8, device=DEV)
             hyps = torch.zeros(B, 3, 32, dtype=torch.int32, device=DEV)
             lens = torch.zeros(B, 3, dtype=torch.int32, device=DEV)
             scores = torch.zeros(B, 3, dtype=torch.float64, device=DEV)
             status = torch.full((B,), 77, dtype=torch.int32, device=DEV)
-            rc = ops._beam_bias_launch(enc, ops._beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws), None,
-                                       (capi.ptr(hyps), capi.ptr(lens), capi.ptr(scores), capi.ptr(status)), B, Tn, Tn, J, H, E, V, 0, 4, 3,
-                                       s.cap, 32, 2.3, 2.3, 0.01, wdt, None, None, 0.0, desc)
+            rc = ops._beam_launch(enc, ops._beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws), None,
+                                  (capi.ptr(hyps), capi.ptr(lens), capi.ptr(scores), capi.ptr(status)), B, Tn, Tn, J, H, E, V, 0, 4, 3,
+                                  s.cap, 32, 2.3, 2.3, 0.01, wdt, None, None, 0.0, desc, wide)
             torch.cuda.synchronize()
+            if out is not None:
+                out.update(hyps=hyps.cpu(), lens=lens.cpu(), scores=scores.cpu())
             return rc, status.tolist(), capi.lib().tsasr_last_error().decode()
 
         rc, status, _ = call(ops._beam_bias_desc(good, B, enc.device))
         assert rc == 0 and status == [0, 0]
-        rc, status, msg = call(None)
-        assert rc != 0 and status == [77, 77] and "null bias" in msg
+        got = {}
+        rc, status, _ = call(None, out=got)                  # no graph: the unbiased search, here in the biased (larger) workspace
+        assert rc == 0 and status == [0, 0]
+        plain = ops.beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, 0, 0.01, wdt, 4, 3, 2.3, 2.3, s.cap)
+        assert plain[2].tolist() == [0, 0]
+        rows = [[r for r in range(3) if int(got["lens"][b, r]) >= 0] for b in range(B)]
+        assert [[got["hyps"][b, r, : int(got["lens"][b, r])].tolist() for r in rows[b]] for b in range(B)] == plain[0]
+        assert [len(h) for h in plain[0]] == [len(r) for r in rows] and all(len(t) <= 32 for h in plain[0] for t in h)
+        assert bits([[float(got["scores"][b, r]) for r in rows[b]] for b in range(B)]) == bits(plain[1])
+        rc, status, msg = call(ops._beam_bias_desc(good, B, enc.device), wide=True)      # V = 29, E = 28 with a graph is the narrow search
+        assert rc == -1 and status == [77, 77] and "wide" in msg
+        state = torch.zeros(B, ops.greedy_stream_state_size(H, J), device=DEV)
+        preds = torch.full((B, Tn), 77, dtype=torch.int32, device=DEV)
+        logp = torch.zeros(B, device=DEV)
+        P = capi.ptr
+        rc = capi.lib().tsasr_greedy_decode(P(enc), P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]),
+                                            P(b_head), P(state), None, P(preds), P(logp), B, Tn, J, H, E, V, 0, 0.01, capi.io_dtype(enc), wdt,
+                                            capi.stream_ptr(), 0)
+        torch.cuda.synchronize()
+        assert rc == -1 and bool((preds == 77).all()) and "n_valid" in capi.lib().tsasr_last_error().decode()
         rc, status, msg = call(ops._beam_bias_desc(good, B, enc.device), ws_delta=-16)
         assert rc != 0 and status == [77, 77] and "workspace" in msg
         empty = ops._beam_bias_desc(good, B, enc.device)

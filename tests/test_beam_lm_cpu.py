@@ -147,13 +147,20 @@ def test_lm_workspace_bytes():
     figure (cap 512, beam 15, the reference-default LM: 527 x (64 + 4096) floats per utterance); C side and wrapper agree."""
     ops = importlib.import_module("ts-asr_amd.ops")
     lib = importlib.import_module("ts-asr_amd._capi").lib()
+    a16 = lambda v: -(-v // 16) * 16  # noqa: E731
     for B, T, H, J, beam, cap, L, Hl in ((32, 250, 512, 640, 15, 512, 2, 1024), (1, 1, 4, 4, 2, 2, 1, 4), (3, 40, 128, 160, 4, 37, 3, 40)):
         for times in (0, 1):
-            base = (ops.beam_stream_timed_workspace_bytes if times else ops.beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
+            nodes = 1 + (T + 1) * beam + cap
+            base = B * (a16(64 + 24 * beam) + a16(8 * nodes) + 4 * (cap + beam) * (J + 2 * H) + times * a16(4 * nodes))
+            assert ops.beam_workspace_bytes(B, T, H, J, 29, beam, cap, times=bool(times)) == base
             want = base + B * 4 * (cap + beam) * (64 + 2 * L * Hl)
-            assert lib.tsasr_beam_search_lm_workspace_bytes(B, T, H, J, beam, cap, L, Hl, times) == want
-            assert ops.beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, L, Hl, bool(times)) == want
-    per_utt = ops.beam_stream_lm_workspace_bytes(1, 250, 512, 640, 15, 512, 2, 1024) - ops.beam_stream_workspace_bytes(1, 250, 512, 640, 15, 512)
+            assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, 29, beam, cap, L, Hl, times, 0, 0) == want
+            assert ops.beam_workspace_bytes(B, T, H, J, 29, beam, cap, L, Hl, bool(times)) == want
+            # lm_layers = 0 means no LM: the LM layout without layers is the plain one (lm_hidden is not read)
+            assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, 29, beam, cap, 0, Hl, times, 0, 0) == base
+            assert ops.beam_workspace_bytes(B, T, H, J, 29, beam, cap, 0, Hl, bool(times)) == base
+    per_utt = ops.beam_workspace_bytes(1, 250, 512, 640, 29, 15, 512, 2, 1024) - ops.beam_workspace_bytes(1, 250, 512, 640, 29, 15, 512)
     assert per_utt == 527 * (64 + 4096) * 4 == 8_769_280
-    assert lib.tsasr_beam_search_lm_workspace_bytes(32, 250, 512, 640, 15, 512, 0, 1024, 0) == 0
-    assert ops.beam_stream_lm_workspace_bytes(32, 250, 512, 640, 15, 512, 2, 0) == 0
+    assert lib.tsasr_beam_search_workspace_bytes(32, 250, 512, 640, 29, 15, 512, 0, 1024, 0, 0, 0) == \
+        lib.tsasr_beam_search_workspace_bytes(32, 250, 512, 640, 29, 15, 512, 0, 0, 0, 0, 0) == 113_355_776
+    assert ops.beam_workspace_bytes(32, 250, 512, 640, 29, 15, 512, 2, 0) == 0

@@ -1,4 +1,4 @@
-"""Beam transducer search with LM fusion on the MI355X (csrc/search.hip: tsasr_beam_search_lm): the device route against the reference's
+"""Beam transducer search with LM fusion on the MI355X (csrc/search.hip: tsasr_beam_search with lm): the device route against the reference's
 own hypotheses (tests/golden/c1_beam_lm.npz), the float64 restatement (tests/helpers/beam_lm_ref.py) and the host loop; LMs the kernel
 does not take; lm_weight = 0; streams; overflow; the reference-default LM's width; the launcher's argument checks; the recipe."""
 import contextlib
@@ -199,13 +199,13 @@ def test_host_loop_takes_other_lms(brains, golden):
 
 
 def _entry_points(s, enc, nv):
-    """(n-best, score bits, status) of the four LM-free entry points on enc."""
+    """(n-best, score bits, status) of the four LM-free forms (offline / stream, untimed / timed) on enc."""
     out = []
     for frames in (False, True):
         r = s._device_beam_call(enc, ops.beam_search, frames=frames)
         out.append((r[0], bits(r[1]), r[2].tolist()) + tuple(r[3:]))
-        size = ops.beam_stream_timed_workspace_bytes if frames else ops.beam_stream_workspace_bytes
-        ws = torch.zeros(size(enc.shape[0], enc.shape[1], 128, 160, s.beam_size, s.cap), dtype=torch.uint8, device=enc.device)
+        ws = torch.zeros(ops.beam_workspace_bytes(enc.shape[0], enc.shape[1], 128, 160, V, s.beam_size, s.cap, times=frames),
+                         dtype=torch.uint8, device=enc.device)
         r = s._device_beam_call(enc, ops.beam_search_stream, ws, nv, enc.shape[1], frames=frames)
         out.append((r[0], bits(r[1]), r[2].tolist()) + tuple(r[3:]))
     return out
@@ -213,7 +213,7 @@ def _entry_points(s, enc, nv):
 
 def test_lm_weight_zero_is_the_plain_search(brains, lms, golden):
     """A searcher given an LM with lm_weight = 0 returns the bits of the searcher without it (hypotheses, scores, status); the four
-    LM-free entry points return the same bits before and after a fused search ran in the process."""
+    LM-free forms return the same bits before and after a fused search ran in the process."""
     brain, h = brains("fp32")
     m = brain.modules
     enc = T(golden["c1_chain_cat"]["enc_proj"]).to(DEV)
@@ -342,8 +342,8 @@ def test_reference_default_lm_width(brains, golden, monkeypatch):
     torch.manual_seed(17)
     lm = nnet.RNNLM(V, return_hidden=True).to(DEV).eval()
     enc = T(golden["c1_chain_cat"]["enc_proj"])[:2, :8].to(DEV)
-    need = ops.beam_stream_lm_workspace_bytes(2, 8, 128, 160, 4, dec.BEAM_CAP, 2, 1024)
-    assert need == capi.lib().tsasr_beam_search_lm_workspace_bytes(2, 8, 128, 160, 4, dec.BEAM_CAP, 2, 1024, 0)
+    need = ops.beam_workspace_bytes(2, 8, 128, 160, V, 4, dec.BEAM_CAP, 2, 1024)
+    assert need == capi.lib().tsasr_beam_search_workspace_bytes(2, 8, 128, 160, V, 4, dec.BEAM_CAP, 2, 1024, 0, 0, 0)
     ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
     with blank_shift(m.transducer_head, float(golden["c1_beam_lm"]["blank_bias"])), torch.no_grad():
         s = searcher(m, 4, lm, 0.3)
@@ -369,15 +369,15 @@ def test_launcher_refuses_bad_lm_arguments(brains, lms, golden):
 
         def call(lm_args, cap=dec.BEAM_CAP, ws_bytes=None):
             desc, weight, layers, hidden = ops._beam_lm_desc(lm_args, V, wdt)
-            need = ops.beam_stream_lm_workspace_bytes(B, Tn, H, J, 4, cap, min(layers, 4), hidden)
+            need = ops.beam_workspace_bytes(B, Tn, H, J, V, 4, cap, min(layers, 4), hidden)
             ws = torch.empty(need if ws_bytes is None else need + ws_bytes, dtype=torch.uint8, device=DEV)
             hyps = torch.zeros(B, 3, 32, dtype=torch.int32, device=DEV)
             lens = torch.zeros(B, 3, dtype=torch.int32, device=DEV)
             scores = torch.zeros(B, 3, dtype=torch.float64, device=DEV)
             status = torch.full((B,), 77, dtype=torch.int32, device=DEV)
-            rc = ops._beam_lm_launch(enc, ops._beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws), None,
-                                     (capi.ptr(hyps), capi.ptr(lens), capi.ptr(scores), capi.ptr(status)), B, Tn, Tn, J, H, E, V, 0, 4, 3, cap, 32,
-                                     2.3, 2.3, 0.01, wdt, None, desc, weight)
+            rc = ops._beam_launch(enc, ops._beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws), None,
+                                  (capi.ptr(hyps), capi.ptr(lens), capi.ptr(scores), capi.ptr(status)), B, Tn, Tn, J, H, E, V, 0, 4, 3, cap, 32,
+                                  2.3, 2.3, 0.01, wdt, None, desc, weight, None, False)
             torch.cuda.synchronize()
             return rc, status.tolist(), capi.lib().tsasr_last_error().decode()
 

@@ -21,10 +21,17 @@ def _net(H=128, J=160, E=29, V=29, wdt=torch.float32):
 
 @pytest.fixture
 def no_device(monkeypatch):
-    """Any call into the library or the device fails the test: validation has to come first."""
+    """Any call into the library or the device fails the test: validation has to come first. The one library function the checks
+    themselves read is the workspace's size, a function of the shape alone that touches no device."""
     def boom(*a, **k):
         raise AssertionError("reached the device before the arguments were checked")
-    monkeypatch.setattr(capi, "lib", boom)
+
+    class SizeOnly:
+        tsasr_beam_search_workspace_bytes = capi.lib().tsasr_beam_search_workspace_bytes
+
+        def __getattr__(self, name):
+            boom()
+    monkeypatch.setattr(capi, "lib", SizeOnly)
     monkeypatch.setattr(capi, "require_gpu", boom)
 
 
@@ -61,7 +68,7 @@ def test_beam_search_wrapper_checks(no_device, case):
 def test_beam_search_stream_wrapper_checks(no_device):
     table, mats, b_ih, b_hh, b_proj, b_head = _net()
     enc = torch.zeros(2, 8, 160)
-    need = ops.beam_stream_workspace_bytes(2, 100, 128, 160, 4, 64)
+    need = ops.beam_workspace_bytes(2, 100, 128, 160, 29, 4, 64)
     args = (table, mats, b_ih, b_hh, b_proj, b_head, 0, 0.01, capi.F32, 4, 2, 2.3, 2.3, 64)
     with torch.no_grad():
         with pytest.raises(ValueError, match="workspace"):
@@ -89,15 +96,35 @@ def test_workspace_bytes_formula_and_monotone():
     base = dict(B=32, T=250, H=512, J=640, beam=15, cap=512)
     for kw in (base, dict(base, T=4000), dict(base, B=1, T=1, H=4, J=4, beam=2, cap=2), dict(base, beam=4, cap=37)):
         args = [kw[k] for k in ("B", "T", "H", "J", "beam", "cap")]
-        assert lib.tsasr_beam_search_workspace_bytes(*args) == ops.beam_stream_workspace_bytes(*args) == _formula(*args)
+        plain = args[:4] + [29] + args[4:]                   # the plain narrow search: no LM, untimed, no graph (V sizes nothing)
+        assert lib.tsasr_beam_search_workspace_bytes(*plain, 0, 0, 0, 0, 0) == ops.beam_workspace_bytes(*plain) == _formula(*args)
     for k in base:
         prev = 0
         for f in (1, 2, 3, 5, 8):
             kw = dict(base, **{k: base[k] * f})
-            n = ops.beam_stream_workspace_bytes(*[kw[x] for x in ("B", "T", "H", "J", "beam", "cap")])
+            n = ops.beam_workspace_bytes(*[kw[x] for x in ("B", "T", "H", "J")], 29, kw["beam"], kw["cap"])
             assert n > prev, k
             prev = n
     # configs[1] (B = 32, T' = 250, beam 15, default cap 512) and configs[4] (T' = 4000): the sizes DESIGN.md quotes
     assert _formula(32, 250, 512, 640, 15, 512) == 113_355_776
     assert _formula(32, 4000, 512, 640, 15, 512) == 127_755_776
-    assert ops.beam_stream_workspace_bytes(0, 250, 512, 640, 15, 512) == 0
+    assert ops.beam_workspace_bytes(0, 250, 512, 640, 29, 15, 512) == 0
+
+
+def test_workspace_bytes_every_form():
+    """times x lm x bias x wide at three shapes against the one formula of include/tsasr_hip.h, written out here. lm on: the shape's own
+    LM, or one layer of 32 where it names none."""
+    lib = capi.lib()
+    a16 = lambda v: -(-v // 16) * 16  # noqa: E731
+    for B, T, H, J, V, beam, cap, Ll, Hl in ((3, 24, 64, 64, 100, 4, 512, 0, 0), (2, 12, 512, 640, 1024, 4, 512, 2, 1024),
+                                             (1, 4096, 64, 64, 101, 15, 33, 1, 32)):
+        for times in (0, 1):
+            for lm in (0, 1):
+                for bias in (0, 1):
+                    for wide in (0, 1):
+                        L, Hh = ((Ll or 1), (Hl or 32)) if lm else (0, 0)
+                        nodes = 1 + (T + 1) * beam + cap
+                        lmw = (-(-V // 4) * 4 if wide else 64) + 2 * L * Hh if L > 0 else 0
+                        want = B * (a16(64 + 24 * beam) + a16(8 * nodes) + 4 * (cap + beam) * (J + 2 * H + lmw) + (times + bias) * a16(4 * nodes))
+                        assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, V, beam, cap, L, Hh, times, bias, wide) == want
+                        assert ops.beam_workspace_bytes(B, T, H, J, V, beam, cap, L, Hh, bool(times), bool(bias), bool(wide)) == want

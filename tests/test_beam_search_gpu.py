@@ -1,4 +1,4 @@
-"""Beam transducer search on the MI355X (csrc/search.hip: tsasr_beam_search / tsasr_beam_search_stream) against the reference's golden
+"""Beam transducer search on the MI355X (csrc/search.hip: tsasr_beam_search, offline and in streams) against the reference's golden
 hypotheses, the CPU oracle and the host loop it replaces; determinism, streams decoded in pieces, overflow, the streaming transcriber and
 the recipe's TEST stage."""
 import contextlib

@@ -266,7 +266,7 @@ def test_gates(monkeypatch):
         ops.beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, 0, 0.01, wdt, 4, 3, 2.3, 2.3, 4000, wide=True)
     with torch.no_grad(), pytest.raises(ValueError, match="E <= 64"):             # without the flag the wrapper keeps the narrow limits
         ops.beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, 0, 0.01, wdt, 4, 3, 2.3, 2.3, 512)
-    # a character model (V = 29, one-hot E = 28) still takes the narrow entry points: the wide launcher is not called
+    # a character model (V = 29, one-hot E = 28) still takes the narrow search: every launch has wide off and no LM
     name, spec = JW.NARROW_CASE
     V, _, H, J, _ = spec
     net = {k: torch.from_numpy(v) for k, v in JW.greedy_net(name, spec=spec).items()}
@@ -282,28 +282,32 @@ def test_gates(monkeypatch):
     enc29 = net["enc"][:, :4].contiguous().to(DEV)
     assert narrow._device_beam_ok(enc29) and not narrow._beam_is_wide()
 
-    def refuse(*a, **k):
-        raise AssertionError("a character model reached the LM / wide launcher")
-    monkeypatch.setattr(ops, "_beam_lm_launch", refuse)
+    real, launches = ops._beam_launch, []
+
+    def spy(*a):                                                             # (..., fr, lm_desc, lm_weight, bias_desc, wide)
+        assert a[-4] is None and not a[-1], "a character model reached the LM / wide search"
+        launches.append(a[-1])
+        return real(*a)
+    monkeypatch.setattr(ops, "_beam_launch", spy)
     before = dec.BEAM_HOST_REDECODES["utterances"]
     _, _, nb, _ = narrow(enc29)
-    assert len(nb) == enc29.shape[0] and dec.BEAM_HOST_REDECODES["utterances"] == before
+    assert launches and len(nb) == enc29.shape[0] and dec.BEAM_HOST_REDECODES["utterances"] == before
 
 
 # ---- 9: workspace -------------------------------------------------------------------------------------------------------------------------
 def test_workspace_bytes_and_guard_region():
-    fn = capi.lib().tsasr_beam_search_wide_workspace_bytes
+    fn = lambda *a: capi.lib().tsasr_beam_search_workspace_bytes(*a, 0, 1)   # noqa: E731  (no graph, wide)
     a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
     for B, T, H, J, V, beam, cap, Ll, Hl, times in ((3, 24, 64, 64, 100, 4, 512, 0, 0, 0), (2, 12, 512, 640, 1022, 15, 77, 2, 1024, 1)):
         nodes = 1 + (T + 1) * beam + cap
         lmw = (V + 3) // 4 * 4 + 2 * Ll * Hl if Ll else 0
         want = B * (a16(64 + 24 * beam) + a16(8 * nodes) + 4 * (cap + beam) * (J + 2 * H + lmw) + (a16(4 * nodes) if times else 0))
-        assert fn(B, T, H, J, V, beam, cap, Ll, Hl, times) == want == ops.beam_wide_workspace_bytes(B, T, H, J, V, beam, cap, Ll, Hl, bool(times))
+        assert fn(B, T, H, J, V, beam, cap, Ll, Hl, times) == want == ops.beam_workspace_bytes(B, T, H, J, V, beam, cap, Ll, Hl, bool(times), wide=True)
     assert fn(0, 24, 64, 64, 100, 4, 512, 0, 0, 0) == 0
     s, enc = searcher("v1024_big", 4)
     enc = enc.to(DEV)
     B, T, J = enc.shape
-    need = ops.beam_wide_workspace_bytes(B, T, 512, J, 1024, 4, s.cap, times=True)
+    need = ops.beam_workspace_bytes(B, T, 512, J, 1024, 4, s.cap, times=True, wide=True)
     buf = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
     with torch.no_grad():
         nb, sc, status, fr = s._device_beam_call(enc.contiguous(), ops.beam_search, workspace=buf[:need], frames=True)
@@ -347,7 +351,7 @@ def _narrow_searcher(with_lm):
 def test_character_model_same_bits_through_the_wide_entry_point(dtype, timed, with_lm):
     """WIDE switches widths, the embedding's route, the log-softmax / top-k and who appends; at V = 29, E = 28 none of them changes a
     bit: wave 0 holds the whole vocabulary (the other waves add a maximum of -inf and a sum of +0), both top-k orders are (value
-    descending, index ascending), and E <= 64 takes the side operand. So tsasr_beam_search_wide gives the narrow entry points' hypotheses,
+    descending, index ascending), and E <= 64 takes the side operand. So tsasr_beam_search with wide = 1 gives the hypotheses of wide = 0,
     lengths, status, fp64 scores and frames."""
     s, enc = _narrow_searcher(with_lm)
     enc = enc.to(DEV, dtype)

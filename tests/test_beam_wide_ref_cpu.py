@@ -71,12 +71,19 @@ def test_entry_points_are_declared_and_prototyped(pkg):
     capi = importlib.import_module("ts-asr_amd._capi")
     header = open(os.path.join(ROOT, "include", "tsasr_hip.h")).read()
     declared = set(re.findall(r"\b(tsasr_[a-z0-9_]+)\s*\(", header))
-    for name in ("tsasr_beam_search_wide", "tsasr_beam_search_wide_workspace_bytes"):
+    for name in ("tsasr_greedy_decode", "tsasr_beam_search", "tsasr_beam_search_workspace_bytes"):
         assert name in declared and name in capi.exported_symbols(), name
+    # the thirteen entry points folded into those three: none is declared, prototyped or exported
+    gone = ["tsasr_greedy_decode" + s for s in ("_stream", "_wide", "_stream_wide")]
+    gone += ["tsasr_beam_search" + s for s in ("_stream", "_timed", "_stream_timed", "_lm", "_wide", "_bias")]
+    gone += ["tsasr_beam_search" + s + "_workspace_bytes" for s in ("_timed", "_lm", "_wide", "_bias")]
+    assert len(gone) == 13
+    for name in gone:
+        assert name not in declared and name not in capi.exported_symbols() and not hasattr(capi.lib(), name), name
 
 
 def test_workspace_and_lds_formulas(pkg):
-    """ops.beam_wide_workspace_bytes / beam_wide_lds_bytes against the formulas of include/tsasr_hip.h, written out here."""
+    """ops.beam_workspace_bytes with ``wide`` / beam_wide_lds_bytes against the formulas of include/tsasr_hip.h, written out here."""
     ops = importlib.import_module("ts-asr_amd.ops")
     a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
     for B, T, H, J, V, beam, cap, Ll, Hl, times in ((3, 24, 64, 64, 100, 4, 512, 0, 0, False), (2, 12, 512, 640, 1024, 4, 512, 2, 1024, True),
@@ -84,8 +91,8 @@ def test_workspace_and_lds_formulas(pkg):
         nodes = 1 + (T + 1) * beam + cap
         lmw = (V + 3) // 4 * 4 + 2 * Ll * Hl if Ll else 0
         want = B * (a16(64 + 24 * beam) + a16(8 * nodes) + 4 * (cap + beam) * (J + 2 * H + lmw) + (a16(4 * nodes) if times else 0))
-        assert ops.beam_wide_workspace_bytes(B, T, H, J, V, beam, cap, Ll, Hl, times) == want
-    assert ops.beam_wide_workspace_bytes(0, 24, 64, 64, 100, 4, 512) == 0
+        assert ops.beam_workspace_bytes(B, T, H, J, V, beam, cap, Ll, Hl, times, wide=True) == want
+    assert ops.beam_workspace_bytes(0, 24, 64, 64, 100, 4, 512, wide=True) == 0
     # H = 512, J = 640, V = 1024, E = 1023, cap 512, a 2 x 1024 LM (emb 1024, no dnn block), timed
     base = 4 * (6 * 512 + 2 * 640 + 1024 + 1024 + 96) + 512 * (16 + 28)
     assert ops.beam_wide_lds_bytes(512, 640, 1023, 1024, 512) == base

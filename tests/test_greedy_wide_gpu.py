@@ -67,10 +67,10 @@ def test_device_greedy_matches_float64(golden, name, dtype):
     table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
     preds = torch.empty(B, T, dtype=torch.int32, device=DEV)
     logp = torch.empty(B, dtype=torch.float32, device=DEV)
-    C.check(C.lib().tsasr_greedy_decode_wide(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                             C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, mats[1].shape[1],
-                                             table.shape[1], mats[3].shape[0], 0, 0.01, C.io_dtype(enc), wdt, C.stream_ptr()),
-            "tsasr_greedy_decode_wide")
+    C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                        C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), None, None, C.ptr(preds), C.ptr(logp), B, T, J,
+                                        mats[1].shape[1], table.shape[1], mats[3].shape[0], 0, 0.01, C.io_dtype(enc), wdt, C.stream_ptr(), 1),
+            "tsasr_greedy_decode (wide)")
     sums = logp.cpu().numpy().astype(np.float64)
     assert float(score) == float(logp.exp().mean())
     for b in range(B):
@@ -116,9 +116,9 @@ def test_stream_form_gives_the_one_call_bits(name, dtype):
     assert tuple(state["dev"].shape) == (B, ops.greedy_stream_state_size(JW.GREEDY_CASES[name][2], J))
 
 
-def test_character_models_keep_the_narrow_kernel():
-    """V = 29 with the one-hot table: the searcher still calls tsasr_greedy_decode, and the wide entry point, given the same network, emits
-    the same preds - the narrow instantiation is what it was, the wide one agrees with it where both apply."""
+def test_character_models_keep_the_narrow_kernel(monkeypatch):
+    """V = 29 with the one-hot table: the searcher still calls tsasr_greedy_decode with wide = 0, and wide = 1, given the same network,
+    emits the same preds - the narrow instantiation is what it was, the wide one agrees with it where both apply."""
     C = importlib.import_module("ts-asr_amd._capi")
     name, spec = JW.NARROW_CASE
     s, enc = searcher(name, spec)
@@ -126,17 +126,21 @@ def test_character_models_keep_the_narrow_kernel():
     assert JW.greedy_case_ok(want)[0]
     enc = enc.to(DEV)
     assert s._device_greedy_ok(enc) and not s._greedy_is_wide()
+    real, wides = C.lib().tsasr_greedy_decode, []
+    monkeypatch.setattr(C.lib(), "tsasr_greedy_decode", lambda *a: (wides.append(a[-1]), real(*a))[1])
     hyps, _, _, _, frames, _ = s.forward_timed(enc)
+    monkeypatch.undo()
+    assert wides == [0]                                        # the searcher's own call
     assert hyps == [r["tokens"] for r in want] and frames == [r["frames"] for r in want]
     B, T, J = enc.shape
     table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
     out = {}
-    for name in ("tsasr_greedy_decode", "tsasr_greedy_decode_wide"):
+    for wide in (0, 1):
         preds = torch.empty(B, T, dtype=torch.int32, device=DEV)
         logp = torch.empty(B, dtype=torch.float32, device=DEV)
-        C.check(getattr(C.lib(), name)(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                       C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, 64, table.shape[1], 29, 0,
-                                       0.01, C.io_dtype(enc), wdt, C.stream_ptr()), name)
-        out[name] = (preds.cpu(), logp.cpu())
-    assert torch.equal(out["tsasr_greedy_decode"][0], out["tsasr_greedy_decode_wide"][0])
-    torch.testing.assert_close(out["tsasr_greedy_decode"][1], out["tsasr_greedy_decode_wide"][1], atol=1e-5, rtol=1e-5)
+        C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                            C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), None, None, C.ptr(preds), C.ptr(logp), B, T, J, 64,
+                                            table.shape[1], 29, 0, 0.01, C.io_dtype(enc), wdt, C.stream_ptr(), wide), f"wide={wide}")
+        out[wide] = (preds.cpu(), logp.cpu())
+    assert torch.equal(out[0][0], out[1][0])
+    torch.testing.assert_close(out[0][1], out[1][1], atol=1e-5, rtol=1e-5)

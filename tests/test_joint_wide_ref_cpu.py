@@ -138,5 +138,7 @@ def test_greedy_entry_points_are_declared(pkg):
     capi = importlib.import_module("ts-asr_amd._capi")
     header = open(os.path.join(ROOT, "include", "tsasr_hip.h")).read()
     declared = set(re.findall(r"\b(tsasr_[a-z0-9_]+)\s*\(", header))
-    for name in ("tsasr_greedy_decode_wide", "tsasr_greedy_decode_stream_wide"):
-        assert name in declared and name in capi.exported_symbols(), name
+    assert "tsasr_greedy_decode" in declared and "tsasr_greedy_decode" in capi.exported_symbols()
+    for suffix in ("_stream", "_wide", "_stream_wide"):          # folded into the one entry point (state / n_valid NULL, wide)
+        name = "tsasr_greedy_decode" + suffix
+        assert name not in declared and name not in capi.exported_symbols() and not hasattr(capi.lib(), name), name

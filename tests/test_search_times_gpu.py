@@ -365,7 +365,7 @@ def test_overflow_redecode_carries_frames(brains, golden):
 
 
 def test_timed_c_abi_truncation_and_workspace(brains, golden):
-    """A direct tsasr_beam_search_timed call with Lmax below the longest hypothesis writes the first Lmax frames of each hypothesis and
+    """A direct tsasr_beam_search call with frames and Lmax below the longest hypothesis writes the first Lmax frames of each hypothesis and
     nothing past them (canary after the buffer, untouched tails inside it); the timed workspace is at least the untimed one and 0 for
     non-positive arguments."""
     brain, h = brains("fp32")
@@ -378,11 +378,11 @@ def test_timed_c_abi_truncation_and_workspace(brains, golden):
         want = s.forward_timed(enc)
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
         H, J, E, V = mats[1].shape[1], enc.shape[-1], table.shape[1], mats[3].shape[0]
-        need = lib.tsasr_beam_search_timed_workspace_bytes(B, frames, H, J, beam, cap)
-        assert need >= lib.tsasr_beam_search_workspace_bytes(B, frames, H, J, beam, cap) > 0
-        assert need == ops.beam_stream_timed_workspace_bytes(B, frames, H, J, beam, cap)
-        for args in ((0, frames, H, J, beam, cap), (B, 0, H, J, beam, cap), (B, frames, H, J, beam, -1)):
-            assert lib.tsasr_beam_search_timed_workspace_bytes(*args) == 0
+        need = lib.tsasr_beam_search_workspace_bytes(B, frames, H, J, V, beam, cap, 0, 0, 1, 0, 0)
+        assert need >= lib.tsasr_beam_search_workspace_bytes(B, frames, H, J, V, beam, cap, 0, 0, 0, 0, 0) > 0
+        assert need == ops.beam_workspace_bytes(B, frames, H, J, V, beam, cap, times=True)
+        for args in ((0, frames, H, J, V, beam, cap), (B, 0, H, J, V, beam, cap), (B, frames, H, J, V, beam, -1)):
+            assert lib.tsasr_beam_search_workspace_bytes(*args, 0, 0, 1, 0, 0) == 0
         ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
         n = B * nbest * Lmax
         hyps = torch.full((n + 64,), -77, dtype=torch.int32, device=DEV)
@@ -391,10 +391,11 @@ def test_timed_c_abi_truncation_and_workspace(brains, golden):
         scores = torch.empty(B, nbest, dtype=torch.float64, device=DEV)
         status = torch.empty(B, dtype=torch.int32, device=DEV)
         P = capi.ptr
-        capi.check(lib.tsasr_beam_search_timed(P(enc), P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]),
-                                               P(b_head), P(ws), ws.numel(), P(hyps), P(lens), P(scores), P(status), B, frames, J, H, E, V, 0,
-                                               beam, nbest, cap, Lmax, 2.3, 2.3, 0.01, capi.io_dtype(enc), wdt, capi.stream_ptr(), P(fr)),
-                   "tsasr_beam_search_timed")
+        capi.check(lib.tsasr_beam_search(P(enc), P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]),
+                                         P(b_head), P(ws), ws.numel(), None, P(hyps), P(lens), P(scores), P(status), B, frames, frames, J, H, E,
+                                         V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01, capi.io_dtype(enc), wdt, capi.stream_ptr(), P(fr), None,
+                                         0.0, None, 0),
+                   "tsasr_beam_search (frames)")
         torch.cuda.synchronize()
     assert status.cpu().tolist() == [0] * B
     assert max(len(t) for nb in want[2] for t in nb) > Lmax

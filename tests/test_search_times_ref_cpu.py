@@ -182,11 +182,15 @@ def test_timed_workspace_bytes_formula():
     lib = capi.lib()
     a16 = lambda v: -(-v // 16) * 16  # noqa: E731
     for B, T, H, J, beam, cap in ((32, 250, 512, 640, 15, 512), (1, 1, 4, 4, 2, 2), (3, 40, 128, 160, 4, 37), (6, 4000, 512, 640, 15, 512)):
-        want = ops.beam_stream_workspace_bytes(B, T, H, J, beam, cap) + B * a16(4 * (1 + (T + 1) * beam + cap))
-        assert lib.tsasr_beam_search_timed_workspace_bytes(B, T, H, J, beam, cap) == ops.beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap) == want
-        assert want >= lib.tsasr_beam_search_workspace_bytes(B, T, H, J, beam, cap)
-    for bad in ((0, 250, 512, 640, 15, 512), (32, -1, 512, 640, 15, 512), (32, 250, 512, 640, 15, 0)):
-        assert lib.tsasr_beam_search_timed_workspace_bytes(*bad) == 0 == ops.beam_stream_timed_workspace_bytes(*bad)
+        nodes = 1 + (T + 1) * beam + cap
+        untimed = B * (a16(64 + 24 * beam) + a16(8 * nodes) + 4 * (cap + beam) * (J + 2 * H))
+        want = untimed + B * a16(4 * nodes)
+        assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, 29, beam, cap, 0, 0, 1, 0, 0) == want
+        assert ops.beam_workspace_bytes(B, T, H, J, 29, beam, cap, times=True) == want
+        assert want >= lib.tsasr_beam_search_workspace_bytes(B, T, H, J, 29, beam, cap, 0, 0, 0, 0, 0) == untimed
+    for B, T, H, J, beam, cap in ((0, 250, 512, 640, 15, 512), (32, -1, 512, 640, 15, 512), (32, 250, 512, 640, 15, 0)):
+        assert lib.tsasr_beam_search_workspace_bytes(B, T, H, J, 29, beam, cap, 0, 0, 1, 0, 0) == 0
+        assert ops.beam_workspace_bytes(B, T, H, J, 29, beam, cap, times=True) == 0
 
 
 def test_write_hyp_ctm(tmp_path):

@@ -156,8 +156,9 @@ def test_greedy_stream_pieces_bit_identical(mods, dtype):
     preds = torch.empty(B, Tn, dtype=torch.int32, device=DEV)
     logp = torch.empty(B, dtype=torch.float32, device=DEV)
     C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                        C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, Tn, J, Hd, table.shape[1],
-                                        mats[3].shape[0], int(srch.blank_id), slope, C.io_dtype(enc), wdt, C.stream_ptr()), "tsasr_greedy_decode")
+                                        C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), None, None, C.ptr(preds), C.ptr(logp), B, Tn, J, Hd,
+                                        table.shape[1], mats[3].shape[0], int(srch.blank_id), slope, C.io_dtype(enc), wdt, C.stream_ptr(), 0),
+            "tsasr_greedy_decode")
     assert int((preds >= 0).sum()) > 0
     with torch.no_grad():
         for step in (1, 7, 40):

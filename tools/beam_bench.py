@@ -8,7 +8,7 @@ reported per utterance. Expansions per frame and predictor steps computed come f
 the device's own inputs (count only; the counts do not depend on which route ran).
 
     python tools/beam_bench.py [--reps 5] [--host-utts 2] [--frames 250]
-    python tools/beam_bench.py --times [--reps 50] [--ab-lib OTHER.so]     # the timed launch (tsasr_beam_search_timed) beside the untimed one
+    python tools/beam_bench.py --times [--reps 50] [--ab-lib OTHER.so]     # the timed launch (tsasr_beam_search with frames) beside the untimed one
 
 --times: the launch alone, without the host read-back: the stream is pre-loaded, events sit around each launch, the two forms
 alternate, median of --reps after warm-up (the method of profiles/align_notes.md); B = 32, T' = --frames, beam 15, bf16 and fp32.
@@ -16,7 +16,7 @@ alternate, median of --reps after warm-up (the method of profiles/align_notes.md
 
     python tools/beam_bench.py --lm [--reps 5] [--host-utts 1] [--lm-weight 0.3] [--ab-lib OTHER.so]
 
---lm: the LM-fused launch (tsasr_beam_search_lm, the reference-default RNNLM: 2 x 1024 LSTM, embedding 128, one 512 block; seeded initial
+--lm: the LM-fused launch (tsasr_beam_search with lm, the reference-default RNNLM: 2 x 1024 LSTM, embedding 128, one 512 block; seeded initial
 weights) beside the unfused launch in the same loop, by the method of --times; then the host loop with the same LM (TSASR_BEAM_KERNEL=0)
 over --host-utts utterances, wall clock per utterance. LM steps per frame = hypothesis nodes expanded (one LM step each, as predictor steps).
 
@@ -30,7 +30,7 @@ symbols into both, --times asks both for the emission frames.
 
     python tools/beam_bench.py --bias 16 [--lm] [--times] [--vocab 256] [--ab-lib OTHER.so] [--bias-weight 1.0] [--reps 5]
 
---bias N: contextual biasing (tsasr_beam_search_bias): one graph of N seeded phrases of 3-6 tokens for every utterance; the biased search
+--bias N: contextual biasing (tsasr_beam_search with bias): one graph of N seeded phrases of 3-6 tokens for every utterance; the biased search
 beside the unbiased one through the searcher's own call (launch and read-back of the n-best), the two forms alternating, median of --reps,
 beams --beams; per-utterance time = batch time / 32. --lm fuses the reference-default RNNLM into both, --times asks both for the emission
 frames, --vocab V takes the subword model; --ab-lib: the unbiased search of another build of the library takes part in the same loop.
@@ -107,20 +107,23 @@ def times_bench(args):
                                            beam_size=beam, nbest=nbest, state_beam=2.3, expand_beam=2.3)
             table, mats, b_ih, b_hh, b_proj, b_head, wdt = s._device_greedy_args(enc)
         H, J, E, V, Lmax = mats[1].shape[1], 640, table.shape[1], mats[3].shape[0], 2 * T + 16
-        ws = torch.zeros(ops.beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap), dtype=torch.uint8, device="cuda:0")
+        ws = torch.zeros(ops.beam_workspace_bytes(B, T, H, J, V, beam, cap, times=True), dtype=torch.uint8, device="cuda:0")
         hyps, frames = (torch.empty(B, nbest, Lmax, dtype=torch.int32, device="cuda:0") for _ in range(2))
         lens = torch.empty(B, nbest, dtype=torch.int32, device="cuda:0")
         scores = torch.empty(B, nbest, dtype=torch.float64, device="cuda:0")
         status = torch.empty(B, dtype=torch.int32, device="cuda:0")
+        # the offline narrow search: n_valid NULL, max_frames = T, then the frames, no LM, no graph, wide = 0
         head = (P(enc), P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]), P(b_head), P(ws), ws.numel(),
-                P(hyps), P(lens), P(scores), P(status), B, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01, capi.io_dtype(enc), wdt)
+                None, P(hyps), P(lens), P(scores), P(status), B, T, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01,
+                capi.io_dtype(enc), wdt)
+        launch = lambda fn, fr, what: capi.check(fn(*head, capi.stream_ptr(), P(fr), None, 0.0, None, 0), what)  # noqa: E731
 
-        forms = {"untimed": lambda: capi.check(lib.tsasr_beam_search(*head, capi.stream_ptr()), "tsasr_beam_search"),
-                 "timed": lambda: capi.check(lib.tsasr_beam_search_timed(*head, capi.stream_ptr(), P(frames)), "tsasr_beam_search_timed")}
+        forms = {"untimed": lambda: launch(lib.tsasr_beam_search, None, "tsasr_beam_search"),
+                 "timed": lambda: launch(lib.tsasr_beam_search, frames, "tsasr_beam_search (frames)")}
         if args.ab_lib:                                      # the untimed launch of another build of the library, in the same loop
             other = ctypes.CDLL(os.path.abspath(args.ab_lib)).tsasr_beam_search
             other.restype, other.argtypes = lib.tsasr_beam_search.restype, lib.tsasr_beam_search.argtypes
-            forms["untimed_ab"] = lambda: capi.check(other(*head, capi.stream_ptr()), "tsasr_beam_search (--ab-lib)")
+            forms["untimed_ab"] = lambda: launch(other, None, "tsasr_beam_search (--ab-lib)")
         names = list(forms)
         ms = {n: [] for n in names}
         fill = torch.empty(256 << 20, dtype=torch.uint8, device="cuda:0")
@@ -178,22 +181,24 @@ def lm_bench(args):
             lm_args = s._device_lm_args(enc)
         H, J, E, V, Lmax = mats[1].shape[1], 640, table.shape[1], mats[3].shape[0], 2 * T + 16
         desc, weight, lm_layers, lm_hidden = ops._beam_lm_desc(lm_args, V, wdt)
-        ws = torch.zeros(ops.beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, lm_layers, lm_hidden), dtype=torch.uint8, device="cuda:0")
+        ws = torch.zeros(ops.beam_workspace_bytes(B, T, H, J, V, beam, cap, lm_layers, lm_hidden), dtype=torch.uint8, device="cuda:0")
         hyps = torch.empty(B, nbest, Lmax, dtype=torch.int32, device="cuda:0")
         lens = torch.empty(B, nbest, dtype=torch.int32, device="cuda:0")
         scores = torch.empty(B, nbest, dtype=torch.float64, device="cuda:0")
         status, status_lm = (torch.empty(B, dtype=torch.int32, device="cuda:0") for _ in range(2))
         wptrs = (P(table), P(mats[0]), P(mats[1]), P(b_ih), P(b_hh), P(mats[2]), P(b_proj), P(mats[3]), P(b_head), P(ws), ws.numel())
-        head = (P(enc),) + wptrs + (P(hyps), P(lens), P(scores), P(status), B, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01,
+        # the offline narrow search: n_valid NULL, max_frames = T, untimed, then the LM and its weight, no graph, wide = 0
+        head = (P(enc),) + wptrs + (None, P(hyps), P(lens), P(scores), P(status), B, T, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3, 0.01,
                                     capi.io_dtype(enc), wdt)
         outs_lm = (P(hyps), P(lens), P(scores), P(status_lm))
-        forms = {"unfused": lambda: capi.check(lib.tsasr_beam_search(*head, capi.stream_ptr()), "tsasr_beam_search"),
-                 "fused": lambda: capi.check(ops._beam_lm_launch(enc, wptrs, None, outs_lm, B, T, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3,
-                                                                 0.01, wdt, None, desc, weight), "tsasr_beam_search_lm")}
+        unfused = lambda fn, what: capi.check(fn(*head, capi.stream_ptr(), None, None, 0.0, None, 0), what)  # noqa: E731
+        forms = {"unfused": lambda: unfused(lib.tsasr_beam_search, "tsasr_beam_search"),
+                 "fused": lambda: capi.check(ops._beam_launch(enc, wptrs, None, outs_lm, B, T, T, J, H, E, V, 0, beam, nbest, cap, Lmax, 2.3, 2.3,
+                                                              0.01, wdt, None, desc, weight, None, False), "tsasr_beam_search (lm)")}
         if args.ab_lib:
             other = ctypes.CDLL(os.path.abspath(args.ab_lib)).tsasr_beam_search
             other.restype, other.argtypes = lib.tsasr_beam_search.restype, lib.tsasr_beam_search.argtypes
-            forms["unfused_ab"] = lambda: capi.check(other(*head, capi.stream_ptr()), "tsasr_beam_search (--ab-lib)")
+            forms["unfused_ab"] = lambda: unfused(other, "tsasr_beam_search (--ab-lib)")
         names = list(forms)
         ms = {n: [] for n in names}
         fill = torch.empty(256 << 20, dtype=torch.uint8, device="cuda:0")

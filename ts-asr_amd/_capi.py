@@ -159,25 +159,10 @@ _PROTOS = {
     "tsasr_abs_lengths": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "tsasr_inject_fwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
     "tsasr_inject_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
-    "tsasr_greedy_decode": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
-    "tsasr_greedy_decode_stream": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
-    "tsasr_greedy_decode_wide": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
-    "tsasr_greedy_decode_stream_wide": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p]),
-    "tsasr_beam_search_workspace_bytes": (c_size_t, [c_int] * 6),
-    "tsasr_beam_search": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
-    "tsasr_beam_search_stream": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p]),
-    "tsasr_beam_search_timed_workspace_bytes": (c_size_t, [c_int] * 6),
-    "tsasr_beam_search_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 4 + [c_int] * 11 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
-    "tsasr_beam_search_stream_timed": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p]),
-    "tsasr_beam_search_lm_workspace_bytes": (c_size_t, [c_int] * 9),
-    "tsasr_beam_search_lm": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_double]),
-    "tsasr_beam_search_wide_workspace_bytes": (c_size_t, [c_int] * 10),
-    "tsasr_beam_search_wide": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
-                                       c_void_p, c_void_p, c_void_p, c_double]),
-    "tsasr_beam_search_bias_workspace_bytes": (c_size_t, [c_int] * 11),
-    "tsasr_beam_search_bias": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
-                                       c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    "tsasr_greedy_decode": (c_int, [c_void_p] * 14 + [c_int] * 7 + [c_float, c_int, c_int, c_void_p, c_int]),
+    "tsasr_beam_search_workspace_bytes": (c_size_t, [c_int] * 12),
+    "tsasr_beam_search": (c_int, [c_void_p] * 11 + [c_size_t] + [c_void_p] * 5 + [c_int] * 12 + [c_double, c_double, c_float, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int]),
     "tsasr_edit_distance_workspace_bytes": (c_size_t, [c_int, c_ll]),
     "tsasr_edit_distance": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_ll] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "tsasr_relpos_attn_stream_workspace_bytes": (c_size_t, [c_int] * 5),
@@ -217,7 +202,7 @@ _PROTOS = {
 
 
 class LmDesc(ctypes.Structure):
-    """tsasr_lm_desc of include/tsasr_hip.h (the LM of tsasr_beam_search_lm), field for field."""
+    """tsasr_lm_desc of include/tsasr_hip.h (the LM of tsasr_beam_search), field for field."""
     _fields_ = [("emb", c_void_p), ("w_ih", c_void_p * 4), ("w_hh", c_void_p * 4), ("b_ih", c_void_p * 4), ("b_hh", c_void_p * 4),
                 ("w_dnn", c_void_p * 2), ("b_dnn", c_void_p * 2), ("ln_g", c_void_p * 2), ("ln_b", c_void_p * 2), ("w_out", c_void_p),
                 ("b_out", c_void_p), ("ln_eps", c_float * 2), ("layers", c_int), ("hidden", c_int), ("emb_dim", c_int), ("dnn_blocks", c_int),
@@ -225,7 +210,7 @@ class LmDesc(ctypes.Structure):
 
 
 class BiasDesc(ctypes.Structure):
-    """tsasr_bias_desc of include/tsasr_hip.h (the packed phrase graphs of tsasr_beam_search_bias), field for field."""
+    """tsasr_bias_desc of include/tsasr_hip.h (the packed phrase graphs of tsasr_beam_search), field for field."""
     _fields_ = [("child_off", c_void_p), ("child_tok", c_void_p), ("child_to", c_void_p), ("pending", c_void_p), ("base", c_void_p),
                 ("weight", c_void_p), ("rows", c_int), ("edges", c_int)]
 

@@ -17,7 +17,7 @@ void tsasr_set_error(const char *fmt, ...) {
 
 extern "C" {
 const char *tsasr_last_error(void) { return g_err; }
-int tsasr_version(void) { return 1; }
+int tsasr_version(void) { return 2; }  // 2: one entry point per transducer search
 int tsasr_device_ok(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;

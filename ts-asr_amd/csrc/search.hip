@@ -40,7 +40,7 @@ struct GreedyArgs {
     float *logp_sum;            // [B]: sum of the emitted symbols' log-probabilities
     int B, T, J, H, E, V, blank;
     float slope;
-    float *state;               // STREAM: [B, S] fp32, S = 2H + J + 4 (tsasr_greedy_decode_stream)
+    float *state;               // STREAM: [B, S] fp32, S = 2H + J + 4 (tsasr_greedy_decode's state)
     const int *n_valid;         // STREAM: [B] frames of this chunk to decode
 };
 
@@ -167,7 +167,7 @@ __device__ __forceinline__ void predictor_step(const NetArgs &N, int E, int H, i
 // primed flag | 0]; a state with primed flag 0 (all zeros) is primed with the blank symbol first, as the one-call decoder does. Only the
 // first n_valid[b] frames are decoded (preds of the rest: -1); with n_valid[b] == 0 the state is neither read for priming nor written.
 //
-// WIDE (tsasr_greedy_decode_wide / _stream_wide: V <= 1024, E <= 1024) switches three things, the rest is one body:
+// WIDE (tsasr_greedy_decode's wide: V <= 1024, E <= 1024) switches three things, the rest is one body:
 //   - x and logits hold round_up(E, 4) and round_up(V, 4) floats instead of 64 each, and 64 floats of reduction space follow them:
 //     red[16] wave maxima | redi[16] wave candidates | reds[16] wave sums | the emit flag;
 //   - the arg max (lowest index among ties) and the sum of its log-softmax term: one vocabulary entry per thread, reduced per wave and
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void greedy_decode_kernel(const Gre
 // not held by the beam are recycled. Workspace of one utterance: header (16 ints: primed, status, nbeam, tree size, frames) + beam
 // entries | tree | slots; a zeroed header is the start of a stream.
 //
-// TIMES (tsasr_beam_search_timed / _stream_timed): the search also reports the encoder frame at which each token was emitted. The search
+// TIMES (tsasr_beam_search's frames): the search also reports the encoder frame at which each token was emitted. The search
 // never merges paths, so a tree node is one concrete path and its emission frame is one value: an extension appended to A at loop index t
 // records (frames of this stream decoded by earlier calls) + t in Afrm, beside Atok / Alen; the promotion step copies it into a node-frame
 // array parallel to the tree (after the slots in the workspace: the timed layout is the untimed one plus align16(4 * nodes) bytes per
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void greedy_decode_kernel(const Gre
 // start: the stream form takes "frames decoded so far" from hdr[4] whether or not the stream is primed, so hdr[0] == 0 over a stale
 // hdr[4] would shift every frame of the stream by that stale count (the untimed form only ever adds to the word).
 //
-// Contextual biasing (tsasr_beam_search_bias; the BIAS instantiations, whose arguments alone carry BeamBiasArgs): a prefix trie of phrases per utterance in CSR form
+// Contextual biasing (tsasr_beam_search's bias; the BIAS instantiations, whose arguments alone carry BeamBiasArgs): a prefix trie of phrases per utterance in CSR form
 // (child_off / child_tok / child_to / pending, states relative to the utterance's own graph at row base[b]) and one trie state per
 // hypothesis: Actx beside Afrm in LDS, nctx[node] in the workspace after the node-frame array (align16(4 * nodes) bytes more per
 // utterance), written at promotion beside nfrm. A non-blank extension by sym moves the state (beam_bias_step: a binary search over the
@@ -386,7 +386,7 @@ struct BeamArgs {
     int *frames;                // TIMES: [B, nbest, Lmax] emission frame of each token of hyps (absolute in the stream)
 };
 
-// LM fusion (tsasr_beam_search_lm; transducer.py:264-266, 311-351, 386-409 with lobes/models/RNNLM.py): a second recurrent network beside
+// LM fusion (tsasr_beam_search's lm; transducer.py:264-266, 311-351, 386-409 with lobes/models/RNNLM.py): a second recurrent network beside
 // the predictor, embedding -> L stacked LSTM cells -> nb blocks of Linear, LayerNorm, LeakyReLU -> Linear to V -> log_softmax. Its step is a
 // function of (token, parent's LM state) like the predictor's, so it runs once per node, in the node's predictor phase, into the node's
 // slot; a non-blank extension by sym scores (logp(a) + logp_joint[sym]) + weight * lm_logp[sym]; the top-k, the expand_beam test and the
@@ -517,7 +517,7 @@ __device__ __forceinline__ void beam_topk_pick(float &k, int &i, float k2, int i
     if (i2 != INT_MAX && (i == INT_MAX || k2 > k || (k2 == k && i2 < i))) { k = k2; i = i2; }
 }
 
-// WIDE (tsasr_beam_search_wide: subword vocabularies, V <= 1024 and E <= 1024) switches four things; the search itself - A in LDS, fp64
+// WIDE (tsasr_beam_search's wide: subword vocabularies, V <= 1024 and E <= 1024) switches four things; the search itself - A in LDS, fp64
 // scores and keys, memoised predictor (and LM) steps in slots, promotion into the token tree, status words, stream resume, TIMES - is
 // one body:
 //   - widths: x, lg, s_lmlp, llg and the lm_logp part of a slot hold round_up(E, 4) / round_up(V, 4) floats instead of 64;
@@ -901,7 +901,7 @@ void search_launch(void (*kern)(const Args), int B, size_t lds, void *stream, co
     kern<<<B, SEARCH_THREADS, lds, (hipStream_t)stream>>>(a);
 }
 
-// The four greedy entry points. wide: V <= 1024 and E <= 1024 instead of V <= 63 and E <= 64; streamed: state and n_valid are given.
+// tsasr_greedy_decode's checks and launch. wide: V <= 1024 and E <= 1024 instead of V <= 63 and E <= 64; streamed: state and n_valid are given.
 int greedy_launch(const char *name, bool wide, bool streamed, const void *enc, const NetArgs &net, float *state, const int32_t *n_valid,
                   int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype,
                   void *stream) {
@@ -931,68 +931,24 @@ int greedy_launch(const char *name, bool wide, bool streamed, const void *enc, c
 extern "C" {
 
 /* Greedy transducer search (speechbrain/decoders/transducer.py:138-218) for a predictor = embedding table -> one-layer LSTM -> Linear and
- * a joiner = LeakyReLU(enc + pn) -> Linear head. enc [B,T,J] (io_dtype); emb fp32 [n_emb, E] (E <= 64); LSTM weights in torch layout
- * (w_ih [4H,E], w_hh [4H,H], gate order i,f,g,o); w_proj [J,H]; w_head [V,J] (V <= 64); matrices in `wdtype` (TSASR_F32 / TSASR_BF16),
- * biases fp32 or NULL. H, J multiples of 4 and <= 1024. preds int32 [B,T]: the symbol emitted at each frame or -1; logp_sum fp32 [B]. One launch. */
+ * a joiner = LeakyReLU(enc + pn) -> Linear head; include/tsasr_hip.h states the arguments. state and n_valid both NULL: the offline
+ * search; both given: one chunk of a stream (pieces give the bits of one offline call). One launch. */
 int tsasr_greedy_decode(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                        const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
-                        int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream) {
-    return greedy_launch("tsasr_greedy_decode", false, false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, nullptr, nullptr,
-                         preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
+                        const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state, const int32_t *n_valid,
+                        int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype,
+                        int wdtype, void *stream, int wide) {
+    TSASR_CHECK_ARG(!state == !n_valid, "tsasr_greedy_decode: state and n_valid are given together (a stream chunk) or both NULL");
+    return greedy_launch("tsasr_greedy_decode", wide != 0, state != nullptr, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head},
+                         state, n_valid, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
 }
 
-/* tsasr_greedy_decode over one chunk of a stream: state fp32 [B, 2H + J + 4] (caller-owned, zeroed before the first chunk) carries the
- * predictor (h, c, projected output), the last symbol, the running log-prob sum and a primed flag between calls; n_valid int32 [B] =
- * frames of this chunk to decode per utterance (preds of the others are -1, and a zero count leaves the state untouched). logp_sum [B]
- * receives the running sum. Decoding a tensor in pieces gives the bits of one tsasr_greedy_decode call over it. */
-int tsasr_greedy_decode_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                               const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state, const int32_t *n_valid,
-                               int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype,
-                               int wdtype, void *stream) {
-    return greedy_launch("tsasr_greedy_decode_stream", false, true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, state,
-                         n_valid, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
-}
-
-/* The two greedy searches for subword vocabularies: the arguments, outputs and stream state of tsasr_greedy_decode / _stream with
- * V <= 1024 and E <= 1024 (a frozen one-hot table has E = V - 1: any E is taken, a multiple of 4 runs the dense product). The host sends
- * V <= 63 with E <= 64 to the narrow entry points. */
-int tsasr_greedy_decode_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, int *preds, float *logp_sum,
-                             int B, int T, int J, int H, int E, int V, int blank, float slope, int io_dtype, int wdtype, void *stream) {
-    return greedy_launch("tsasr_greedy_decode_wide", true, false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, nullptr,
-                         nullptr, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
-}
-
-int tsasr_greedy_decode_stream_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                                    const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, float *state,
-                                    const int32_t *n_valid, int *preds, float *logp_sum, int B, int T, int J, int H, int E, int V, int blank,
-                                    float slope, int io_dtype, int wdtype, void *stream) {
-    return greedy_launch("tsasr_greedy_decode_stream_wide", true, true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, state,
-                         n_valid, preds, logp_sum, B, T, J, H, E, V, blank, slope, io_dtype, wdtype, stream);
-}
-
-/* Beam transducer search (speechbrain/decoders/transducer.py:220-373, no LM) for the networks tsasr_greedy_decode takes; see the kernel's
- * comment. Workspace: tsasr_beam_search_workspace_bytes(B, max_frames, H, J, beam, cap) bytes; T = max_frames for the offline call. */
-size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int beam, int cap) {
-    if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
-    return (size_t)B * beam_layout(T, H, J, beam, cap).per_utt;
-}
-
-static size_t beam_workspace_bytes(int B, int T, int H, int J, int beam, int cap, bool times, int lmw = 0, bool bias = false) {
-    if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || beam <= 0 || cap <= 0) return 0;
-    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap, lmw), times, bias);
-}
-
-/* The LM-fused search's workspace: every slot also holds lm_logp[64] | lm_h | lm_c (64 + 2 lm_layers lm_hidden floats); times != 0: the
- * timed layout. 0 for a non-positive size. */
-size_t tsasr_beam_search_lm_workspace_bytes(int B, int T, int H, int J, int beam, int cap, int lm_layers, int lm_hidden, int times) {
-    if (lm_layers <= 0 || lm_hidden <= 0) return 0;
-    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, beam_lm_slot_floats(false, 0, lm_layers, lm_hidden));
-}
-
-/* The timed searches' workspace: the untimed layout of each utterance plus one int per tree node (align16(4 (1 + (T + 1) beam + cap))). */
-size_t tsasr_beam_search_timed_workspace_bytes(int B, int T, int H, int J, int beam, int cap) {
-    return beam_workspace_bytes(B, T, H, J, beam, cap, true);
+/* The beam search's workspace (see the kernel's comment), the host's one statement of its layout: a slot's LM part is beam_lm_slot_floats
+ * (lm_layers 0: no LM, lm_hidden is not read), times and bias add one int per tree node each. 0 for a shape no call takes. */
+size_t tsasr_beam_search_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times,
+                                         int bias, int wide) {
+    if (B <= 0 || T <= 0 || H <= 0 || J <= 0 || V <= 0 || beam <= 0 || cap <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
+    const int lmw = lm_layers > 0 ? beam_lm_slot_floats(wide != 0, V, lm_layers, lm_hidden) : 0;
+    return (size_t)B * beam_per_utt(beam_layout(T, H, J, beam, cap, lmw), times != 0, bias != 0);
 }
 
 // Checks an LM descriptor and restates it, with the fusion weight, as the kernel's arguments
@@ -1015,14 +971,15 @@ static int beam_lm_args(const char *name, const tsasr_lm_desc *lm, double lm_wei
     return 0;
 }
 
-// Every beam entry point. wide: V <= 1024, E <= 1024 and the LDS budget of the wide instantiations; times: frames are reported.
+// tsasr_beam_search's checks and launch. wide: V <= 1024, E <= 1024 and the LDS budget of the wide instantiations; frames given: timed.
 static int beam_launch(const char *name, bool wide, const void *enc, const NetArgs &net, void *workspace, size_t workspace_bytes,
-                       const int32_t *n_valid, int *hyps, int *frames, bool times, int *lens, double *scores, int *status, int B, int T,
-                       int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                       double expand_beam, float slope, int io_dtype, int wdtype, void *stream, const tsasr_lm_desc *lm = nullptr,
-                       double lm_weight = 0.0, const tsasr_bias_desc *bias = nullptr) {
-    TSASR_CHECK_ARG(enc && net.emb && net.w_ih && net.w_hh && net.w_proj && net.w_head && workspace && hyps && lens && scores && status &&
-                    (frames || !times), "%s: null pointer", name);
+                       const int32_t *n_valid, int *hyps, int *frames, int *lens, double *scores, int *status, int B, int T, int max_frames,
+                       int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam,
+                       float slope, int io_dtype, int wdtype, void *stream, const tsasr_lm_desc *lm, double lm_weight,
+                       const tsasr_bias_desc *bias) {
+    const bool times = frames != nullptr;
+    TSASR_CHECK_ARG(enc && net.emb && net.w_ih && net.w_hh && net.w_proj && net.w_head && workspace && hyps && lens && scores && status,
+                    "%s: null pointer", name);
     TSASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && J % 4 == 0 && H > 0 && H % 4 == 0 && E > 0 && E <= (wide ? 1024 : 64) && V > 1 &&
                     V <= (wide ? SEARCH_THREADS : 63) && blank >= 0 && blank < V,
                     "%s: bad shape (B=%d T=%d J=%d H=%d E=%d V=%d blank=%d)", name, B, T, J, H, E, V, blank);
@@ -1037,7 +994,6 @@ static int beam_launch(const char *name, bool wide, const void *enc, const NetAr
         if (const int err = beam_lm_args(name, lm, lm_weight, m)) return err;
         lm_lds = (size_t)(std::max(std::max(m.E, m.Hl), m.D) + 2 * m.Hl + std::max(4 * m.Hl, m.D) + 2 * Vp + 2) * sizeof(float);
     }
-    const int lmw = lm ? beam_lm_slot_floats(wide, V, lm->layers, lm->hidden) : 0;
     BeamBiasArgs g{};
     if (bias) {
         TSASR_CHECK_ARG(bias->child_off && bias->child_tok && bias->child_to && bias->pending && bias->base && bias->weight,
@@ -1045,7 +1001,8 @@ static int beam_launch(const char *name, bool wide, const void *enc, const NetAr
         TSASR_CHECK_ARG(bias->rows >= 1 && bias->edges >= 0, "%s: bad bias sizes (rows=%d edges=%d)", name, bias->rows, bias->edges);
         g = BeamBiasArgs{bias->child_off, bias->child_tok, bias->child_to, bias->pending, bias->base, bias->weight, bias->rows};
     }
-    const size_t need = beam_workspace_bytes(B, max_frames, H, J, beam, cap, times, lmw, bias != nullptr);
+    const size_t need = tsasr_beam_search_workspace_bytes(B, max_frames, H, J, V, beam, cap, lm ? lm->layers : 0, lm ? lm->hidden : 0, times,
+                                                          bias != nullptr, wide);
     TSASR_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu B, need %zu", name, workspace_bytes, need);
     // dynamic LDS (the kernel's comment); wide: + 4 KB for its static arrays (the beam's and the top-k's, 2.4 KB) within the CU's 160 KB
     const size_t lds = (size_t)(6 * H + 2 * J + Ep + Vp + (wide ? 96 : 0)) * sizeof(float) +
@@ -1070,120 +1027,24 @@ static int beam_launch(const char *name, bool wide, const void *enc, const NetAr
     return 0;
 }
 
-/* Beam search over enc [B,T,J] from the start (every frame, padding included, as the reference). The workspace is (re)initialised and
- * left holding the final beam: a tsasr_beam_search_stream call with zero counts (max_frames = T) reads the n-best out again, e.g. with a
- * larger Lmax. hyps int32 [B,nbest,Lmax] (the first min(len, Lmax) tokens), lens int32 [B,nbest] (-1: fewer beam entries), scores fp64
- * [B,nbest] = logp / len(prediction incl. the blank prefix), status int32 [B]: 0 ok, 1 more than cap hypotheses in a frame, 2 token
- * tree full, 3 no hypothesis left to expand; an utterance with a nonzero status stops there, the others are unaffected. */
+/* Beam transducer search (speechbrain/decoders/transducer.py:220-373) for the networks tsasr_greedy_decode takes; see the kernel's comment
+ * and include/tsasr_hip.h. n_valid NULL: the offline search over every frame of enc [B,T,J], padding included, as the reference (the
+ * workspace is started afresh and left holding the final beam: a call with zero counts reads the n-best out again, e.g. with a larger
+ * Lmax); given: one chunk of a stream resumed from the workspace (zeroed = start of the stream). frames NULL: untimed; lm NULL: no LM
+ * fusion (see BeamLmArgs; lm_weight is then not read); bias NULL: no phrase graphs (see BeamBiasArgs). wide: the WIDE instantiation; a
+ * biased call has only ever run the one its shape needs, so with a graph wide must say V > 63 || E > 64. */
 int tsasr_beam_search(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
                       const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace, size_t workspace_bytes,
-                      int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V, int blank, int beam,
-                      int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
-    return beam_launch("tsasr_beam_search", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
-                       nullptr, hyps, nullptr, false, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
-                       expand_beam, slope, io_dtype, wdtype, stream);
-}
-
-/* The same search over one chunk of a stream: the beam, token tree and predictor slots are resumed from the workspace (laid out for
- * max_frames; zeroed = start of the stream), n_valid int32 [B] = frames of this chunk to decode per utterance (0: the state is left as it
- * is). The outputs describe the beam after the chunk; a nonzero status is sticky. Pieces give the bits of one call over the whole. */
-int tsasr_beam_search_stream(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                             const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                             size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                             int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                             double expand_beam, float slope, int io_dtype, int wdtype, void *stream) {
-    TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream: null n_valid");
-    return beam_launch("tsasr_beam_search_stream", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
-                       workspace_bytes, n_valid, hyps, nullptr, false, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
-                       cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
-}
-
-/* tsasr_beam_search that also reports when each token was emitted: frames int32 [B,nbest,Lmax], frames[b,r,i] = index of the encoder
- * frame whose joint emitted hyps[b,r,i] (non-decreasing along a hypothesis; several tokens may share a frame), written for the first
- * min(len, Lmax) tokens. workspace >= tsasr_beam_search_timed_workspace_bytes(...). Hypotheses, lengths, scores and status are the
- * bits of tsasr_beam_search. */
-int tsasr_beam_search_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                            const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                            size_t workspace_bytes, int *hyps, int *lens, double *scores, int *status, int B, int T, int J, int H, int E, int V,
-                            int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope, int io_dtype,
-                            int wdtype, void *stream, int *frames) {
-    return beam_launch("tsasr_beam_search_timed", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
-                       nullptr, hyps, frames, true, lens, scores, status, B, T, T, J, H, E, V, blank, beam, nbest, cap, Lmax, state_beam,
-                       expand_beam, slope, io_dtype, wdtype, stream);
-}
-
-/* tsasr_beam_search_stream with frames (absolute from the start of the stream). The workspace has the timed layout and must have been
- * started (zeroed, or by tsasr_beam_search_timed) and continued by timed calls only: an untimed call records no frames for the nodes it
- * adds. A zero count leaves the state alone and reads the n-best and their frames out again. */
-int tsasr_beam_search_stream_timed(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                                   const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                                   size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B,
-                                   int T, int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax,
-                                   double state_beam, double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames) {
-    TSASR_CHECK_ARG(n_valid, "tsasr_beam_search_stream_timed: null n_valid");
-    return beam_launch("tsasr_beam_search_stream_timed", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
-                       workspace_bytes, n_valid, hyps, frames, true, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest,
-                       cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream);
-}
-
-/* The LM-fused search (see BeamLmArgs): tsasr_beam_search_stream_timed's arguments, then the LM and its weight. n_valid NULL: the offline
- * search (the workspace is started afresh; max_frames sizes it, T for one call); frames NULL: untimed. The LM's matrices are in wdtype
- * like the predictor's, its biases, LayerNorm vectors and embedding table fp32. workspace >= tsasr_beam_search_lm_workspace_bytes. */
-int tsasr_beam_search_lm(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                         const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                         size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                         int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                         double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                         double lm_weight) {
-    TSASR_CHECK_ARG(lm, "tsasr_beam_search_lm: null lm");
-    return beam_launch("tsasr_beam_search_lm", false, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
-                       n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
-                       Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
-}
-
-/* The wide search's workspace (beam_search_kernel's WIDE), a function of the shape alone: the narrow layout with the slot's LM part
- * widened to round_up(V, 4) + 2 lm_layers lm_hidden floats; lm_layers == 0: no LM (lm_hidden is not read). 0 for a shape no call takes. */
-size_t tsasr_beam_search_wide_workspace_bytes(int B, int T, int H, int J, int V, int beam, int cap, int lm_layers, int lm_hidden, int times) {
-    if (V <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
-    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_lm_slot_floats(true, V, lm_layers, lm_hidden) : 0);
-}
-
-/* The beam search for subword vocabularies: tsasr_beam_search_lm's arguments with V <= 1024, E <= 1024 (any E; a multiple of 4 runs the
- * dense product), beam <= 64, and lm NULL = no LM fusion (lm_weight is then not read). n_valid NULL: the offline search; frames NULL:
- * untimed. The LDS the shape needs is checked here: a shape past it is an argument error. */
-int tsasr_beam_search_wide(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                           double lm_weight) {
-    return beam_launch("tsasr_beam_search_wide", true, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace, workspace_bytes,
-                       n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap,
-                       Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight);
-}
-
-/* The biased search's workspace (see BeamBiasArgs): the layout of the same search without a graph - narrow for V <= 63 and E <= 64, wide
- * otherwise; lm_layers 0: no LM; times != 0: the timed layout - plus one int per tree node, the trie state of the node's path. */
-size_t tsasr_beam_search_bias_workspace_bytes(int B, int T, int H, int J, int E, int V, int beam, int cap, int lm_layers, int lm_hidden,
-                                              int times) {
-    if (E <= 0 || V <= 0 || lm_layers < 0 || (lm_layers > 0 && lm_hidden <= 0)) return 0;
-    const bool wide = V > 63 || E > 64;
-    return beam_workspace_bytes(B, T, H, J, beam, cap, times != 0, lm_layers > 0 ? beam_lm_slot_floats(wide, V, lm_layers, lm_hidden) : 0, true);
-}
-
-/* Beam search with contextual biasing: tsasr_beam_search_lm's arguments, then the packed phrase graphs. n_valid NULL: the offline search;
- * frames NULL: untimed; lm NULL: no LM fusion (lm_weight is then not read). V <= 63 with E <= 64 runs the narrow instantiation, every
- * other shape the wide one with its limits. bias NULL is an argument error: a search without a graph takes the entry points above. */
-int tsasr_beam_search_bias(const void *enc, const float *emb, const void *w_ih, const void *w_hh, const float *b_ih, const float *b_hh,
-                           const void *w_proj, const float *b_proj, const void *w_head, const float *b_head, void *workspace,
-                           size_t workspace_bytes, const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T,
-                           int max_frames, int J, int H, int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam,
-                           double expand_beam, float slope, int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm,
-                           double lm_weight, const tsasr_bias_desc *bias) {
-    TSASR_CHECK_ARG(bias, "tsasr_beam_search_bias: null bias");
-    return beam_launch("tsasr_beam_search_bias", V > 63 || E > 64, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
-                       workspace_bytes, n_valid, hyps, frames, frames != nullptr, lens, scores, status, B, T, max_frames, J, H, E, V, blank,
-                       beam, nbest, cap, Lmax, state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight, bias);
+                      const int32_t *n_valid, int *hyps, int *lens, double *scores, int *status, int B, int T, int max_frames, int J, int H,
+                      int E, int V, int blank, int beam, int nbest, int cap, int Lmax, double state_beam, double expand_beam, float slope,
+                      int io_dtype, int wdtype, void *stream, int *frames, const tsasr_lm_desc *lm, double lm_weight,
+                      const tsasr_bias_desc *bias, int wide) {
+    TSASR_CHECK_ARG(n_valid || max_frames == T, "tsasr_beam_search: the offline search (n_valid NULL) takes max_frames = T, got %d and T=%d",
+                    max_frames, T);
+    TSASR_CHECK_ARG(!bias || (wide != 0) == (V > 63 || E > 64), "tsasr_beam_search: bias with wide=%d but V=%d E=%d", wide, V, E);
+    return beam_launch("tsasr_beam_search", wide != 0, enc, {emb, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, w_head, b_head}, workspace,
+                       workspace_bytes, n_valid, hyps, frames, lens, scores, status, B, T, max_frames, J, H, E, V, blank, beam, nbest, cap, Lmax,
+                       state_beam, expand_beam, slope, io_dtype, wdtype, stream, lm, lm_weight, bias);
 }
 
 }  // extern "C"

@@ -9,26 +9,26 @@ reference's list order, one predictor step per hypothesis node); utterances that
 every other network shape, run the host loop: host-side hypothesis bookkeeping exactly as specified there (SURVEY.md section 8f
 row f1), device-side predictor / joint / head steps. Pinned to the reference's own hypotheses by tests/golden/c1_beam.npz.
 Subword models (64 <= V <= 1024, or an embedding of up to 1024 columns; beam_size <= 64) run the same search in
-beam_search_wide_kernel (tsasr_beam_search_wide: offline, streams, timestamps and LM fusion through one entry point).
+beam_search_kernel's WIDE instantiations (tsasr_beam_search with wide set: offline, streams, timestamps and LM fusion alike).
 
 LM fusion (lm_module, lm_weight > 0; transducer.py:95-110, 264-266, 311-351, 386-409): a hypothesis also carries the LM's state; each
 expansion of a runs the LM on a's last token (blank doubles as its BOS) from a's LM state; a non-blank extension by sym takes the new
 state and scores (logp(a) + logp_joint[sym]) + lm_weight * logp_lm[sym]; the top-k, the expand_beam test and the blank copies read
-the joint alone. An nnet.RNNLM of the shapes _device_lm_ok lists is fused into the device search (tsasr_beam_search_lm: one LM step
+the joint alone. An nnet.RNNLM of the shapes _device_lm_ok lists is fused into the device search (tsasr_beam_search's lm: one LM step
 per node, beside its predictor step); any other module with the reference's call form runs in the host loop. Greedy search never uses
 the LM. Pinned to the reference's hypotheses by tests/golden/c1_beam_lm.npz.
 
 Timestamps (forward_timed, greedy_stream / beam_stream with return_frames=True): frames[i] = index of the encoder frame whose joint
 emitted token i, absolute from the start of the utterance or stream. Greedy emits at most one symbol per frame, so the frame is the
 token's column in the kernel's ``preds``; the beam search never merges paths, so each hypothesis carries one frame list (the device
-search records it per tree node, tsasr_beam_search_timed; the host loop carries it with the hypothesis). Seconds and word spans:
+search records it per tree node, tsasr_beam_search's frames; the host loop carries it with the hypothesis). Seconds and word spans:
 align.frame_seconds / align.word_spans.
 
 Contextual biasing (``bias``: a biasing.ContextGraph for every utterance, or a list of B entries, each a graph or None; biasing.py
 states the rule): a hypothesis also carries a trie state, 0 at the start; a blank copy keeps it; a non-blank extension by sym moves it
 (graph.step) and adds the step's bonus d last, after the joint's and the LM's terms; the n-best is ranked and reported with
 (logp - pending[state]) / len while the beam itself keeps logp. The host loop below is the definition; the device search carries the
-state per tree node (tsasr_beam_search_bias). With no graph (None, an empty graph, a list of them) every call is today's.
+state per tree node (tsasr_beam_search's bias). With no graph (None, an empty graph, a list of them) every call is today's.
 """
 import os
 import warnings
@@ -36,7 +36,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
-GREEDY_WIDE_MAX = 1024          # vocabulary and embedding columns the device greedy search takes (csrc/search.hip greedy_decode_wide_kernel)
+GREEDY_WIDE_MAX = 1024          # vocabulary and embedding columns the device greedy search takes (csrc/search.hip greedy_decode_kernel's WIDE instantiations)
 BEAM_CAP = 512                  # hypotheses one frame of the device beam search may hold (its A list); past it: the host loop
 BEAM_STREAM_FRAMES = 4096       # frames a beam_stream workspace is laid out for when the caller does not say
 BEAM_HOST_REDECODES = {"utterances": 0}     # utterances the device beam search handed back to the host loop (status != 0)
@@ -131,7 +131,7 @@ class TransducerBeamSearcher(torch.nn.Module):
     def _device_greedy_ok(self, tn_output):
         """The one-launch device decoder (csrc/search.hip) covers the recipes' networks: one-hot or learned embedding, one-layer
         unidirectional LSTM, Linear projection, joint = LeakyReLU(sum), one Linear classifier. Character models (V <= 63, embedding <= 64
-        columns) run the narrow kernel, subword models up to V = 1024 and 1024 embedding columns its wide sibling."""
+        columns) run the narrow instantiation, subword models up to V = 1024 and 1024 embedding columns the wide one."""
         if os.environ.get("TSASR_GREEDY_KERNEL", "1") == "0":
             return False
         if not self._device_net_ok(tn_output, GREEDY_WIDE_MAX, GREEDY_WIDE_MAX):
@@ -163,7 +163,7 @@ class TransducerBeamSearcher(torch.nn.Module):
         return ok
 
     def _beam_is_wide(self):
-        """Subword models (V > 63 or an embedding wider than 64 columns) run beam_search_wide_kernel, character models the narrow one."""
+        """Subword models (V > 63 or an embedding wider than 64 columns) run beam_search_kernel's WIDE instantiations, character models the narrow ones."""
         return self._greedy_is_wide()
 
     def _device_lm_ok(self, V):
@@ -202,7 +202,7 @@ class TransducerBeamSearcher(torch.nn.Module):
 
     def _device_net_ok(self, tn_output, emb_max, vocab_max):
         """The network shape csrc/search.hip takes, with the caller's limits on the embedding width and the vocabulary: the greedy and
-        the beam search (with LM fusion) both go to GREEDY_WIDE_MAX, in the wide kernels past 64 columns / V = 63."""
+        the beam search (with LM fusion) both go to GREEDY_WIDE_MAX, in the WIDE instantiations past 64 columns / V = 63."""
         from . import nnet, rnnt
         if not tn_output.is_cuda or tn_output.dtype not in (torch.float32, torch.bfloat16):
             return False
@@ -218,18 +218,11 @@ class TransducerBeamSearcher(torch.nn.Module):
 
     @torch.no_grad()
     def _greedy_on_device(self, tn_output, timed=False):
-        from . import _capi as C
-        B, T, J = tn_output.shape
+        from . import ops
         enc = tn_output.contiguous()
-        rnn = self.decode_network_lst[1].rnn
         table, mats, b_ih, b_hh, b_proj, b_head, wdt = self._device_greedy_args(enc)   # (bf16 activations: the bf16 weight shadows)
-        preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
-        logp = torch.empty(B, dtype=torch.float32, device=enc.device)
-        name = "tsasr_greedy_decode_wide" if self._greedy_is_wide() else "tsasr_greedy_decode"
-        C.check(getattr(C.lib(), name)(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                       C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(preds), C.ptr(logp), B, T, J, rnn.hidden_size,
-                                       table.shape[1], mats[3].shape[0], int(self.blank_id), float(self.tjoint.nonlinearity.negative_slope),
-                                       C.io_dtype(enc), wdt, C.stream_ptr()), name)
+        preds, logp = ops.greedy_decode(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id,
+                                        self.tjoint.nonlinearity.negative_slope, wdt)
         if timed:
             hyps, frames = self._unpack_preds(preds)
             return hyps, logp.exp().mean(), None, None, frames, None
@@ -449,19 +442,21 @@ class TransducerBeamSearcher(torch.nn.Module):
         return fn(enc, table, mats, b_ih, b_hh, b_proj, b_head, self.blank_id, self.tjoint.nonlinearity.negative_slope, wdt, self.beam_size,
                   self.nbest, self.state_beam, self.expand_beam, self.cap, *extra, **kw)
 
+    @staticmethod
+    def _beam_kw(timed, graphs, device):
+        """The keywords of a _device_beam_call: ``graphs`` (None: unbiased) packed for the device."""
+        if graphs is None:
+            return dict(frames=bool(timed))
+        from .biasing import pack
+        return dict(frames=bool(timed), bias=pack(graphs, device))
+
     @torch.no_grad()
     def _beam_on_device(self, tn_output, timed=False, graphs=None):
         from . import ops
         enc = tn_output.contiguous()
-        if graphs is not None:
-            from .biasing import pack
-            out = self._device_beam_call(enc, ops.beam_search, frames=bool(timed), bias=pack(graphs, enc.device))
-            nbest_batch, nbest_scores, status = out[:3]
-            nbest_frames = out[3] if timed else None
-        elif timed:
-            nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search, frames=True)
-        else:
-            nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search)
+        out = self._device_beam_call(enc, ops.beam_search, **self._beam_kw(timed, graphs, enc.device))
+        nbest_batch, nbest_scores, status = out[:3]
+        nbest_frames = out[3] if timed else None
         bad = [b for b in range(enc.shape[0]) if int(status[b]) != 0]
         if bad:
             if BEAM_HOST_REDECODES["utterances"] == 0:
@@ -572,39 +567,19 @@ class TransducerBeamSearcher(torch.nn.Module):
             enc = enc_chunk.contiguous()
             if state is None:
                 mf = int(max_frames or BEAM_STREAM_FRAMES)
-                size = ops.beam_stream_timed_workspace_bytes if timed else ops.beam_stream_workspace_bytes
-                nbytes = size(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1], self.beam_size, self.cap)
-                if biased:
-                    lm_rnn = self.lm.rnn.rnn if self.lm_weight > 0 else None
-                    nbytes = ops.beam_bias_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1],
-                                                           self.decode_network_lst[0].embedding_dim, self.classifier_network[0].w.out_features,
-                                                           self.beam_size, self.cap, lm_rnn.num_layers if lm_rnn is not None else 0,
-                                                           lm_rnn.hidden_size if lm_rnn is not None else 0, timed)
-                elif self.lm_weight > 0:
-                    lm_rnn = self.lm.rnn.rnn
-                    hid, V = self.decode_network_lst[1].rnn.hidden_size, self.classifier_network[0].w.out_features
-                    if self._beam_is_wide():
-                        nbytes = ops.beam_wide_workspace_bytes(B, mf, hid, enc.shape[-1], V, self.beam_size, self.cap, lm_rnn.num_layers,
-                                                               lm_rnn.hidden_size, timed)
-                    else:
-                        nbytes = ops.beam_stream_lm_workspace_bytes(B, mf, hid, enc.shape[-1], self.beam_size, self.cap, lm_rnn.num_layers,
-                                                                    lm_rnn.hidden_size, timed)
+                lm_layers, lm_hidden = (self.lm.rnn.rnn.num_layers, self.lm.rnn.rnn.hidden_size) if self.lm_weight > 0 else (0, 0)
+                nbytes = ops.beam_workspace_bytes(B, mf, self.decode_network_lst[1].rnn.hidden_size, enc.shape[-1],
+                                                  self.classifier_network[0].w.out_features, self.beam_size, self.cap, lm_layers, lm_hidden,
+                                                  timed, biased, self._beam_is_wide())
                 state = {"dev": torch.zeros(nbytes, dtype=torch.uint8, device=dev), "max_frames": mf, "B": B}
                 if biased:
                     state["graphs"] = graphs
             elif "dev" not in state:
                 raise ValueError("beam_stream: this state was made by the host route")
-            if biased:
-                from .biasing import pack
-                out = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"], frames=timed,
-                                             bias=pack(graphs, dev))
-                nbest_batch, nbest_scores, status = out[:3]
-                nbest_frames = out[3] if timed else None
-            elif timed:
-                nbest_batch, nbest_scores, status, nbest_frames = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv,
-                                                                                         state["max_frames"], frames=True)
-            else:
-                nbest_batch, nbest_scores, status = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"])
+            out = self._device_beam_call(enc, ops.beam_search_stream, state["dev"], nv, state["max_frames"],
+                                         **self._beam_kw(timed, graphs, dev))
+            nbest_batch, nbest_scores, status = out[:3]
+            nbest_frames = out[3] if timed else None
             bad = [b for b in range(B) if int(status[b]) != 0]
             state["stopped"] = {b: ops.BEAM_STATUS[int(status[b])] for b in bad}
             if bad and raise_stopped:

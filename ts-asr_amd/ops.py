@@ -25,9 +25,9 @@ STATUS = {
     "joint(32 < V <= 1024: subword vocabularies)": "HIP (joint_wide.hip: vocabulary tiles inside the kernels; bf16-rounded h / W / dlogits with bf16 OR fp32 activations - "
                                                    "an exact-fp32 wide joint is not built: compute_dtype fp32 with V > 32 runs these kernels with fp32 storage)",
     "joint + loss without logits (joint_logits: lazy, 32 < V <= 1024)": "HIP (joint_wide.hip: joint_wide_lp / joint_wide_lazy_x / joint_wide_lazy_w; V <= 32 materialises)",
-    "greedy search (V <= 1024, embedding <= 1024 columns)": "HIP (search.hip: greedy_decode_kernel for V <= 63 / E <= 64, greedy_decode_wide_kernel above)",
+    "greedy search (V <= 1024, embedding <= 1024 columns)": "HIP (search.hip: greedy_decode_kernel, its WIDE instantiations above V = 63 / E = 64)",
     "beam search / LM fusion with V > 63 or an embedding past 64 columns (V, E <= 1024, beam_size <= 64)":
-        "HIP (search.hip: beam_search_wide_kernel, workgroup-wide log-softmax and top-k; offline, streams, timestamps and LM fusion)",
+        "HIP (search.hip: beam_search_kernel's WIDE instantiations, workgroup-wide log-softmax and top-k; offline, streams, timestamps and LM fusion)",
     "injection sum / prod": "HIP (inject)", "mix_sources": "HIP (dataio.hip)", "fbank": "HIP", "sentence_norm": "HIP", "fbank_frames": "HIP", "running_norm": "HIP (features_stream.hip)",
     "fbank_frames_slots": "HIP (features.hip: the fbank frame body over per-slot sample rings)", "audio_ring_append": "HIP (features_stream.hip)",
     "relpos_attention": "HIP (forward: everything-in-LDS kernel for T <= 256 and, per chunk of 256 keys, for long sequences in small batches, streaming kernel otherwise; backward = query-major, key-major, d(pk) and partial-sum kernels)",
@@ -41,10 +41,10 @@ STATUS = {
     "relpos_attention(need_weights=True: attention maps for plots)": "LIB (ATen matmul / softmax), logged",
     "streaming (causal encoder, chunk by chunk)": "HIP (stream.hip: relpos_attention_stream on a K/V cache, convmod_stream with carried history, "
                                                   "both also per slot with a device array of offsets for sessions that join and leave a batch; "
-                                                  "search.hip: greedy_decode_stream); every other op of the chunk is the offline HIP op",
-    "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search / beam_search_stream, one launch per batch or chunk; "
+                                                  "search.hip: greedy_decode_kernel's STREAM instantiations); every other op of the chunk is the offline HIP op",
+    "beam search (TEST stage, streaming search='beam')": "HIP (search.hip: beam_search_kernel, one launch per batch or chunk; "
                                                          "the host loop only for other predictor shapes and utterances past cap)",
-    "beam search with LM fusion (lm_module, lm_weight > 0)": "HIP (search.hip: beam_search_lm, an nnet.RNNLM with an LSTM fused into the same launch); "
+    "beam search with LM fusion (lm_module, lm_weight > 0)": "HIP (search.hip: beam_search_kernel's LM instantiations, an nnet.RNNLM with an LSTM fused into the same launch); "
                                                              "the host loop for every other LM",
     "WER / CER statistics (VALID / TEST stages)": "HIP (editdist.hip: edit_distance, one launch per searched batch; metrics.ErrorRateStats)",
 }
@@ -2375,8 +2375,30 @@ def convmod_stream(y2, b2, conv_w, conv_b, ln_w, ln_b, hist_in, hist_out, eps, s
 
 
 def greedy_stream_state_size(H, J):
-    """fp32 words of one utterance's tsasr_greedy_decode_stream state: h | c | projected output | symbol | log-prob sum | flag | pad."""
+    """fp32 words of one utterance's tsasr_greedy_decode stream state: h | c | projected output | symbol | log-prob sum | flag | pad."""
     return 2 * H + J + 4
+
+
+def _greedy_launch(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_valid, blank, slope, wdtype):
+    """tsasr_greedy_decode over enc [B,T,J]; state and n_valid None: the offline search. Returns (preds, logp_sum)."""
+    B, T, J = enc.shape
+    E, V = table.shape[1], mats[3].shape[0]
+    preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
+    logp = torch.empty(B, dtype=torch.float32, device=enc.device)
+    # character models keep the narrow instantiation; subword vocabularies (V > 63) or embeddings past 64 columns run the wide one (same state)
+    C.check(C.lib().tsasr_greedy_decode(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
+                                        C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(state), C.ptr(n_valid), C.ptr(preds), C.ptr(logp),
+                                        B, T, J, mats[1].shape[1], E, V, int(blank), float(slope), C.io_dtype(enc), wdtype, C.stream_ptr(),
+                                        int(E > 64 or V > 63)), "tsasr_greedy_decode")
+    return preds, logp
+
+
+def greedy_decode(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype):
+    """Greedy transducer search of every utterance of enc [B,T,J] in one launch. Returns (preds int32 [B,T] with -1 for no symbol,
+    logp_sum fp32 [B])."""
+    _no_grad_only("greedy_decode")
+    C.require_gpu(enc)
+    return _greedy_launch(enc.contiguous(), table, mats, b_ih, b_hh, b_proj, b_head, None, None, blank, slope, wdtype)
 
 
 def greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_valid, blank, slope, wdtype):
@@ -2384,72 +2406,31 @@ def greedy_decode_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_
     n_valid int32 [B]. Returns (preds int32 [B,T] with -1 for no symbol, running logp_sum fp32 [B])."""
     _no_grad_only("greedy_decode_stream")
     C.require_gpu(enc, state, n_valid)
-    B, T, J = enc.shape
-    H = mats[1].shape[1]
-    if tuple(state.shape) != (B, greedy_stream_state_size(H, J)) or state.dtype != torch.float32 or not state.is_contiguous():
+    B, _, J = enc.shape
+    if tuple(state.shape) != (B, greedy_stream_state_size(mats[1].shape[1], J)) or state.dtype != torch.float32 or not state.is_contiguous():
         raise ValueError("greedy_decode_stream: state must be a contiguous fp32 [B, 2H + J + 4] tensor")
-    preds = torch.empty(B, T, dtype=torch.int32, device=enc.device)
-    logp = torch.empty(B, dtype=torch.float32, device=enc.device)
-    nv = n_valid.to(torch.int32).contiguous()
-    # character models keep the narrow kernel; subword vocabularies (V > 63) or embeddings past 64 columns run its wide sibling (same state)
-    name = "tsasr_greedy_decode_stream_wide" if table.shape[1] > 64 or mats[3].shape[0] > 63 else "tsasr_greedy_decode_stream"
-    C.check(getattr(C.lib(), name)(C.ptr(enc), C.ptr(table), C.ptr(mats[0]), C.ptr(mats[1]), C.ptr(b_ih), C.ptr(b_hh), C.ptr(mats[2]),
-                                   C.ptr(b_proj), C.ptr(mats[3]), C.ptr(b_head), C.ptr(state), C.ptr(nv), C.ptr(preds), C.ptr(logp),
-                                   B, T, J, H, table.shape[1], mats[3].shape[0], int(blank), float(slope), C.io_dtype(enc), wdtype,
-                                   C.stream_ptr()), name)
-    return preds, logp
+    return _greedy_launch(enc, table, mats, b_ih, b_hh, b_proj, b_head, state, n_valid.to(torch.int32).contiguous(), blank, slope, wdtype)
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Beam transducer search on the device (csrc/search.hip: tsasr_beam_search / tsasr_beam_search_stream). Inference only.
+# Beam transducer search on the device (csrc/search.hip: tsasr_beam_search). Inference only.
 BEAM_STATUS = {0: "ok", 1: "a frame needed more than cap hypotheses", 2: "token tree full", 3: "no hypothesis left to expand"}
 
 
-def beam_stream_workspace_bytes(B, T, H, J, beam, cap):
-    """Bytes of the beam-search workspace for B utterances of at most T frames (include/tsasr_hip.h): per utterance a header with the
-    beam, a token tree of 1 + (T + 1) * beam + cap nodes and cap + beam predictor slots of J + 2H floats."""
-    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
-    B, T, H, J, beam, cap = (int(v) for v in (B, T, H, J, beam, cap))
-    if min(B, T, H, J, beam, cap) <= 0:
-        return 0
-    return B * (a16(64 + 24 * beam) + a16(8 * (1 + (T + 1) * beam + cap)) + 4 * (cap + beam) * (J + 2 * H))
+def beam_workspace_bytes(B, T, H, J, V, beam, cap, lm_layers=0, lm_hidden=0, times=False, bias=False, wide=False):
+    """Bytes of the beam-search workspace for B utterances of at most T frames (tsasr_beam_search_workspace_bytes, include/tsasr_hip.h,
+    the one statement of the layout): per utterance a header with the beam, a token tree of 1 + (T + 1) * beam + cap nodes and cap + beam
+    predictor slots of J + 2H floats, each with the node's LM step when ``lm_layers`` > 0; ``times`` / ``bias``: one int32 per tree node
+    more each (emission frames, trie states); ``wide``: the subword search's LM part. 0 for a shape no call takes."""
+    return C.lib().tsasr_beam_search_workspace_bytes(int(B), int(T), int(H), int(J), int(V), int(beam), int(cap), int(lm_layers),
+                                                     int(lm_hidden), int(bool(times)), int(bool(bias)), int(bool(wide)))
 
 
-def beam_stream_timed_workspace_bytes(B, T, H, J, beam, cap):
-    """Bytes of the timed searches' workspace (beam_search / beam_search_stream with ``frames=True``): the untimed layout of each
-    utterance plus one int32 per token-tree node, the frame at which the node's token was emitted."""
-    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
-    B, T, H, J, beam, cap = (int(v) for v in (B, T, H, J, beam, cap))
-    if min(B, T, H, J, beam, cap) <= 0:
-        return 0
-    return beam_stream_workspace_bytes(B, T, H, J, beam, cap) + B * a16(4 * (1 + (T + 1) * beam + cap))
-
-
-def beam_stream_lm_workspace_bytes(B, T, H, J, beam, cap, lm_layers, lm_hidden, times=False):
-    """Bytes of the LM-fused searches' workspace (``lm=``): every predictor slot also holds the node's LM step, 64 + 2 * lm_layers *
-    lm_hidden floats (lm_logp | lm_h | lm_c); ``times``: the timed layout."""
-    B, T, H, J, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, beam, cap, lm_layers, lm_hidden))
-    if min(B, T, H, J, beam, cap, Ll, Hl) <= 0:
-        return 0
-    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
-    return base + B * 4 * (cap + beam) * (64 + 2 * Ll * Hl)
-
-
-BEAM_WIDE_LDS_MAX = 156 * 1024      # dynamic LDS tsasr_beam_search_wide takes (160 KB less 4 KB for the kernel's static arrays)
-
-
-def beam_wide_workspace_bytes(B, T, H, J, V, beam, cap, lm_layers=0, lm_hidden=0, times=False):
-    """Bytes of the wide search's workspace (tsasr_beam_search_wide_workspace_bytes): the narrow layout, a slot's LM part holding
-    round_up(V, 4) + 2 * lm_layers * lm_hidden floats (lm_layers 0: no LM); ``times``: the timed layout."""
-    B, T, H, J, V, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, V, beam, cap, lm_layers, lm_hidden))
-    if min(B, T, H, J, V, beam, cap) <= 0 or Ll < 0 or (Ll > 0 and Hl <= 0):
-        return 0
-    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
-    return base + (B * 4 * (cap + beam) * ((V + 3) // 4 * 4 + 2 * Ll * Hl) if Ll > 0 else 0)
+BEAM_WIDE_LDS_MAX = 156 * 1024      # dynamic LDS tsasr_beam_search takes with wide (160 KB less 4 KB for the kernel's static arrays)
 
 
 def beam_wide_lds_bytes(H, J, E, V, cap, lm_dims=None, times=True, bias=False):
-    """Dynamic LDS of beam_search_wide_kernel (include/tsasr_hip.h); lm_dims = (emb_dim, hidden, dnn_neurons) of a fused LM; ``bias``:
+    """Dynamic LDS of beam_search_kernel's WIDE instantiations (include/tsasr_hip.h); lm_dims = (emb_dim, hidden, dnn_neurons) of a fused LM; ``bias``:
     the biased search's trie state per hypothesis, 4 * cap bytes more."""
     r4 = lambda v: (int(v) + 3) // 4 * 4  # noqa: E731
     n = 4 * (6 * H + 2 * J + r4(E) + r4(V) + 96) + int(cap) * (16 + 4 * ((7 if times else 6) + (1 if bias else 0)))
@@ -2457,19 +2438,6 @@ def beam_wide_lds_bytes(H, J, E, V, cap, lm_dims=None, times=True, bias=False):
         El, Hl, D = (int(v) for v in lm_dims)
         n += 4 * (max(El, Hl, D) + 2 * Hl + max(4 * Hl, D) + 2 * r4(V) + 2)
     return n
-
-
-def beam_bias_workspace_bytes(B, T, H, J, E, V, beam, cap, lm_layers=0, lm_hidden=0, times=False):
-    """Bytes of the biased searches' workspace (``bias=``; tsasr_beam_search_bias_workspace_bytes): the layout of the same search
-    without a graph - narrow for V <= 63 and E <= 64, wide otherwise; lm_layers 0: no LM; ``times``: timed - plus one int32 per
-    token-tree node, the trie state of the node's path."""
-    a16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
-    B, T, H, J, E, V, beam, cap, Ll, Hl = (int(v) for v in (B, T, H, J, E, V, beam, cap, lm_layers, lm_hidden))
-    if min(B, T, H, J, E, V, beam, cap) <= 0 or Ll < 0 or (Ll > 0 and Hl <= 0):
-        return 0
-    base = (beam_stream_timed_workspace_bytes if times else beam_stream_workspace_bytes)(B, T, H, J, beam, cap)
-    lm_part = ((V + 3) // 4 * 4 if (V > 63 or E > 64) else 64) + 2 * Ll * Hl if Ll > 0 else 0
-    return base + B * 4 * (cap + beam) * lm_part + B * a16(4 * (1 + (T + 1) * beam + cap))
 
 
 _BIAS_KEYS = (("child_off", torch.int32), ("child_tok", torch.int32), ("child_to", torch.int32), ("pending", torch.float64),
@@ -2500,16 +2468,6 @@ def _beam_bias_desc(bias, B, device):
     d.child_off, d.child_tok, d.child_to, d.pending = (bias[k].data_ptr() for k in ("child_off", "child_tok", "child_to", "pending"))
     d.base, d.weight, d.rows, d.edges = bias["base"].data_ptr(), bias["weight"].data_ptr(), rows, edges
     return d
-
-
-def _beam_bias_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam,
-                      slope, wdtype, fr, lm_desc, lm_weight, bias_desc):
-    """tsasr_beam_search_bias's return code: n_valid None = the offline search, fr None = untimed, lm_desc None = no LM."""
-    return C.lib().tsasr_beam_search_bias(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank),
-                                          int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
-                                          C.io_dtype(encc), wdtype, C.stream_ptr(), C.ptr(fr),
-                                          None if lm_desc is None else C.ctypes.byref(lm_desc), float(lm_weight),
-                                          None if bias_desc is None else C.ctypes.byref(bias_desc))
 
 
 _LM_KEYS = ("emb", "w_ih", "w_hh", "b_ih", "b_hh", "w_dnn", "b_dnn", "ln_g", "ln_b", "ln_eps", "w_out", "b_out", "slope", "weight")
@@ -2555,17 +2513,8 @@ def _beam_lm_desc(lm, V, wdtype):
     return d, float(lm["weight"]), nl, Hl
 
 
-def _beam_lm_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope,
-                    wdtype, fr, desc, weight, name="tsasr_beam_search_lm"):
-    """tsasr_beam_search_lm's (or, by ``name``, tsasr_beam_search_wide's: desc None = no LM) return code (0: launched): n_valid None = the
-    offline search, fr None = untimed."""
-    return getattr(C.lib(), name)(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank), int(beam_size),
-                                  int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope), C.io_dtype(encc),
-                                  wdtype, C.stream_ptr(), C.ptr(fr), None if desc is None else C.ctypes.byref(desc), float(weight))
-
-
 def _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide=False):
-    """Shapes and settings tsasr_beam_search takes, with ``wide`` those of tsasr_beam_search_wide (ValueError before any device call)."""
+    """Shapes and settings tsasr_beam_search takes, with ``wide`` those of its wide form (ValueError before any device call)."""
     emax, vmax = (1024, 1024) if wide else (64, 63)
     if not isinstance(enc, torch.Tensor) or enc.dim() != 3 or enc.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("beam_search: enc must be a float32 / bfloat16 [B, T, J] tensor")
@@ -2636,124 +2585,80 @@ def _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws):
             C.ptr(ws), ws.numel())
 
 
-def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
-                workspace=None, frames=False, lm=None, wide=False, bias=None):
-    """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
-    lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
-    n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_stream_workspace_bytes(B, T, H, J, beam_size, cap).
-    ``frames=True`` (tsasr_beam_search_timed): a fourth value, the n-best lists of the encoder frame that emitted each token; the
-    workspace then has beam_stream_timed_workspace_bytes; the first three values are the bits of the untimed call.
-    ``lm`` (tsasr_beam_search_lm): a dict of the fused LM's tensors (_beam_lm_desc) with its weight; the workspace then has
-    beam_stream_lm_workspace_bytes.
-    ``wide=True`` (tsasr_beam_search_wide, subword models): V and the embedding's columns up to 1024, beam_size <= 64; every form above
-    through the one entry point; with an LM the workspace has beam_wide_workspace_bytes. Without it the narrow limits hold (V <= 63, 64
-    embedding columns).
-    ``bias`` (tsasr_beam_search_bias): the packed phrase graphs of the batch (biasing.pack); every form above through that one entry
-    point (which picks narrow or wide by the shape: ``wide`` must say the same); the workspace has beam_bias_workspace_bytes. None:
-    the entry points and bytes above."""
-    _no_grad_only("beam_search")
+def _beam_launch(encc, ptrs, n_valid, outs, B, T, max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope,
+                 wdtype, fr, lm_desc, lm_weight, bias_desc, wide):
+    """tsasr_beam_search's return code (0: launched): n_valid None = the offline search, fr None = untimed, lm_desc None = no LM,
+    bias_desc None = no graph."""
+    return C.lib().tsasr_beam_search(C.ptr(encc), *ptrs, C.ptr(n_valid), *outs, B, T, int(max_frames), J, H, E, V, int(blank),
+                                     int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
+                                     C.io_dtype(encc), wdtype, C.stream_ptr(), C.ptr(fr),
+                                     None if lm_desc is None else C.ctypes.byref(lm_desc), float(lm_weight),
+                                     None if bias_desc is None else C.ctypes.byref(bias_desc), int(bool(wide)))
+
+
+def _beam_run(what, enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
+              workspace, n_valid, max_frames, frames, lm, wide, bias):
+    """What beam_search (``what``; n_valid None, max_frames = T, the workspace may be None: one is made) and beam_search_stream share:
+    the checks, the descriptors, the workspace's bytes and the launch, read out again when a hypothesis is longer than the first Lmax."""
     B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
-    need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, T, H, J, beam_size, cap)
-    desc, lm_weight, lm_layers, lm_hidden = None, 0.0, 0, 0
-    if lm is not None:
-        desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
-        need = (beam_wide_workspace_bytes(B, T, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
-                beam_stream_lm_workspace_bytes(B, T, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
+    stream = what == "beam_search_stream"
+    max_frames = max_frames if stream else T
+    desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype) if lm is not None else (None, 0.0, 0, 0)
     bdesc = None
     if bias is not None:
         if bool(wide) != (V > 63 or E > 64):
-            raise ValueError(f"beam_search: bias with wide={wide} but V={V}, E={E} (the biased entry point picks by V <= 63 and E <= 64)")
+            raise ValueError(f"{what}: bias with wide={wide} but V={V}, E={E} (the biased search picks by V <= 63 and E <= 64)")
         bdesc = _beam_bias_desc(bias, B, enc.device)
-        need = beam_bias_workspace_bytes(B, T, H, J, E, V, beam_size, cap, lm_layers, lm_hidden, bool(frames))
-    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < need):
-        raise ValueError(f"beam_search: workspace must be uint8 with at least {need} bytes")
-    C.require_gpu(enc, table, *mats)
+    need = beam_workspace_bytes(B, max_frames, H, J, V, beam_size, cap, lm_layers, lm_hidden, frames, bias is not None, wide)
+    if (stream or workspace is not None) and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8
+                                              or workspace.numel() < need):
+        raise ValueError(f"{what}: workspace must be uint8 with at least {need} bytes" + (f" (max_frames={max_frames})" if stream else ""))
+    if stream and (not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,)):
+        raise ValueError(f"{what}: n_valid must be a [B={B}] tensor")
+    C.require_gpu(enc, table, *mats, *((workspace, n_valid) if stream else ()))
     encc = enc.contiguous()
     ws = torch.empty(need, dtype=torch.uint8, device=enc.device) if workspace is None else workspace
+    nv = n_valid.to(torch.int32).contiguous() if stream else None
     zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
     ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, ws)
 
     def run(hyps, lens, scores, status, Lmax, readout, fr):
-        tail = (int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam), float(expand_beam), float(slope),
-                C.io_dtype(encc), wdtype, C.stream_ptr())
-        outs = (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status))
-        if bdesc is not None:
-            C.check(_beam_bias_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
-                                      state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight, bdesc), "tsasr_beam_search_bias")
-            return
-        if lm is not None or wide:
-            name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
-            C.check(_beam_lm_launch(encc, ptrs, zero if readout else None, outs, B, T, T, J, H, E, V, blank, beam_size, nbest, cap, Lmax,
-                                    state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight, name), name)
-            return
-        if frames:
-            tail += (C.ptr(fr),)
-            stream_fn, fn, sfx = C.lib().tsasr_beam_search_stream_timed, C.lib().tsasr_beam_search_timed, "_timed"
-        else:
-            stream_fn, fn, sfx = C.lib().tsasr_beam_search_stream, C.lib().tsasr_beam_search, ""
-        if readout:
-            C.check(stream_fn(C.ptr(encc), *ptrs, C.ptr(zero), *outs, B, T, T, J, H, E, V, *tail), "tsasr_beam_search_stream" + sfx)
-        else:
-            C.check(fn(C.ptr(encc), *ptrs, *outs, B, T, J, H, E, V, *tail), "tsasr_beam_search" + sfx)
+        C.check(_beam_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T, max_frames,
+                             J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr, desc, lm_weight,
+                             bdesc, wide), "tsasr_beam_search")
 
-    with prof.region("beam_search"):
-        return _beam_read(run, B, int(nbest), 2 * T + 16, enc.device, bool(frames))
+    with prof.region(what):
+        return _beam_read(run, B, int(nbest), 256 if stream else 2 * T + 16, enc.device, bool(frames))
+
+
+def beam_search(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
+                workspace=None, frames=False, lm=None, wide=False, bias=None):
+    """Beam transducer search of every utterance of enc [B,T,J] in one launch (every frame, as the reference). Returns (n-best token
+    lists, n-best fp64 scores logp / len, status int32 [B] on the host: ops.BEAM_STATUS). An utterance with a nonzero status has no
+    n-best (the caller re-decodes it). ``workspace``: uint8 of at least beam_workspace_bytes(B, T, H, J, V, beam_size, cap, the LM's
+    layers and hidden size, frames, bias is not None, wide) bytes; None: one is made.
+    ``frames=True``: a fourth value, the n-best lists of the encoder frame that emitted each token; the first three values are the bits
+    of the untimed call.
+    ``lm``: a dict of the fused LM's tensors (_beam_lm_desc) with its weight.
+    ``wide=True`` (subword models): V and the embedding's columns up to 1024, beam_size <= 64. Without it the narrow limits hold
+    (V <= 63, 64 embedding columns).
+    ``bias``: the packed phrase graphs of the batch (biasing.pack); the biased search runs narrow or wide by the shape, and ``wide``
+    must say the same. None: no graph."""
+    _no_grad_only("beam_search")
+    return _beam_run("beam_search", enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam,
+                     expand_beam, cap, workspace, None, None, frames, lm, wide, bias)
 
 
 def beam_search_stream(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam, expand_beam, cap,
                        workspace, n_valid, max_frames, frames=False, lm=None, wide=False, bias=None):
-    """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_stream_workspace_bytes(B, max_frames, ...) bytes
-    (zeroed at the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what
-    beam_search returns, for the beam after the chunk. ``frames=True`` (tsasr_beam_search_stream_timed): also the n-best frame lists,
-    absolute from the start of the stream; the workspace has beam_stream_timed_workspace_bytes and every call of the stream is timed.
-    ``lm``: as in beam_search; the workspace has beam_stream_lm_workspace_bytes and every call of the stream carries the same LM.
-    ``wide``: as in beam_search, the same for every call of the stream.
-    ``bias``: as in beam_search; the workspace has beam_bias_workspace_bytes and every call of the stream is biased (the graph of a
-    stream stays the same from its zeroed start on; the packed arrays around it may change)."""
+    """One chunk of beam search on the device: enc [B,C,J], workspace uint8 of beam_workspace_bytes(B, max_frames, ...) bytes (zeroed at
+    the start of the streams, updated in place), n_valid int32 [B] = frames of this chunk per stream. Returns what beam_search returns,
+    for the beam after the chunk. ``frames``, ``lm``, ``wide``, ``bias``: as in beam_search, the same for every call of the stream
+    (frames are absolute from the start of the stream; the graph of a stream stays the same from its zeroed start on, the packed arrays
+    around it may change)."""
     _no_grad_only("beam_search_stream")
-    B, T, J, H, E, V = _beam_check(enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, beam_size, nbest, cap, wdtype, wide)
-    need = (beam_stream_timed_workspace_bytes if frames else beam_stream_workspace_bytes)(B, max_frames, H, J, beam_size, cap)
-    desc, lm_weight, lm_layers, lm_hidden = None, 0.0, 0, 0
-    if lm is not None:
-        desc, lm_weight, lm_layers, lm_hidden = _beam_lm_desc(lm, V, wdtype)
-        need = (beam_wide_workspace_bytes(B, max_frames, H, J, V, beam_size, cap, lm_layers, lm_hidden, bool(frames)) if wide else
-                beam_stream_lm_workspace_bytes(B, max_frames, H, J, beam_size, cap, lm_layers, lm_hidden, bool(frames)))
-    bdesc = None
-    if bias is not None:
-        if bool(wide) != (V > 63 or E > 64):
-            raise ValueError(f"beam_search_stream: bias with wide={wide} but V={V}, E={E}")
-        bdesc = _beam_bias_desc(bias, B, enc.device)
-        need = beam_bias_workspace_bytes(B, max_frames, H, J, E, V, beam_size, cap, lm_layers, lm_hidden, bool(frames))
-    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need:
-        raise ValueError(f"beam_search_stream: workspace must be uint8 with at least {need} bytes (max_frames={max_frames})")
-    if not isinstance(n_valid, torch.Tensor) or tuple(n_valid.shape) != (B,):
-        raise ValueError(f"beam_search_stream: n_valid must be a [B={B}] tensor")
-    C.require_gpu(enc, table, workspace, n_valid, *mats)
-    encc = enc.contiguous()
-    nv = n_valid.to(torch.int32).contiguous()
-    zero = torch.zeros(B, dtype=torch.int32, device=enc.device)
-    ptrs = _beam_ptrs(table, mats, b_ih, b_hh, b_proj, b_head, workspace)
-
-    def run(hyps, lens, scores, status, Lmax, readout, fr):
-        if bdesc is not None:
-            C.check(_beam_bias_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,
-                                      max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr,
-                                      desc, lm_weight, bdesc), "tsasr_beam_search_bias")
-            return
-        if lm is not None or wide:
-            name = "tsasr_beam_search_wide" if wide else "tsasr_beam_search_lm"
-            C.check(_beam_lm_launch(encc, ptrs, zero if readout else nv, (C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status)), B, T,
-                                    max_frames, J, H, E, V, blank, beam_size, nbest, cap, Lmax, state_beam, expand_beam, slope, wdtype, fr,
-                                    desc, lm_weight, name), name)
-            return
-        fn, extra = (C.lib().tsasr_beam_search_stream_timed, (C.ptr(fr),)) if frames else (C.lib().tsasr_beam_search_stream, ())
-        C.check(fn(C.ptr(encc), *ptrs, C.ptr(zero if readout else nv), C.ptr(hyps), C.ptr(lens), C.ptr(scores), C.ptr(status), B, T,
-                   int(max_frames), J, H, E, V, int(blank), int(beam_size), int(nbest), int(cap), int(Lmax), float(state_beam),
-                   float(expand_beam), float(slope), C.io_dtype(encc), wdtype, C.stream_ptr(), *extra),
-                "tsasr_beam_search_stream_timed" if frames else "tsasr_beam_search_stream")
-
-    with prof.region("beam_search_stream"):
-        return _beam_read(run, B, int(nbest), 256, enc.device, bool(frames))
+    return _beam_run("beam_search_stream", enc, table, mats, b_ih, b_hh, b_proj, b_head, blank, slope, wdtype, beam_size, nbest, state_beam,
+                     expand_beam, cap, workspace, n_valid, max_frames, frames, lm, wide, bias)
 
 
 EditResult = __import__("collections").namedtuple("EditResult", ["counts", "align_op", "align_i", "align_j", "align_len", "totals"])
